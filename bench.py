@@ -11,11 +11,14 @@ fused Adam update of both grid tensors (voxe_grid_adam_step) -- so the grid real
 cached across steps.  Inputs are resident in HBM before timing.  `--optimizer split` = the same arithmetic as
 voxe_render_bwd + all-reduce + voxe_adam_step per tensor.
 
-    python bench.py [--gpus N --steps K --warmup W]           (N > 1: launched by torch.distributed.run)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0 with the `roofline` (dominant kernel, HIP-event timed on the launch
-stream through voxe_profile_*) and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded
-sample) objects described in DESIGN.md.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, the configuration).  `--full` adds everything else described in DESIGN.md: the `roofline` object
+(dominant kernel, HIP-event timed on the launch stream through voxe_profile_*), per-step and per-view device times,
+the secondary lines, the same-GPU PyTorch and the CPU oracle baselines, and the replica check of N > 1 jobs.
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy; the state the
+timed steps start from depends on the arguments only, so two runs -- or two builds -- can be compared array by array.
 """
 import argparse
 import gc
@@ -43,6 +46,37 @@ ORACLE_VS_REFERENCE_100 = 2.6
 # milliseconds, not over a fixed number of 1 ms steps -- step() runs until this much time has passed (r03's fixed 20 steps
 # = 23 ms left the driver's `--steps 20 --warmup 5` line 3 - 5 % below the builder's `--steps 100 --warmup 20`)
 PRE_WARM_MS = float(os.environ.get("VOXE_BENCH_PRE_WARM_MS", "400"))
+# --dump-outputs: at most this many rows (rays, voxels) per array -- more are written as a fixed, seeded sample of rows
+DUMP_MAX_ROWS = 1 << 20
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """`arrays`: {name: tensor whose first dimension is rays or voxels}.  Writes directory/<name>.npy in float32.  An array
+    of more than DUMP_MAX_ROWS rows is written as the rows at sorted indices drawn by a generator of fixed seed -- the same
+    rows for every array of that row count and in every run.  Every value must be finite: nothing is written otherwise.
+    Returns {name: number of rows in the file}."""
+    picks, out, total = {}, {}, 0
+    for name, t in arrays.items():
+        t = t.detach().reshape(t.shape[0], -1)
+        n = t.shape[0]
+        if n > DUMP_MAX_ROWS:
+            if n not in picks:
+                perm = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ROWS]
+                picks[n] = torch.sort(perm).values
+            t = t.index_select(0, picks[n].to(t.device))
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_BUDGET_BYTES >> 20} MB at {name}")
+        bad = int(a.size - np.isfinite(a).sum())
+        if bad:
+            raise SystemExit(f"--dump-outputs: {bad} values of {name} are not finite")
+        out[name] = a
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+    return {name: a.shape[0] for name, a in out.items()}
 
 
 def parse():
@@ -77,7 +111,18 @@ def parse():
                          "its rows (what a multi-GPU SDS iteration does: one image per step, modules/sds_trainer.py) -- same "
                          "gradient exchange")
     ap.add_argument("--no-gpu-baseline", action="store_true", help="skip timing the PyTorch restatement of the path on this GPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: roofline (per-step events, library phase timers, clock probe, PMC summary), "
+                         "per-view times, secondary lines, same-GPU and CPU baselines, replica check of N > 1 jobs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): the render outputs "
+                         "colour / depth / acc / disp of rank 0's rays (disp 0 where acc == 0) and the updated grid (densities, "
+                         "features); arrays of more "
+                         f"than {DUMP_MAX_ROWS} rows as a fixed, seeded sample of rows")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -172,10 +217,10 @@ def main():
     disp = torch.empty((R, 1), dtype=torch.float32, device=dev)
     ws = ops.Workspace()
 
-    # in-AABB sample count of this camera (un-jittered depths), outside the timed region
+    # in-AABB sample count of this camera (un-jittered depths), outside the timed region (--full: roofline, per-view figures)
     probe_params = ops.RenderParams(num_samples=S, near=NEAR, far=FAR, white_bkgd=True, image_width=hint)
     s_in_views = []
-    for ro_j, rd_j in view_rays:
+    for ro_j, rd_j in (view_rays if args.full else []):
         inside = ops.sample_probe(spec, probe_params, dens, feat, ro_j, rd_j, outputs=("inside",))["inside"]
         s_in_views.append(int(inside.sum().item()))
         del inside
@@ -195,6 +240,9 @@ def main():
         opt = ShardedGridAdam(spec, dens, feat, lr=1e-4, exercise_collectives=os.environ.get("VOXE_BENCH_FORCE_DIST") == "1",
                               exchange="reduce-scatter" if want_exchange == "auto" else want_exchange)
         exp_avg = exp_avg_sq = None   # (the split path's moments; the fused optimiser owns its own)
+    # the grid as it stands before the time-based clock-settling run, which ends after a varying number of steps: restored
+    # behind it (see reset_after_pre_warm), so that the state of the timed steps depends on the arguments only
+    flat_p_initial = flat_p.clone() if PRE_WARM_MS > 0 else None
 
     def fused_step(prm, ro, rd, outs, gcol, wsx, ev=None):
         # the gradient stays in the workspace in the backward kernel's layout; one pass then applies the chain rule of
@@ -239,6 +287,24 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def reset_after_pre_warm():
+        # device work only (no host staging, no synchronisation): the chip stays busy between the clock-settling run and
+        # the warm-up.  Grid, optimiser moments and step count (also the jitter's counter) back to their initial values,
+        # the view cycle back to view 0; the workspace re-packs the restored grid at the next forward.
+        flat_p.copy_(flat_p_initial)
+        if fused:
+            for state in (opt.state_densities, opt.state_features):
+                for moment in state or ():
+                    moment.zero_()
+            opt.steps = 0
+        else:
+            flat_g.zero_()
+            exp_avg.zero_()
+            exp_avg_sq.zero_()
+        ws.invalidate()
+        step_no[0] = 0
+        del view_of_step[:]
+
     if fused and dist is not None and want_exchange == "auto":
         # outside the timed region: one render so that the workspace exists and holds the packed grid, then dry optimiser
         # steps (zero gradient, zero moments: no parameter bit changes) through each exchange
@@ -263,15 +329,17 @@ def main():
     # (gc.collect, 1024 hipEventCreate) between the two and was still ramping back up inside the short timed region.
     gc.collect()          # like timeit: no interpreter garbage collection inside the timed steps
     gc.disable()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # (per-step events and the library's phase timers feed the --full figures only: a plain run times the steps by wall clock)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     # Kernel times of the timed steps.  A timing event on the launch stream costs ~5.5 us of device time (kernel timeline of this
     # script, profiles/r06_bench_trace.txt: gaps of 5.9 / 10.6 / 11 us wherever 1 / 2 events sit between two kernels, 0.0 us between
     # kernels with none).  The fused step therefore carries THREE events: the step mark (= start of the forward), one behind the
     # forward (= start of the backward), one behind the backward (= start of the grid step) -- the library's per-phase timers
     # (start + stop per phase: five per step with the mark, 27 us of an 0.82 ms step) stay for the split-optimiser path, whose
     # pack / memset / unpack phases they separate.
-    phase_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if fused else None
-    ops.profile_enable(True)    # (creates the library's timing events)
+    phase_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if fused and args.full else None
+    if args.full:
+        ops.profile_enable(True)    # (creates the library's timing events)
     untimed_steps, untimed_s = 0, 0.0
     if PRE_WARM_MS > 0:
         step()                                # (first call: allocations, lazy initialisation)
@@ -288,57 +356,100 @@ def main():
             untimed_s += timed_batch(n)
             untimed_steps += n
             more -= n
+        reset_after_pre_warm()
     for _ in range(args.warmup):
         step()
     if fused:   # exchange timing of the timed region only (events on the launch stream; 0 for one process)
         opt.read_exchange_ms()
         opt.exchange_ms, opt.exchange_steps = 0.0, 0
-    ops.profile_enable(not fused)
+    if args.full:
+        ops.profile_enable(not fused)
     barrier()
     del view_of_step[:]         # (the timed steps start at view 0 whatever the warm-up rendered)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        marks[i].record()
-        step(phase_ev[i] if fused else None)
-    marks[args.steps].record()
+        if marks:
+            marks[i].record()
+        step(phase_ev[i] if phase_ev else None)
+    if marks:
+        marks[args.steps].record()
     barrier()
     elapsed = time.perf_counter() - t0
-    timed_views = list(view_of_step)
-    # in-AABB samples of the launches that were timed (every view as often as it was rendered)
-    s_in_total = sum(s_in_views[v] for v in timed_views) / max(len(timed_views), 1)
     gc.enable()
-    step_ms_in_order = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
-    step_ms = sorted(step_ms_in_order)
+    timed_views = list(view_of_step)
     exchange_ms = opt.read_exchange_ms() if fused else None
-    prof = ops.profile_read()
-    ops.profile_enable(False)
-    if fused:   # (events of this script, see above: forward = mark -> first event, backward = first -> second)
-        prof = dict(prof)
-        prof.update(ms_fwd=sum(marks[i].elapsed_time(phase_ev[i][0]) for i in range(args.steps)), n_fwd=args.steps,
-                    ms_bwd=sum(phase_ev[i][0].elapsed_time(phase_ev[i][1]) for i in range(args.steps)), n_bwd=args.steps)
+    if args.full:
+        # in-AABB samples of the launches that were timed (every view as often as it was rendered)
+        s_in_total = sum(s_in_views[v] for v in timed_views) / max(len(timed_views), 1)
+        step_ms_in_order = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+        step_ms = sorted(step_ms_in_order)
+        prof = ops.profile_read()
+        ops.profile_enable(False)
+        if fused:   # (events of this script, see above: forward = mark -> first event, backward = first -> second)
+            prof = dict(prof)
+            prof.update(ms_fwd=sum(marks[i].elapsed_time(phase_ev[i][0]) for i in range(args.steps)), n_fwd=args.steps,
+                        ms_bwd=sum(phase_ev[i][0].elapsed_time(phase_ev[i][1]) for i in range(args.steps)), n_bwd=args.steps)
 
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # outside the timed region: every rank must hold the same packed grid (what the next render samples); the sharded
-    # optimiser then makes the raw parameter tensors whole again
+    # outside the timed region (--full): every rank must hold the same packed grid (what the next render samples); the
+    # sharded optimiser then makes the raw parameter tensors whole again (also for --dump-outputs)
     replicas_consistent = None
-    if dist is not None and fused:
+    if dist is not None and fused and args.full:
         packed = ops.workspace_packed_view(spec, dens, feat, ws).double()
         chk = torch.stack([packed.sum(), packed.abs().sum(), (packed * packed).sum()])
         lo_chk, hi_chk = chk.clone(), chk.clone()
         dist.all_reduce(lo_chk, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi_chk, op=dist.ReduceOp.MAX)
         replicas_consistent = bool(torch.equal(lo_chk, hi_chk))
-        opt.gather_parameters()
         del packed
+    if dist is not None and fused and (args.full or args.dump_outputs):
+        opt.gather_parameters()
 
     # sustained shader clock, measured right behind the timed region (the chip is at its working temperature / power state)
-    clock_hz = ops.clock_probe(dev)
+    clock_hz = ops.clock_probe(dev) if args.full else None
     rays_per_s = R_job * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    # what the last timed step computed: rank 0's render outputs and the grid after its optimiser step.  The disparity of a
+    # ray that gathers no opacity (acc == 0: it misses the grid) is NaN, as in the reference (0 / 0 in accumulate.py:85-88);
+    # the file holds 0 there -- the disparity of a ray that sees nothing out to infinity -- and acc.npy says which rays
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        disp_seen = torch.where(acc == 0, torch.zeros_like(disp), disp)
+        dumped = dump_outputs(args.dump_outputs, {"colour": colour, "depth": depth, "acc": acc, "disp": disp_seen,
+                                                  "densities": dens.reshape(nvox, -1), "features": feat.reshape(nvox, -1)})
+    if dist is not None and args.dump_outputs:
+        dist.barrier()
+
+    workload = (f"{G}^3 SH-0 softplus ReLU-field grid ({args.scene}), "
+                + (f"ONE {HW}x{HW} camera per step split into row bands over the GPUs, " if strong else f"one {HW}x{HW} camera per GPU and step, ") +
+                (f"the steps cycle through {n_views} cameras of the 100-view set, " if n_views > 1 else f"camera {args.camera}, ") +
+                f"S={S}, jitter {'off' if args.no_jitter else 'on'}, white bkgd, ray order {args.ray_order}; step = render fwd + bwd"
+                f"{' + RCCL all-reduce of the grid gradient' if world > 1 else ''}"
+                f"{'' if args.no_adam else (' + Adam (fused grid step)' if fused else ' + Adam')}")
+    if not args.full:
+        out = None
+        if rank == 0:
+            out = {
+                "metric": "rendered rays/sec (fwd+bwd)", "value": round(rays_per_s, 1), "unit": "rays/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+                "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "config": {
+                    "workload": workload, "grid": G, "image": [HW, HW], "samples_per_ray": S, "rays_per_gpu_per_step": R,
+                    "views": {"count": n_views, "cameras_of_rank0": view_cams},
+                    "grad_exchange": (opt.mode if fused else ("all-reduce" if dist is not None else "none")),
+                    "rows_of_rank0": list(rows), "backend": (backend if dist is not None else None),
+                    "exchange_ms_per_step": (round(exchange_ms, 4) if exchange_ms is not None else None),
+                    "term_eps": args.term_eps, "optimizer": ("none" if args.no_adam else ("fused" if fused else "split")),
+                    "untimed_warmup_ms": round(1e3 * untimed_s, 1), "untimed_steps_before_timing": untimed_steps + args.warmup,
+                },
+                "outputs": dumped,
+            }
+        finish(dist, out)
+        return
 
     # ---- roofline of the dominant kernel (HIP events on the launch stream, voxe_profile_*) -------------
     ms_fwd = prof["ms_fwd"] / max(prof["n_fwd"], 1)
@@ -901,7 +1012,7 @@ def main():
                       f"threads = {dt * threads:.0f} core-seconds",
         }
 
-    views_report = None
+    views_report, out = None, None
     if rank == 0:
         by_view = {}
         for v, ms in zip(timed_views, step_ms_in_order):
@@ -926,12 +1037,7 @@ def main():
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             "config": {
-                "workload": f"{G}^3 SH-0 softplus ReLU-field grid ({args.scene}), "
-                            + (f"ONE {HW}x{HW} camera per step split into row bands over the GPUs, " if strong else f"one {HW}x{HW} camera per GPU and step, ") +
-                            (f"the steps cycle through {n_views} cameras of the 100-view set, " if n_views > 1 else f"camera {args.camera}, ") +
-                            f"S={S}, jitter {'off' if args.no_jitter else 'on'}, white bkgd, ray order {args.ray_order}; step = render fwd + bwd"
-                            f"{' + RCCL all-reduce of the grid gradient' if world > 1 else ''}"
-                            f"{'' if args.no_adam else (' + Adam (fused grid step)' if fused else ' + Adam')}",
+                "workload": workload,
                 "grid": G, "image": [HW, HW], "samples_per_ray": S, "rays_per_gpu_per_step": R,
                 # r06 (the single headline camera was the fastest of seven): the timed steps cycle through
                 # `count` cameras of the 100-view set, so `value` IS the mean over views; per view (rank 0): device time between
@@ -950,11 +1056,16 @@ def main():
                 "untimed_warmup_ms": round(1e3 * untimed_s, 1), "untimed_steps_before_timing": untimed_steps + args.warmup,
             },
             "roofline": roofline, "secondary": secondary,
-            "gpu_baseline": gpu_baseline, "cpu_baseline": cpu_baseline,
+            "gpu_baseline": gpu_baseline, "cpu_baseline": cpu_baseline, "outputs": dumped,
         }
+    finish(dist, out)
+
+
+def finish(dist, out):
+    """ends the process group; rank 0 (`out` is not None) prints the result line"""
     if dist is not None:
         dist.destroy_process_group()
-    if rank == 0:
+    if out is not None:
         # RCCL writes a version banner through C stdio; flush it first so the JSON is the LAST line
         import ctypes
 

@@ -29,7 +29,7 @@ def test_two_rank_bench_on_one_gpu(exchange, expect):
     env = dict(os.environ, VOXE_BENCH_BACKEND="gloo", VOXE_GRAD_EXCHANGE=exchange, VOXE_BENCH_PRE_WARM_MS="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--grid", "32", "--image", "96", "--samples", "64"]
+           "--grid", "32", "--image", "96", "--samples", "64", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=560)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [l for l in res.stdout.strip().splitlines() if l.startswith("{")][-1]
@@ -52,7 +52,7 @@ def test_two_rank_strong_scaling_bench_on_one_gpu():
     env = dict(os.environ, VOXE_BENCH_BACKEND="gloo", VOXE_GRAD_EXCHANGE="reduce-scatter", VOXE_BENCH_PRE_WARM_MS="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--grid", "32", "--image", "100", "--samples", "64", "--scaling", "strong"]
+           "--grid", "32", "--image", "100", "--samples", "64", "--scaling", "strong", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=560)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([l for l in res.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -106,7 +106,7 @@ def test_default_bench_line_has_the_contract_fields():
     summary that belongs to these kernel sources (not stale), the CPU / same-GPU baselines; r06: the steps cycle through 20 cameras
     of the 100-view set (value = mean over views) and `roofline.frac` is the utilisation of the ceiling that binds (<= 1)"""
     env = dict(os.environ, VOXE_BENCH_PRE_WARM_MS="20")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--cpu-sample", "40"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--cpu-sample", "40", "--full"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=560)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.strip().splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@ var=$1; shift
 vals=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do vals+=("$1"); shift; done
 [ "${1:-}" == "--" ] && shift
 for v in "${vals[@]}"; do
-  env $var=$v python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary "$@" 2>/dev/null | tail -1 > /tmp/ab_line.json
+  env $var=$v python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary "$@" 2>/dev/null | tail -1 > /tmp/ab_line.json
   python - "$var=$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_line.json"))

@@ -4,7 +4,7 @@
 for round in 1 2; do
 for tag in "$@"; do
   lib=""; [ "$tag" != "base" ] && lib=variants/libvoxe_hip_$tag.so
-  r=$(VOXE_HIP_LIB=$lib python bench.py --no-cpu-baseline --steps 60 --warmup 5 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['secondary']['ms_per_step'])")
+  r=$(VOXE_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --steps 60 --warmup 5 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['secondary']['ms_per_step'])")
   echo "$tag: $r"
 done
 done
