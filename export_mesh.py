@@ -1,0 +1,52 @@
+#!/usr/bin/env python3
+"""Export the density iso-surface of a trained, edited or refined voxel grid as a closed, coloured triangle mesh (binary
+PLY, opens in Blender / MeshLab / slicers).  Marching cubes runs on the GPU (vox-e_amd/csrc/voxe_mesh.hip); vertex
+colours are the diffuse (DC) colour of the field at each vertex.  --edit_region_only keeps the voxels a refined model
+marks as its edit region (keep-grid value 0) and caps the mesh where that region cuts the object."""
+import os
+import sys
+import time
+from pathlib import Path
+
+import click
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "vox-e_amd"))
+
+from thre3d_atom.modules.volumetric_model import create_volumetric_model_from_saved_model_attn  # noqa: E402
+from thre3d_atom.thre3d_reprs.constants import STATE_DICT, THRE3D_REPR, u_ATTN  # noqa: E402
+from thre3d_atom.thre3d_reprs.mesh import default_level, extract_mesh, save_ply  # noqa: E402
+from thre3d_atom.thre3d_reprs.voxels import create_voxel_grid_from_saved_info_dict_attn  # noqa: E402
+
+
+@click.command()
+@click.option("-i", "--model_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="path to the trained / edited / refined model")
+@click.option("-o", "--output_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="output mesh (.ply)")
+@click.option("--level", type=click.FLOAT, default=None,
+              help="iso-level of the (post-activated) density; default ln 2 / voxel size: a one-voxel slab absorbs half the light")
+@click.option("--edit_region_only", is_flag=True, default=False, help="refined models: mesh only the edit region (keep grid == 0)")
+def main(**kwargs) -> None:
+    cfg = type("Config", (), kwargs)
+    device = torch.device("cuda")
+    path = Path(cfg.model_path)
+    has_attn = u_ATTN in torch.load(path, map_location="cpu", weights_only=False)[THRE3D_REPR][STATE_DICT]
+    if cfg.edit_region_only and not has_attn:
+        raise click.UsageError(f"{path} holds no keep grid (attn): --edit_region_only needs a refined model")
+    vol_mod, _ = create_volumetric_model_from_saved_model_attn(path, create_voxel_grid_from_saved_info_dict_attn, device=device,
+                                                               load_attn=has_attn)
+    grid = vol_mod.thre3d_repr
+    mask = (grid.attn.detach()[..., 0] == 0) if cfg.edit_region_only else None
+    level = cfg.level if cfg.level is not None else default_level(grid)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    mesh = extract_mesh(grid, level=level, mask=mask)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3
+    out = Path(cfg.output_path)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    save_ply(mesh, out)
+    print(f"level {level:.6g}: V = {len(mesh.vertices)}  T = {len(mesh.faces)}  extract {ms:.2f} ms  -> {out}")
+
+
+if __name__ == "__main__":
+    main()

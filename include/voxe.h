@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VOXE_ABI_VERSION 12
+#define VOXE_ABI_VERSION 13
 
 typedef enum VoxeStatus {
   VOXE_OK = 0,
@@ -622,6 +622,30 @@ size_t voxe_cc_scratch_bytes(int32_t X, int32_t Y, int32_t Z, int32_t k);
 int voxe_cc_largest_k(const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t k,
                       int32_t* labels, int32_t* num_components,
                       void* scratch, size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh export (ABI v13): marching cubes over the density iso-surface, DESIGN.md section 4 "Mesh export".
+ *   v_i = pre(density_scale * densities[i]) per voxel, 0 where mask[i] == 0 (mask u8 [X,Y,Z], NULL = none); the padded
+ *   lattice has nodes at voxel indices -1..N per axis (0 outside the grid).  The surface is trilerp(v) = L with
+ *   L = post^-1(level) (Identity / ReLU: level; Softplus: level > 20 ? level : log(expm1(level))), i.e. where the
+ *   un-masked density VoxelGrid.forward returns equals `level`; level must exceed post(0) (0, or ln 2 for Softplus), so
+ *   that the zero-padded ring is outside and every surface is closed (VOXE_ERR_BAD_SHAPE otherwise).  A node is inside
+ *   iff v > L.  Only `densities`, the dims and the density activation fields of the descriptor are read.
+ *   voxe_mesh_count: totals (DEVICE int64[2]) = (V, T); the case per node and the scan offsets stay in scratch
+ *                    (>= voxe_mesh_scratch_bytes(X, Y, Z) bytes) for voxe_mesh_emit.
+ *   voxe_mesh_emit : same grid, level, mask and scratch, on the same stream, after voxe_mesh_count:
+ *                    vertices f32 [V,3] in world space: one per crossing lattice edge, numbered by (node, axis), at
+ *                    t = (L - v_a) / (v_b - v_a) along the edge; faces int32 [T,3] numbered by (cell, table order),
+ *                    counter-clockwise seen from outside (normals toward lower density).  Nothing is written past
+ *                    max_vertices / max_faces (a grid changed since the count gives a wrong mesh, never a bad access).
+ *   Deterministic: the output is the same bit for bit from run to run.  (X+2)(Y+2)(Z+2) * 5 (the table's most triangles per
+ *   cell) must stay below 2^31 (VOXE_ERR_BAD_SHAPE otherwise).  Feature kind SH or attention; the features are not read.         */
+size_t voxe_mesh_scratch_bytes(int32_t X, int32_t Y, int32_t Z);
+int voxe_mesh_count(const VoxeGridDesc* grid, float level, const uint8_t* mask, int64_t* totals,
+                    void* scratch, size_t scratch_bytes, void* stream);
+int voxe_mesh_emit(const VoxeGridDesc* grid, float level, const uint8_t* mask,
+                   float* vertices, int64_t max_vertices, int32_t* faces, int64_t max_faces,
+                   void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.

@@ -1313,4 +1313,58 @@ int voxe_cc_largest_k(const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int3
   return finish();
 }
 
+// ---- mesh export ---------------------------------------------------------------------------------------------------
+namespace {
+// L = post^-1(level) in the pre-post domain; false when level <= post(0) (the zero-padded ring would not be outside)
+bool mesh_iso_value(int post, float level, float* L) {
+  if (!(level < INFINITY)) return false;   // (NaN, +inf)
+  if (post == VOXE_ACT_SOFTPLUS) {
+    if (!(level > 0.693147182464599609375f)) return false;   // softplus(0) in float
+    *L = level > 20.0f ? level : (float)log(expm1((double)level));
+    return *L > 0.0f;
+  }
+  if (!(level > 0.0f)) return false;
+  *L = level;
+  return true;
+}
+
+int validate_mesh(const VoxeGridDesc* g, float level, void* scratch, size_t scratch_bytes, float* L) {
+  if (!g || !g->densities) return VOXE_ERR_NULL_POINTER;
+  if (!mesh_dims_ok(g->X, g->Y, g->Z)) return VOXE_ERR_BAD_SHAPE;
+  if (g->feature_kind != VOXE_FEAT_SH && g->feature_kind != VOXE_FEAT_ATTN) return VOXE_ERR_UNSUPPORTED;
+  if (g->density_pre_act != VOXE_ACT_IDENTITY && g->density_pre_act != VOXE_ACT_ABS) return VOXE_ERR_UNSUPPORTED;
+  if (g->density_post_act != VOXE_ACT_IDENTITY && g->density_post_act != VOXE_ACT_RELU &&
+      g->density_post_act != VOXE_ACT_SOFTPLUS)
+    return VOXE_ERR_UNSUPPORTED;
+  if (!mesh_iso_value(g->density_post_act, level, L)) return VOXE_ERR_BAD_SHAPE;
+  if (!scratch || scratch_bytes < mesh_scratch_bytes(g->X, g->Y, g->Z)) return VOXE_ERR_WORKSPACE;
+  return VOXE_OK;
+}
+}  // namespace
+
+size_t voxe_mesh_scratch_bytes(int32_t X, int32_t Y, int32_t Z) {
+  return mesh_dims_ok(X, Y, Z) ? mesh_scratch_bytes(X, Y, Z) : 0;
+}
+
+int voxe_mesh_count(const VoxeGridDesc* grid, float level, const uint8_t* mask, int64_t* totals, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (!totals) return VOXE_ERR_NULL_POINTER;
+  float L;
+  const int st = validate_mesh(grid, level, scratch, scratch_bytes, &L);
+  if (st) return st;
+  launch_mesh_count(grid, L, mask, totals, scratch, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_mesh_emit(const VoxeGridDesc* grid, float level, const uint8_t* mask, float* vertices, int64_t max_vertices,
+                   int32_t* faces, int64_t max_faces, void* scratch, size_t scratch_bytes, void* stream) {
+  if (max_vertices < 0 || max_faces < 0) return VOXE_ERR_BAD_SHAPE;
+  if ((max_vertices > 0 && !vertices) || (max_faces > 0 && !faces)) return VOXE_ERR_NULL_POINTER;
+  float L;
+  const int st = validate_mesh(grid, level, scratch, scratch_bytes, &L);
+  if (st) return st;
+  launch_mesh_emit(grid, L, mask, vertices, max_vertices, faces, max_faces, scratch, (hipStream_t)stream);
+  return finish();
+}
+
 }  // extern "C"

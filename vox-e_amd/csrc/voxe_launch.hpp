@@ -189,4 +189,11 @@ size_t cc_scratch_bytes(int X, int Y, int Z, int k);
 void launch_cc_largest_k(const uint8_t* mask, int X, int Y, int Z, int k, int32_t* labels, int32_t* ncomp,
                          void* scratch, hipStream_t stream);
 
+// voxe_mesh.hip: marching-cubes export of the density iso-surface (L = the pre-post iso-value, validated by the API)
+bool mesh_dims_ok(int X, int Y, int Z);   // (X+2)(Y+2)(Z+2) nodes: every vertex / triangle id fits an int32
+size_t mesh_scratch_bytes(int X, int Y, int Z);
+void launch_mesh_count(const VoxeGridDesc* g, float L, const uint8_t* mask, int64_t* totals, void* scratch, hipStream_t st);
+void launch_mesh_emit(const VoxeGridDesc* g, float L, const uint8_t* mask, float* vertices, long long max_vertices,
+                      int32_t* faces, long long max_faces, void* scratch, hipStream_t st);
+
 }  // namespace voxe

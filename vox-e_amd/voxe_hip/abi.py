@@ -7,7 +7,7 @@ shares the same signatures minus (workspace, stream).
 """
 import ctypes as C
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # VoxeStatus
 OK = 0
@@ -213,6 +213,10 @@ HIP_ONLY = {
     "cc_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "profile_enable": (C.c_int, [C.c_int32]),
     "profile_read": (C.c_int, [C.POINTER(VoxeProfile)]),
+    # mesh export (ABI v13)
+    "mesh_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "mesh_count": (C.c_int, [_GD, C.c_float, _P, _P, _P, C.c_size_t, _P]),
+    "mesh_emit": (C.c_int, [_GD, C.c_float, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
 }
 
 CPU_ONLY = {

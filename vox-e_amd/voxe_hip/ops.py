@@ -1129,3 +1129,45 @@ def profile_read() -> dict:
     p = abi.VoxeProfile()
     check(lib().voxe_profile_read(C.byref(p)), "voxe_profile_read")
     return {name: getattr(p, name) for name, _ in abi.VoxeProfile._fields_}
+
+
+# ------------------------------------------------------------------------------------------------
+# mesh export (marching cubes over the density iso-surface; DESIGN.md section 4 "Mesh export")
+# ------------------------------------------------------------------------------------------------
+def extract_mesh(spec: GridSpec, densities: torch.Tensor, level: float,
+                 mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Closed, outward-wound triangle mesh of {density == level} on the device: vertices [V,3] float32 (world space),
+    faces [T,3] int32.  `mask` ([X,Y,Z] or [X,Y,Z,1], bool / uint8, 0 = excluded) turns voxels into outside.  The count
+    pass's totals are read back once (one synchronisation) to size the outputs."""
+    require_device(densities, "extract_mesh (densities)")
+    if densities.dim() != 4 or densities.shape[-1] != 1:
+        raise VoxeError(f"extract_mesh: densities must be [X,Y,Z,1]; got {tuple(densities.shape)}")
+    dens = f32c(densities.detach())
+    device = dens.device
+    X, Y, Z = (int(s) for s in dens.shape[:3])
+    m = None
+    if mask is not None:
+        require_device(mask, "extract_mesh (mask)")
+        if tuple(mask.shape[:3]) != (X, Y, Z) or mask.numel() != X * Y * Z:
+            raise VoxeError(f"extract_mesh: mask must be [X,Y,Z]=({X},{Y},{Z}); got {tuple(mask.shape)}")
+        m = (mask.reshape(X, Y, Z) != 0).to(torch.uint8).contiguous()
+    ensure_gfx950(device)
+    L = lib()
+    g = make_grid_desc(dens.data_ptr(), dens.data_ptr(), (X, Y, Z), 1, spec.aabb, spec.density_scale,
+                       spec.density_pre_act, spec.density_post_act, spec.feature_kind)
+    with torch.cuda.device(device):
+        nbytes = L.voxe_mesh_scratch_bytes(X, Y, Z)
+        if nbytes == 0:
+            raise VoxeError(f"extract_mesh: grid {X}x{Y}x{Z} is too large for int32 vertex / triangle ids")
+        sc = _scratch_for(device, nbytes)
+        totals = torch.empty(2, dtype=torch.int64, device=device)
+        st = stream_ptr(device)
+        check(L.voxe_mesh_count(C.byref(g), float(level), ptr(m), ptr(totals), ptr(sc), sc.numel(), st), "voxe_mesh_count")
+        V, T = (int(v) for v in totals.cpu())
+        if V >= 2 ** 31 or T >= 2 ** 31:
+            raise VoxeError(f"extract_mesh: {V} vertices / {T} triangles exceed int32 ids")
+        vertices = torch.empty((V, 3), dtype=torch.float32, device=device)
+        faces = torch.empty((T, 3), dtype=torch.int32, device=device)
+        check(L.voxe_mesh_emit(C.byref(g), float(level), ptr(m), ptr(vertices), V, ptr(faces), T, ptr(sc), sc.numel(), st),
+              "voxe_mesh_emit")
+    return vertices, faces
