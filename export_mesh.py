@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Export the density iso-surface of a trained, edited or refined voxel grid as a closed, coloured triangle mesh (binary
 PLY, opens in Blender / MeshLab / slicers).  Marching cubes runs on the GPU (vox-e_amd/csrc/voxe_mesh.hip); vertex
-colours are the diffuse (DC) colour of the field at each vertex.  --edit_region_only keeps the voxels a refined model
+colours are the diffuse (DC) colour of the field at each vertex; --vertex_normals adds unit density-gradient normals (smooth
+shading, vox-e_amd/csrc/voxe_normals.hip).  --edit_region_only keeps the voxels a refined model
 marks as its edit region (keep-grid value 0) and caps the mesh where that region cuts the object."""
 import os
 import sys
@@ -15,6 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "vox
 
 from thre3d_atom.modules.volumetric_model import create_volumetric_model_from_saved_model_attn  # noqa: E402
 from thre3d_atom.thre3d_reprs.constants import STATE_DICT, THRE3D_REPR, u_ATTN  # noqa: E402
+from thre3d_atom.thre3d_reprs.geometry import vertex_normals  # noqa: E402
 from thre3d_atom.thre3d_reprs.mesh import default_level, extract_mesh, save_ply  # noqa: E402
 from thre3d_atom.thre3d_reprs.voxels import create_voxel_grid_from_saved_info_dict_attn  # noqa: E402
 
@@ -25,6 +27,7 @@ from thre3d_atom.thre3d_reprs.voxels import create_voxel_grid_from_saved_info_di
 @click.option("--level", type=click.FLOAT, default=None,
               help="iso-level of the (post-activated) density; default ln 2 / voxel size: a one-voxel slab absorbs half the light")
 @click.option("--edit_region_only", is_flag=True, default=False, help="refined models: mesh only the edit region (keep grid == 0)")
+@click.option("--vertex_normals", is_flag=True, default=False, help="write unit vertex normals (nx ny nz) from the density gradient")
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
     device = torch.device("cuda")
@@ -40,11 +43,12 @@ def main(**kwargs) -> None:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     mesh = extract_mesh(grid, level=level, mask=mask)
+    normals = vertex_normals(grid, mesh.vertices) if cfg.vertex_normals else None
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3
     out = Path(cfg.output_path)
     out.parent.mkdir(parents=True, exist_ok=True)
-    save_ply(mesh, out)
+    save_ply(mesh, out, normals=normals)
     print(f"level {level:.6g}: V = {len(mesh.vertices)}  T = {len(mesh.faces)}  extract {ms:.2f} ms  -> {out}")
 
 

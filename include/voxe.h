@@ -648,6 +648,32 @@ int voxe_mesh_emit(const VoxeGridDesc* grid, float level, const uint8_t* mask,
                    void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Density-gradient normals (additive; still ABI v13), DESIGN.md section 4 "Normals".
+ *   The field is the mesh export's: v_i = pre(density_scale * densities[i]), V(p) its trilinear interpolant (grid_sample
+ *   semantics, zero padding), u_a = ((p_a * scale_a + bias_a + 1) * N_a - 1) / 2 as in the renderer, the cell floor(u).
+ *   G_a(p) = dV/du_a * (N_a * norm_scale_a / 2): the derivative of exactly what VoxelGrid.forward evaluates in that cell
+ *   (corners outside the grid count as 0, also for the slope at the faces), in world units.  n(p) = -G / |G| in f32,
+ *   (0,0,0) where G == 0: toward lower density, outward on a solid (the side the mesh export's faces wind toward).
+ *   voxe_query_normals : points [N,3] (world) -> normals [N,3] = n(p); points outside the grid give (0,0,0).
+ *   voxe_render_normals: per ray r, normals [R,3] = sum_k w_k n(p_k) (world space, NOT renormalised: |N_r| <= acc_r, no
+ *                        background, white_bkgd does not apply), depth [R,1] = sum_k w_k z_k, acc [R,1] = sum_k w_k (either
+ *                        may be NULL), with the points p_k and weights w_k = T_k alpha_k of voxe_render_fwd for the same rays,
+ *                        cfg and jitter / (seed, rng_offset).  cfg fields honoured: num_samples, near, far, perturb,
+ *                        linear_disparity, aabb_clip, seed, rng_offset; image_width / image_height only choose the ray -> thread
+ *                        mapping (pixel tiles when they describe R exactly, linear order otherwise).  Every other field
+ *                        (white_bkgd, sh_degree, render_diffuse, term_eps, reuse_packed_grid, deterministic, linear_grad,
+ *                        ray_state_valid, dispatch) is ignored.
+ *   Only grid->densities ([X,Y,Z,1]) is read: features, F and feature_kind are ignored (features may be NULL), so SH and
+ *   attention grid descriptors both work.  No workspace: nothing is packed, no forward record is read or dropped, no
+ *   voxe_recon_prefetch hint is touched.  Caller's stream, no host synchronisation, no allocation, no atomics: the same bits
+ *   on every run.  Pointers may be NULL when N / R is 0 (VOXE_OK, no launch); R and the voxel count stay below 2^31 and the
+ *   grid within validate's 24-bit index limits (VOXE_ERR_BAD_SHAPE otherwise), as does num_samples <= 0.            */
+int voxe_query_normals(const VoxeGridDesc* grid, const float* points, int64_t N, float* normals, void* stream);
+int voxe_render_normals(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                        const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                        float* normals, float* depth, float* acc, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.
  * ---------------------------------------------------------------------------------------------- */

@@ -1367,4 +1367,60 @@ int voxe_mesh_emit(const VoxeGridDesc* grid, float level, const uint8_t* mask, f
   return finish();
 }
 
+
+// ---- density-gradient normals ------------------------------------------------------------------------
+// the grid checks of validate_grid_only() for a call that reads `densities` only (features / F / feature_kind are ignored)
+static int validate_normals_grid(const VoxeGridDesc* g) {
+  if (!g || !g->densities) return VOXE_ERR_NULL_POINTER;
+  if (g->X <= 0 || g->Y <= 0 || g->Z <= 0) return VOXE_ERR_BAD_SHAPE;
+  if ((long long)g->X * g->Y * g->Z >= (1LL << 31)) return VOXE_ERR_BAD_SHAPE;
+  if ((long long)g->X * g->Y >= (1LL << 24) || (long long)g->Y * g->Z >= (1LL << 24) || g->Z >= (1 << 24)) return VOXE_ERR_BAD_SHAPE;
+  if (g->density_pre_act != VOXE_ACT_IDENTITY && g->density_pre_act != VOXE_ACT_ABS) return VOXE_ERR_UNSUPPORTED;
+  if (g->density_post_act != VOXE_ACT_IDENTITY && g->density_post_act != VOXE_ACT_RELU &&
+      g->density_post_act != VOXE_ACT_SOFTPLUS)
+    return VOXE_ERR_UNSUPPORTED;
+  return VOXE_OK;
+}
+
+int voxe_query_normals(const VoxeGridDesc* grid, const float* points, int64_t N, float* normals, void* stream) {
+  const int st = validate_normals_grid(grid);
+  if (st) return st;
+  if (N < 0) return VOXE_ERR_BAD_SHAPE;
+  if (N > 0 && (!points || !normals)) return VOXE_ERR_NULL_POINTER;
+  if (N == 0) return VOXE_OK;
+  DevGrid dg;
+  grid_to_dev(grid, &dg);
+  launch_query_normals(dg, grid->densities, points, N, normals, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_render_normals(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
+                        const float* jitter, float* normals, float* depth, float* acc, void* stream) {
+  const int st = validate_normals_grid(grid);
+  if (st) return st;
+  if (!cfg) return VOXE_ERR_NULL_POINTER;
+  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  if (R > 0 && (!rays_o || !rays_d || !normals)) return VOXE_ERR_NULL_POINTER;
+  if (R == 0) return VOXE_OK;
+  DevGrid dg;
+  grid_to_dev(grid, &dg);
+  DevCfg dc;
+  memset(&dc, 0, sizeof(dc));
+  // the sampling fields make_dev() copies, with make_dev()'s expressions: the forward's depths and jitter stream
+  dc.S = cfg->num_samples;
+  dc.near = cfg->near; dc.far = cfg->far;
+  dc.perturb = cfg->perturb; dc.lindisp = cfg->linear_disparity; dc.aabb_clip = cfg->aabb_clip;
+  dc.key0 = (uint32_t)cfg->seed ^ ((uint32_t)cfg->rng_offset * 0x9E3779B1u);
+  dc.key1 = (uint32_t)(cfg->seed >> 32) ^ (uint32_t)(cfg->rng_offset >> 32) ^ 0x7F4A7C15u;
+  dc.R = R;
+  // image order (pixel tiles) only when the image fields describe R exactly; otherwise (or when absent) linear order
+  const int64_t W = cfg->image_width, H = cfg->image_height > 0 ? cfg->image_height : (W > 0 ? R / W : 0);
+  if (W > 0 && H > 0 && H <= INT32_MAX && R % (W * H) == 0) {
+    dc.image_width = (int)W;
+    dc.image_height = (int)H;
+  }
+  launch_render_normals(dg, dc, grid->densities, rays_o, rays_d, jitter, normals, depth, acc, (hipStream_t)stream);
+  return finish();
+}
+
 }  // extern "C"

@@ -196,4 +196,10 @@ void launch_mesh_count(const VoxeGridDesc* g, float L, const uint8_t* mask, int6
 void launch_mesh_emit(const VoxeGridDesc* g, float L, const uint8_t* mask, float* vertices, long long max_vertices,
                       int32_t* faces, long long max_faces, void* scratch, hipStream_t st);
 
+// voxe_normals.hip: density-gradient normals; both read the raw densities only, no workspace
+int normals_lanes_for(long long R);   // lanes per ray of the render kernel (1, 2, 4 or 8)
+void launch_query_normals(const DevGrid& g, const float* dens, const float* points, long long N, float* normals, hipStream_t st);
+void launch_render_normals(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
+                           const float* jitter, float* normals, float* depth, float* acc, hipStream_t st);
+
 }  // namespace voxe

@@ -53,19 +53,26 @@ def extract_mesh(voxel_grid: VoxelGrid, level: Optional[float] = None, mask: Opt
     return Mesh(vertices, faces, colours)
 
 
-def save_ply(mesh: Mesh, path: Union[str, Path]) -> None:
-    """binary little-endian PLY: float x y z, uchar red green blue per vertex; a uchar-counted int32 list per face"""
+def save_ply(mesh: Mesh, path: Union[str, Path], normals: Optional[Tensor] = None) -> None:
+    """binary little-endian PLY: float x y z (then float nx ny nz when `normals` [V,3] is given, e.g.
+    geometry.vertex_normals), uchar red green blue per vertex; a uchar-counted int32 list per face"""
     v = mesh.vertices.detach().cpu().numpy().astype("<f4")
     f = mesh.faces.detach().cpu().numpy().astype("<i4")
     c = np.clip(np.rint(mesh.colours.detach().cpu().numpy().astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+    n = None if normals is None else normals.detach().cpu().numpy().astype("<f4").reshape(-1, 3)
+    if n is not None and len(n) != len(v):
+        raise ValueError(f"save_ply: {len(n)} normals for {len(v)} vertices")
     header = (
         "ply\nformat binary_little_endian 1.0\ncomment vox-e mesh export\n"
         f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
-        "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        + ("" if n is None else "property float nx\nproperty float ny\nproperty float nz\n")
+        + "property uchar red\nproperty uchar green\nproperty uchar blue\n"
         f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n"
     )
-    vrec = np.empty(len(v), dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    vrec = np.empty(len(v), dtype=[("xyz", "<f4", 3)] + ([] if n is None else [("nxyz", "<f4", 3)]) + [("rgb", "u1", 3)])
     vrec["xyz"], vrec["rgb"] = v, c
+    if n is not None:
+        vrec["nxyz"] = n
     frec = np.empty(len(f), dtype=[("n", "u1"), ("idx", "<i4", 3)])
     frec["n"], frec["idx"] = 3, f
     with open(path, "wb") as fh:

@@ -217,6 +217,9 @@ HIP_ONLY = {
     "mesh_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "mesh_count": (C.c_int, [_GD, C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "mesh_emit": (C.c_int, [_GD, C.c_float, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
+    # density-gradient normals (additive, still ABI v13)
+    "query_normals": (C.c_int, [_GD, _P, C.c_int64, _P, _P]),
+    "render_normals": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
 }
 
 CPU_ONLY = {

@@ -1171,3 +1171,69 @@ def extract_mesh(spec: GridSpec, densities: torch.Tensor, level: float,
         check(L.voxe_mesh_emit(C.byref(g), float(level), ptr(m), ptr(vertices), V, ptr(faces), T, ptr(sc), sc.numel(), st),
               "voxe_mesh_emit")
     return vertices, faces
+
+
+# ------------------------------------------------------------------------------------------------
+# density-gradient normals (DESIGN.md section 4 "Normals"): read the raw densities only, no workspace, not differentiable
+# ------------------------------------------------------------------------------------------------
+def _normals_grid_desc(spec: GridSpec, dens: torch.Tensor):
+    X, Y, Z = (int(s) for s in dens.shape[:3])
+    # (features, F and feature_kind are not read by the normals entry points: no feature tensor is needed)
+    return make_grid_desc(dens.data_ptr(), 0, (X, Y, Z), 0, spec.aabb, spec.density_scale, spec.density_pre_act,
+                          spec.density_post_act, spec.feature_kind)
+
+
+def _check_densities(densities: torch.Tensor, what: str) -> None:
+    require_device(densities, f"{what} (densities)")
+    if densities.dim() != 4 or densities.shape[-1] != 1:
+        raise VoxeError(f"{what}: densities must be [X,Y,Z,1]; got {tuple(densities.shape)}")
+
+
+def query_normals(spec: GridSpec, densities: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+    """n(p) = -grad V / |grad V| at world points [N,3] -> [N,3] float32 ((0,0,0) where the gradient vanishes, e.g. outside the
+    grid).  V is the trilinear pre-activated density VoxelGrid.forward interpolates; no gradient flows through the result."""
+    _check_densities(densities, "query_normals")
+    require_device(points, "query_normals (points)")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise VoxeError(f"query_normals: points must be [N,3]; got {tuple(points.shape)}")
+    device = densities.device
+    ensure_gfx950(device)
+    dens, pts = f32c(densities.detach()), f32c(points.detach().to(device))
+    g = _normals_grid_desc(spec, dens)
+    N = pts.shape[0]
+    with torch.cuda.device(device):
+        out = torch.empty((N, 3), dtype=torch.float32, device=device)
+        check(lib().voxe_query_normals(C.byref(g), ptr(pts), N, ptr(out), stream_ptr(device)), "voxe_query_normals")
+    return out
+
+
+def render_normals(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                   jitter: Optional[torch.Tensor] = None, rng: Optional[Tuple[int, int]] = None):
+    """Rendered normals of flat rays: (normals [R,3] = sum_k w_k n(p_k) in world space, not renormalised; depth [R,1];
+    acc [R,1]) with the samples and weights `render` uses for the same params, jitter and rng (`rng` follows render's rule:
+    None = a fresh stream when params.perturb and no jitter is given).  The background and white_bkgd do not apply.
+    Not differentiable."""
+    _check_densities(densities, "render_normals")
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+        require_device(t, f"render_normals ({name})")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_o.shape != rays_d.shape:
+        raise VoxeError(f"rays must be flat [R,3]; got {tuple(rays_o.shape)}, {tuple(rays_d.shape)}")
+    if jitter is not None and tuple(jitter.shape) != (rays_o.shape[0], params.num_samples):
+        raise VoxeError(f"jitter must be [R,S]={rays_o.shape[0], params.num_samples}; got {tuple(jitter.shape)}")
+    if rng is None:
+        rng = _next_rng() if (params.perturb and jitter is None) else (0, 0)
+    device = densities.device
+    ensure_gfx950(device)
+    dens, ro, rd = f32c(densities.detach()), f32c(rays_o.detach()), f32c(rays_d.detach())
+    jit = None if jitter is None else f32c(jitter.detach())
+    g = _normals_grid_desc(spec, dens)
+    c = make_render_cfg(params.num_samples, params.near, params.far, params.perturb, params.linear_disparity, params.aabb_clip,
+                        seed=rng[0], rng_offset=rng[1], image_width=params.image_width, image_height=params.image_height)
+    R = ro.shape[0]
+    with torch.cuda.device(device):
+        normals = torch.empty((R, 3), dtype=torch.float32, device=device)
+        depth = torch.empty((R, 1), dtype=torch.float32, device=device)
+        acc = torch.empty((R, 1), dtype=torch.float32, device=device)
+        check(lib().voxe_render_normals(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), ptr(normals), ptr(depth),
+                                        ptr(acc), stream_ptr(device)), "voxe_render_normals")
+    return normals, depth, acc
