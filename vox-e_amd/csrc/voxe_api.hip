@@ -115,7 +115,7 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // workspace = [ packed grid | packed gradient | per-ray depth-segment states ]
 struct WsLayout {
-  size_t packed_off, grad_off, state_off, seg_off, prec_off, src_off, fwdval_off, planar_off, det_off, region_off, fwd_total, total, total_with_src;
+  size_t packed_off, grad_off, state_off, seg_off, prec_off, sched_off, src_off, fwdval_off, planar_off, det_off, region_off, fwd_total, total, total_with_src;
   bool region;   // the space-binned backward applies to (grid, cfg, R): its scratch is part of the workspace
 };
 WsLayout ws_layout(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R) {
@@ -139,7 +139,10 @@ WsLayout ws_layout(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R) {
   const bool precise = c && disp_of(c).precise_grad > 0 && c->image_width > 0 && cout == 3;
   const size_t prec = precise ? align_up((size_t)nseg * 5 * (size_t)(R > 0 ? R : 0) * sizeof(double), 256) : 0;
   l.prec_off = bytes + gbytes + state + seg;
-  l.total = bytes + gbytes + state + seg + prec;
+  // cost-ordered block list of the lean tile kernels, next to the states it is valid with
+  const size_t sched = c ? align_up(tile_sched_bytes(R, c->image_width, c->image_height, c->num_samples), 256) : 0;
+  l.sched_off = bytes + gbytes + state + seg + prec;
+  l.total = bytes + gbytes + state + seg + prec + sched;
   // per-sample gradient sources of the two-phase backward of view-dependent grids (optional: without it the channel
   // groups re-march the segment)
   l.src_off = l.total;
@@ -180,7 +183,7 @@ int finish() { return hipGetLastError() == hipSuccess ? VOXE_OK : VOXE_ERR_LAUNC
 // a depth-segmented march (nseg > 1), one segment per task, the lean forward's own conditions.  Everywhere else (S <= one segment,
 // fwd_segments_per_thread > 1, caller jitter, AABB clip, ...) the backward runs its default suffix arithmetic.
 bool precise_sums_apply(const WsLayout& l, const DevGrid& dg, const HostCfg& dc, const VoxeRenderCfg* cfg, const float* jitter) {
-  if (!(l.total > l.prec_off) || cfg->sh_degree != 0 || dc.attn) return false;
+  if (!(l.sched_off > l.prec_off) || cfg->sh_degree != 0 || dc.attn) return false;
   if (num_segments(cfg->num_samples, dc.seg_len) <= 1 || dc.disp.fwd_segments_per_thread > 1) return false;
   FwdArgs probe{};
   probe.jitter = jitter;
@@ -369,6 +372,24 @@ int voxe_random_subset(int64_t n, int64_t count, uint64_t seed, uint64_t rng_off
   return finish();
 }
 
+// test aid (not part of voxe.h): where the cost-ordered block list of the lean tile kernels lives in the workspace of this render --
+// out = (1 when launches of this configuration build one, byte offset, blocks of a launch, tile slots of a launch)
+int voxe_tile_sched_debug_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, int64_t out[4]) {
+  Variant v;
+  const int st = validate(grid, cfg, R, &v);
+  if (st) return st;
+  if (!out) return VOXE_ERR_NULL_POINTER;
+  DevGrid dg; HostCfg dc;
+  make_dev(grid, cfg, R, v, &dg, &dc);
+  const WsLayout l = ws_layout(grid, cfg, R);
+  const int64_t ntp = dc.image_width > 0 ? blocks_for_tiles(dc.map_mode, (dc.image_width + 7) / 8, tile_rows_total(dc, 8)) : 0;
+  out[0] = (l.total > l.sched_off && tile_sched_applies(dc)) ? 1 : 0;
+  out[1] = (int64_t)l.sched_off;
+  out[2] = ntp * num_segments(dc.S, dc.seg_len);
+  out[3] = ntp;
+  return VOXE_OK;
+}
+
 size_t voxe_workspace_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
   if (!grid || grid->X <= 0 || grid->Y <= 0 || grid->Z <= 0 || grid->F <= 0) return 0;
   const WsLayout l = ws_layout(grid, cfg, R);
@@ -409,6 +430,7 @@ int voxe_render_fwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const fl
   FwdArgs a{packed, rays_o, rays_d, jitter, colour, depth, acc, disparity, state, segbuf};
   a.keep_samples = cfg->ray_state_valid >= 0;
   if (segbuf && cfg->ray_state_valid >= 0 && precise_sums_apply(l, dg, dc, cfg, jitter)) a.segsum_d = (double*)((char*)workspace + l.prec_off);
+  if (segbuf && l.total > l.sched_off) a.sched = (int*)((char*)workspace + l.sched_off);
   if (cfg->ray_state_valid >= 0 && tiled && l.fwdval_off > l.src_off && workspace_bytes >= l.total_with_src && !two_phase_disabled(dc.disp))
     a.sample_fwd = (float*)((char*)workspace + l.fwdval_off);   // (what render_bwd_common's two-phase backward will read)
   if (l.region && workspace_bytes >= l.total_with_src) {
@@ -452,6 +474,9 @@ int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
               want_d, want_f, (tiled || packed_bwd) ? state : nullptr};
     const bool precise = precise_sums_apply(l, dg, dc, cfg, jitter);
     if (precise) a.segsum_d = (const double*)((char*)workspace + l.prec_off);
+    // (the forward of these rays -- voxe_render_fwd with this workspace or the re-march below -- built the list whenever it ran
+    // the lean forward)
+    if (l.total > l.sched_off) a.sched = (const int*)((char*)workspace + l.sched_off);
     const bool two_phase = tiled && l.fwdval_off > l.src_off && workspace_bytes >= l.total_with_src && !two_phase_disabled(dc.disp);
     if (two_phase) {
       a.sample_src = (float*)((char*)workspace + l.src_off);
@@ -490,6 +515,7 @@ int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
                 (float*)((char*)workspace + l.seg_off)};
       if (two_phase) f.sample_fwd = (float*)((char*)workspace + l.fwdval_off);
       if (precise) f.segsum_d = (double*)((char*)workspace + l.prec_off);
+      if (l.total > l.sched_off) f.sched = (int*)((char*)workspace + l.sched_off);
       launch_fwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, f, s);
     }
     PhaseTimer t(PH_BWD, s);

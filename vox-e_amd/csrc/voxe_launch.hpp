@@ -21,6 +21,9 @@ struct FwdArgs {
   // VoxeDispatch::precise_grad (lean tile kernels): per (segment, component, ray) the segment-LOCAL sums (csum[3], asum, dsum) of
   // the forward accumulated in double over the exact products (nullable)
   double* segsum_d = nullptr;
+  // cost-ordered block list of the lean tile kernels (tile_sched_bytes(); nullable): the lean forward builds it for itself and
+  // for the backward of the same rays
+  int* sched = nullptr;
 };
 struct BwdArgs {
   const float *packed, *rays_o, *rays_d, *jitter, *colour, *depth, *acc, *d_colour, *d_depth, *d_acc;
@@ -35,6 +38,7 @@ struct BwdArgs {
   unsigned long long* gdet = nullptr;
   float* det_scale = nullptr;
   const double* segsum_d = nullptr;   // FwdArgs::segsum_d of the forward of the SAME rays (VoxeDispatch::precise_grad), or null
+  const int* sched = nullptr;         // FwdArgs::sched of the forward of the SAME rays, or null
 };
 // Launch-constant device config + the dispatch decisions of THIS call (VoxeRenderCfg::dispatch, NULL = all defaults): kernels
 // take the DevCfg base by value, host-side predicates and launchers read `disp` through the accessors below (0 = default).
@@ -108,6 +112,10 @@ void launch_bwd_tile4_dep(const DevGrid& g, const HostCfg& c, const BwdArgs& a, 
                           float fit_lat, hipStream_t st);
 bool fwd_tile4_supported(const DevGrid& g, const HostCfg& c, const FwdArgs& a, int cout, int ncm);
 void launch_fwd_tile4(const DevGrid& g, const HostCfg& c, const FwdArgs& a, hipStream_t st);
+// cost-ordered block list of the lean kernels: does a launch of this configuration use one, and its bytes in the
+// workspace for R image-ordered rays (0: never)
+bool tile_sched_applies(const HostCfg& c);
+size_t tile_sched_bytes(long long R, int W, int H, int S);
 // LDS-staged forward for SH-0 image-ordered renders: writes the per-segment partials into a.segbuf (the caller then runs
 // the ordinary combine pass)
 bool fwd_tile_supported(const DevGrid& g, const HostCfg& c, int cout, int ncm);

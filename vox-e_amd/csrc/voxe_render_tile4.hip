@@ -77,7 +77,188 @@ struct Tile4Args {
   const float4* sample_src;
   int ngrp, ng;
   long long nvox;
+  const int* sched;       // cost-ordered block list of this launch (build_tile_sched), or null: blocks run in launch order
 };
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Cost-ordered block list of the lean forward and backward.  A launch is one one-wave block per (pixel tile,
+// depth segment), handed out in block order onto a fixed number of wave slots; what a block costs is the number of wave
+// iterations of its march, the in-volume sample span [kmin, kmax] of the tile's 64 rays inside the segment.  In launch order
+// (segment-major) the last blocks to start are the exit-side partial segments with 1 .. seg_len iterations, and the launch drains
+// for as long as the longest of them.  The list holds the same blocks, longest first: block b of the launch does the work of
+// launch-order block list[b].  Blocks are sorted by buckets of VOXE_SCHED_BUCKET iterations with a STABLE counting sort (histogram,
+// scan, scatter: a pure function of rays and configuration), so inside a bucket the depth-coherent launch order survives.  Blocks
+// without a sample come last with bit 31 set: the forward still owes their segment records, the backward owes nothing.
+// Built on the launch stream in front of the lean forward, into the workspace; valid exactly as long as the depth-segment states
+// next to it (same rays, same configuration).
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int kSchedMaxBuckets = 9;           // 0 (empty) + ceil(32 / 4)
+constexpr int kSchedMaxSegs = 64;             // depth segments of a launch that builds a list
+constexpr int kSchedEmpty = (int)0x80000000;  // list entry: a block without a sample inside the volume
+constexpr long long kSchedMaxBlocks = 1ll << 18;   // (every scatter block reads the launch's whole histogram: 0.6 bytes per block)
+// bucket width in wave iterations: 4, the schedule model's knee (tools/schedule_model.py); 8 for A/B builds (tools/variants.py)
+#ifndef VOXE_SCHED_BUCKET
+#define VOXE_SCHED_BUCKET 4
+#endif
+static_assert(VOXE_SCHED_BUCKET >= 4 && 32 / VOXE_SCHED_BUCKET + 1 <= kSchedMaxBuckets, "bucket rows of the schedule histogram");
+
+// this lane's sample range inside the depth segment [ks, ke] (empty: k_lo > k_hi) -- the render kernels' and the schedule's
+// common notion of which samples of a ray a block marches
+template <class RC>
+__device__ __forceinline__ void seg_sample_range(const RC& rc, const bool alive, const int ks, const int ke, int& k_lo, int& k_hi) {
+  k_lo = max(rc.k_lo, ks);
+  k_hi = alive ? min(rc.k_hi, ke) : k_lo - 1;
+}
+// bucket rank of a block of `it` wave iterations: 0 = the longest bucket ... nbk - 1 = no sample at all
+__device__ __forceinline__ int sched_rank(int it, int nbk) {
+  return it == 0 ? nbk - 1 : nbk - 1 - min((it + VOXE_SCHED_BUCKET - 1) / VOXE_SCHED_BUCKET, nbk - 1);
+}
+
+// Pass 1: wave iterations of every (tile slot, segment) of the launch -- one wave per tile slot, the render kernels' own ray
+// mapping, 16 tile slots per block -- and, per segment, how many of the block's 16 slots fall into each bucket:
+// hist[rank][segment * ngrp + group] (bytes; group = this block).  (segment, group) ascending is the launch order.
+__global__ __launch_bounds__(1024) void tile_sched_cost_kernel(const DevGrid g, const DevCfg c, const float* __restrict__ rays_o,
+                                                               const float* __restrict__ rays_d, const int ntp, const int nbk,
+                                                               const int hstride, unsigned char* __restrict__ cost,
+                                                               unsigned char* __restrict__ hist) {
+  __shared__ unsigned char rk[kSchedMaxSegs][16];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int rb = blockIdx.x * 16 + w;
+  const int nseg = num_segments(c.S, c.seg_len);
+  const int ntx = (c.image_width + 7) >> 3, nty = (int)tile_rows_total(c, 8);
+  const int tile = rb < ntp ? logical_tile_of(c, rb, ntp, ntx, nty) : -1;
+  if (tile < 0) {   // (wave-uniform) launch padding: blocks without work; slots behind the launch: in no bucket
+    for (int seg = lane; seg < nseg; seg += 64) {
+      if (rb < ntp) cost[(long long)seg * ntp + rb] = 0;
+      rk[seg][w] = rb < ntp ? (unsigned char)(nbk - 1) : (unsigned char)255;
+    }
+  } else {
+    const int ty = tile / ntx, tx = tile - ty * ntx;
+    long long r_px;
+    const bool alive = tile_pixel_ray(c, ty, lane >> 3, (tx << 3) + (lane & 7), 8, r_px);
+    const long long r = alive ? r_px : 0;
+    RayCtx<3, 1, 1> rc;
+    rc.init(g, c, r, rays_o, rays_d, nullptr);
+    for (int seg = 0; seg < nseg; ++seg) {
+      const int ks = seg * c.seg_len, ke = min(c.S, ks + c.seg_len) - 1;
+      int k_lo, k_hi;
+      seg_sample_range(rc, alive, ks, ke, k_lo, k_hi);
+      const bool has = k_lo <= k_hi;
+      const int kmin = wave_min_i32(has ? k_lo : INT_MAX);
+      const int kmax = wave_max_i32(has ? k_hi : -1);
+      const int it = kmin <= kmax ? kmax - kmin + 1 : 0;
+      if (lane == 0) {
+        cost[(long long)seg * ntp + rb] = (unsigned char)it;
+        rk[seg][w] = (unsigned char)sched_rank(it, nbk);
+      }
+    }
+  }
+  __syncthreads();
+  const int ngrp = gridDim.x;
+  for (int p = threadIdx.x; p < nseg * nbk; p += 1024) {
+    const int seg = p / nbk, r = p - seg * nbk;
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) n += rk[seg][i] == r ? 1 : 0;
+    hist[(long long)r * hstride + seg * ngrp + blockIdx.x] = (unsigned char)n;
+  }
+}
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// Pass 2: stable counting sort of the launch's blocks by bucket, longest first.  Block (chunk, segment) places the 256 blocks
+// [chunk * 256, chunk * 256 + 256) of that segment: behind every block of a longer bucket and behind the blocks of its own
+// bucket that come earlier in launch order (pass 1's histogram, groups [0, segment * ngrp + 16 chunk)), in launch order among
+// themselves (ballots).  No atomics: the list is a pure function of the costs.
+__global__ __launch_bounds__(256) void tile_sched_scatter_kernel(const unsigned char* __restrict__ cost,
+                                                                 const unsigned char* __restrict__ hist, const int ntp,
+                                                                 const int ngrp, const int nbk, const int hstride,
+                                                                 int* __restrict__ list) {
+  __shared__ int s_tot[kSchedMaxBuckets], s_pre[kSchedMaxBuckets], s_base[kSchedMaxBuckets];
+  __shared__ int s_wc[kSchedMaxBuckets][4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int seg = blockIdx.y, nseg = gridDim.y;
+  const int H = nseg * ngrp;                         // histogram entries per bucket
+  const int G0 = seg * ngrp + blockIdx.x * 16;       // groups in front of this block's
+  for (int r = w; r < nbk; r += 4) {                 // bucket r: all entries, and those in front of G0
+    const unsigned int* row = reinterpret_cast<const unsigned int*>(hist + (long long)r * hstride);   // (hstride: a multiple of 4)
+    int tot = 0, pre = 0;
+    for (int q = lane; q * 4 < H; q += 64) {
+      const unsigned int v = row[q];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int e = 4 * q + i, n = (int)(v >> (8 * i) & 255u);
+        tot += e < H ? n : 0;
+        pre += e < G0 ? n : 0;
+      }
+    }
+    tot = wave_sum_i32(tot); pre = wave_sum_i32(pre);
+    if (lane == 0) { s_tot[r] = tot; s_pre[r] = pre; }
+  }
+  const int rb = blockIdx.x * 256 + tid;
+  const bool valid = rb < ntp;
+  const int b = seg * ntp + rb;
+  const int it = valid ? (int)cost[b] : 0;
+  const int rank = valid ? sched_rank(it, nbk) : -1;
+  int within = 0, mine = 0;
+  for (int r = 0; r < nbk; ++r) {
+    const unsigned long long m = __ballot(rank == r);
+    if (rank == r) within = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == r) mine = __popcll(m);
+  }
+  if (lane < nbk) s_wc[lane][w] = mine;
+  __syncthreads();
+  if (tid < nbk) {
+    int base = s_pre[tid];
+    for (int r = 0; r < tid; ++r) base += s_tot[r];
+    s_base[tid] = base;
+  }
+  __syncthreads();
+  if (valid) {
+    int pos = s_base[rank] + within;
+    for (int i = 0; i < w; ++i) pos += s_wc[rank][i];
+    list[pos] = it == 0 ? (b | kSchedEmpty) : b;
+  }
+}
+
+// The cost order pays where a launch runs several rounds of waves (400x400: 20 000 blocks on 3 072 / 5 120 slots).  Below the
+// size at which the backward turns a tile's parts into sibling blocks (launch_bwd_tile_t: 11 000 tile-segments) the launch is
+// about one round and the order cannot help; the two extra kernels would only cost.  VoxeDispatch::tile_map 1 - 3 name a static
+// block -> tile map and keep it exactly; 4 asks for the cost order at every launch size (tests, A/B runs).
+bool tile_sched_applies(const HostCfg& c) {
+  if ((c.disp.tile_map != 0 && c.disp.tile_map != 4) || c.image_width <= 0 || c.attn || c.disp.fwd_segments_per_thread > 1) return false;
+  const int nseg = num_segments(c.S, c.seg_len);
+  const long long tiles = (long long)((c.image_width + 7) / 8) * tile_rows_total(c, 8);
+  const long long nb = (long long)blocks_for_tiles(c.map_mode, (c.image_width + 7) / 8, tile_rows_total(c, 8)) * nseg;
+  return nseg > 1 && nseg <= kSchedMaxSegs && c.seg_len <= 32 && (tiles * nseg > 11000 || c.disp.tile_map == 4) && nb <= kSchedMaxBlocks;
+}
+// workspace of a launch of ntp tile slots x nseg segments: [list: nb ints | cost: nb bytes | histogram: buckets x hstride bytes]
+static long long sched_hist_stride(long long ntp, int nseg) { return ((ntp + 15) / 16 * nseg + 3) / 4 * 4; }
+static long long sched_cost_bytes(long long nb) { return (nb + 15) / 16 * 16; }
+size_t tile_sched_bytes(long long R, int W, int H1, int S) {
+  if (W <= 0 || R <= 0) return 0;
+  const long long H = H1 > 0 ? H1 : R / W, nimg = R / (H * W);
+  const long long ntp = (((W + 7) / 8) * ((H + 7) / 8) * (nimg > 0 ? nimg : 1) + 7) / 8 * 8;
+  const int nseg = num_segments(S, seg_len_for(R));
+  const long long nb = ntp * nseg;
+  if (nb > kSchedMaxBlocks) return 0;
+  return (size_t)nb * sizeof(int) + (size_t)sched_cost_bytes(nb) + (size_t)(kSchedMaxBuckets * sched_hist_stride(ntp, nseg));
+}
+static void build_tile_sched(const DevGrid& g, const HostCfg& c, const float* rays_o, const float* rays_d, int* sched, hipStream_t st) {
+  const int nseg = num_segments(c.S, c.seg_len);
+  const int ntp = blocks_for_tiles(c.map_mode, (c.image_width + 7) / 8, tile_rows_total(c, 8));
+  const int nb = ntp * nseg;
+  unsigned char* cost = reinterpret_cast<unsigned char*>(sched + nb);
+  unsigned char* hist = cost + sched_cost_bytes(nb);
+  const int nbk = (c.seg_len + VOXE_SCHED_BUCKET - 1) / VOXE_SCHED_BUCKET + 1;
+  const int ngrp = (ntp + 15) / 16, hstride = (int)sched_hist_stride(ntp, nseg);
+  tile_sched_cost_kernel<<<ngrp, 1024, 0, st>>>(g, c, rays_o, rays_d, ntp, nbk, hstride, cost, hist);
+  tile_sched_scatter_kernel<<<dim3((ntp + 255) / 256, nseg), 256, 0, st>>>(cost, hist, ntp, ngrp, nbk, hstride, sched);
+}
 
 // what a deposit pass multiplies the sample's sources with (this lane's ray, this block's channel group):
 // window channel s = A * mA[s] + B * mB[s] with A / B two of (d rad_0, d rad_1, d rad_2, d v) -- a group of four consecutive
@@ -865,6 +1046,15 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
   __shared__ double win[WinMap<KL, 4>::kDoubles];
   __shared__ int2 tab[kTabKeys];
   const int lane = threadIdx.x;
+  // cost-ordered launches (Tile4Args::sched): this block does the work of launch-order block sched[blockIdx.x]; a block without
+  // a sample inside the volume has nothing to do
+  int bid = blockIdx.x;
+  if constexpr (!DEP) {
+    if (a_in.sched) {
+      bid = a_in.sched[blockIdx.x];
+      if (bid < 0) return;   // (wave-uniform)
+    }
+  }
   for (int i = lane; i < WinMap<KL, 4>::kDoubles; i += 64) win[i] = 0.0;
 
   // ---- block -> ([channel group,] pixel tile, depth segment[, part]): the block order of render_bwd_tile_kernel ----------
@@ -872,13 +1062,13 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
   const int ntx = (W + 7) >> 3, nty = (int)tile_rows_total(c, 8);
   const int nseg = num_segments(c.S, c.seg_len);
   const int ntp = gridDim.x / (nseg * a_in.qsplit * (DEP ? a_in.ngrp : 1));
-  int part = blockIdx.x / ntp;
+  int part = bid / ntp;
   int grp = 0;
   if constexpr (DEP) { grp = part / (nseg * a_in.qsplit); part -= grp * nseg * a_in.qsplit; }
   Tile4Args a = a_in;
   if constexpr (DEP) a.gpacked = a_in.gpacked + (long long)grp * a_in.nvox * 4;   // the group's plane of the staging gradient
   const int quad = part / nseg, seg = part - quad * nseg;
-  const int tile = logical_tile_of(c, blockIdx.x % ntp, ntp, ntx, nty);
+  const int tile = logical_tile_of(c, bid % ntp, ntp, ntx, nty);
   if (tile < 0) return;  // launch padding (wave-uniform)
   const int ks = seg * c.seg_len, ke = min(c.S, ks + c.seg_len) - 1;
   const int ty = tile / ntx, tx = tile - ty * ntx;
@@ -1017,8 +1207,8 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
   // lanes of one ray (bwd4_march)
   auto run_pass = [&](const bool alive_q, const int centre_lane, const int centre_lane2, auto ph_tag, const int phase, const int xm1, const int xm2) {
     constexpr int PH = decltype(ph_tag)::value;
-    const int k_lo = max(rc.k_lo, ks);
-    int k_hi = alive_q ? min(rc.k_hi, ke) : k_lo - 1;
+    int k_lo, k_hi;
+    seg_sample_range(rc, alive_q, ks, ke, k_lo, k_hi);
     bool has = k_lo <= k_hi;
     if (has && seg > 0 && c.term_eps > 0.0f) {   // gradient truncation: nothing behind T < term_eps receives a gradient
       if (a.ray_state[ray_state_index(seg, 0, 6, c.R, r)] < c.term_eps) { has = false; k_hi = k_lo - 1; }
@@ -1209,8 +1399,8 @@ __global__ __launch_bounds__(64, VOXE_FWD4_LB) void render_fwd_tile4_kernel(cons
     }
   }
   const int ks = seg * c.seg_len, ke = min(c.S, ks + c.seg_len) - 1;
-  const int k_lo = max(rc.k_lo, ks);
-  const int k_hi = alive ? min(rc.k_hi, ke) : k_lo - 1;
+  int k_lo, k_hi;
+  seg_sample_range(rc, alive, ks, ke, k_lo, k_hi);
   const bool has = k_lo <= k_hi;
   const int kmin = wave_min_dpp(has ? k_lo : INT_MAX);
   const int kmax = -wave_min_dpp(has ? -k_hi : INT_MAX);
@@ -1564,14 +1754,17 @@ __global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_kernel(co
                                                                               const float* __restrict__ rays_d,
                                                                               float* __restrict__ segbuf, double* __restrict__ segsum,
                                                                               const float fit_lat, const float fit_m, const float zdom,
-                                                                              const float max_adv) {
+                                                                              const float max_adv, const int* __restrict__ sched) {
   constexpr int COUT = 3, NC = COUT + 3;
   __shared__ float4 tex[kF4Ring * 64];
   __shared__ int4 org[kF4Table];
   const int lane = threadIdx.x;
   const int nseg = num_segments(c.S, c.seg_len);
   const int nrb = gridDim.x / nseg;                    // tile slots (segment-major block order, like render_fwd_seg_kernel)
-  const int seg = blockIdx.x / nrb, rb = blockIdx.x - seg * nrb;
+  // cost-ordered launches: the work of launch-order block sched[blockIdx.x] (bit 31: no sample inside the volume -- its rays
+  // still get their identity segment records below)
+  const int bid = sched ? (sched[blockIdx.x] & 0x7fffffff) : (int)blockIdx.x;
+  const int seg = bid / nrb, rb = bid - seg * nrb;
   const int W = c.image_width;
   const int ntx = (W + 7) >> 3, nty = (int)tile_rows_total(c, 8);
   const int tile = logical_tile_of(c, rb, nrb, ntx, nty);
@@ -1619,8 +1812,8 @@ __global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_kernel(co
       }
     }
   }
-  const int k_lo = max(rc.k_lo, ks);
-  const int k_hi = alive ? min(rc.k_hi, ke) : k_lo - 1;
+  int k_lo, k_hi;
+  seg_sample_range(rc, alive, ks, ke, k_lo, k_hi);
   const bool has = k_lo <= k_hi;
   const int kmin = wave_min_dpp(has ? k_lo : INT_MAX);
   const int kmax = -wave_min_dpp(has ? -k_hi : INT_MAX);
@@ -1663,12 +1856,16 @@ bool fwd_tile4_supported(const DevGrid& g, const HostCfg& c, const FwdArgs& a, i
 void launch_fwd_tile4(const DevGrid& g, const HostCfg& c, const FwdArgs& a, hipStream_t st) {
   const int nseg = num_segments(c.S, c.seg_len);
   const int nb = blocks_for_tiles(c.map_mode, (c.image_width + 7) / 8, tile_rows_total(c, 8)) * nseg;
+  // the cost-ordered block list of these rays: built here for the windowed forward AND for the lean backward of the same rays,
+  // whichever forward kernel of this function runs (launch_bwd_tile4 counts on it under the same condition)
+  int* const sched = (a.sched && tile_sched_applies(c)) ? a.sched : nullptr;
+  if (sched) build_tile_sched(g, c, a.rays_o, a.rays_d, sched, st);
   if (c.attn) render_fwd_tile4_kernel<1, false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr);
   else if (c.disp.fwd_window >= 0 && (reinterpret_cast<uintptr_t>(a.packed) & 15) == 0) {   // r06: corners from an LDS window of the tile's texels
     const float fit_lat = disp_or(c.disp.fwd_fit_lat, 5.5f), fit_m = disp_or(c.disp.fwd_fit_m, (float)kF4Ring - 1.5f);
     const float zdom = disp_or(c.disp.fwd_zdom, VOXE_FWD4W_ZDOM), max_adv = disp_or(c.disp.fwd_max_adv, 1.7f);
-    if (a.segsum_d) render_fwd_tile4w_kernel<true><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, a.segsum_d, fit_lat, fit_m, zdom, max_adv);
-    else render_fwd_tile4w_kernel<false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr, fit_lat, fit_m, zdom, max_adv);
+    if (a.segsum_d) render_fwd_tile4w_kernel<true><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, a.segsum_d, fit_lat, fit_m, zdom, max_adv, sched);
+    else render_fwd_tile4w_kernel<false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr, fit_lat, fit_m, zdom, max_adv, sched);
   }
   else if (a.segsum_d) render_fwd_tile4_kernel<3, true><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, a.segsum_d);
   else render_fwd_tile4_kernel<3, false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr);
@@ -1739,6 +1936,7 @@ void launch_bwd_tile4_dep(const DevGrid& g, const HostCfg& c, const BwdArgs& a, 
   t.qsplit = qsplit; t.fit_m = fit_m; t.fit_lat = fit_lat; t.want_d = 1; t.want_f = 1;
   t.segsum = nullptr; t.phases = -1;
   t.sample_src = reinterpret_cast<const float4*>(a.sample_src);
+  t.sched = nullptr;
   const int cm = 3 * ncu + 1;
   t.ngrp = ngrp; t.ng = cm; t.nvox = (long long)g.X * g.Y * g.Z;
   (void)hipMemsetAsync(a.grad_planar, 0, tile_planar_bytes(t.nvox, cm), st);
@@ -1758,6 +1956,9 @@ void launch_bwd_tile4(const DevGrid& g, const HostCfg& c, const BwdArgs& a, int 
   t.d_colour = a.d_colour; t.d_depth = a.d_depth; t.d_acc = a.d_acc; t.ray_state = a.ray_state; t.gpacked = a.gpacked;
   t.qsplit = qsplit; t.fit_m = fit_m; t.fit_lat = fit_lat; t.want_d = a.want_d ? 1 : 0; t.want_f = a.want_f ? 1 : 0;
   t.segsum = a.segsum_d; t.phases = c.disp.tile_phases;
+  // the forward of these rays left its cost-ordered block list next to the depth-segment states (launch_fwd_tile4, same
+  // condition); sibling-part launches (qsplit 4) have another block count and keep the launch order
+  t.sched = (a.sched && qsplit == 1 && tile_sched_applies(c)) ? a.sched : nullptr;
   if (a.segsum_d) {   // VoxeDispatch::precise_grad
     if (kl == 10) render_bwd_tile4_kernel<10, true><<<nb, 64, 0, st>>>(g, c, t);
     else render_bwd_tile4_kernel<8, true><<<nb, 64, 0, st>>>(g, c, t);

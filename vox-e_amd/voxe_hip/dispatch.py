@@ -27,7 +27,8 @@ from . import abi
 class Dispatch:
     """field for field `VoxeDispatch`; 0 = the shipped default everywhere"""
     bwd_mode: int = 0                # 0 auto | 1 plain global-atomic scatter | 2 line-dense scatter
-    tile_map: int = 0                # 0 auto | 1 interleave | 2 band | 3 rows
+    tile_map: int = 0                # 0 auto (lean tile kernels: cost-ordered blocks on large launches) | 1 interleave | 2 band | 3 rows
+                                     # (1 - 3: that static map, launch order) | 4 cost order at every launch size
     tile_min_rays: int = 0           # 0 = 8192 | > 0 | -1: no minimum (small images through the LDS-window backward)
     tile_two_phase: int = 0          # 0 default | -1 single-kernel channel groups
     tile_qsplit: int = 0             # 0 auto | 1 | 4
@@ -83,7 +84,7 @@ def from_env() -> Dispatch:
         kw["bwd_mode"] = 1
     elif mode == "packed":
         kw["bwd_mode"] = 2
-    tmap = {"interleave": 1, "band": 2, "rows": 3}.get(os.environ.get("VOXE_TILE_MAP", ""))
+    tmap = {"interleave": 1, "band": 2, "rows": 3, "cost": 4}.get(os.environ.get("VOXE_TILE_MAP", ""))
     if tmap:
         kw["tile_map"] = tmap
     v = _env_int("VOXE_TILE_MIN_RAYS")
