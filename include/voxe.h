@@ -674,6 +674,36 @@ int voxe_render_normals(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
                         float* normals, float* depth, float* acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-voxel visibility (additive; still ABI v13), DESIGN.md section 4 "Visibility".
+ *   voxe_visibility_accumulate: the samples p_k, depths z_k, inside test and weights w_k = T_k alpha_k (T_k: the transmittance
+ *       on arrival at sample k) are those of voxe_render_fwd / voxe_render_normals for the same rays, cfg and jitter / (seed,
+ *       rng_offset); the cfg fields honoured and ignored are those of voxe_render_normals.  For every sample that passes the
+ *       strict AABB test and each of its 8 footprint corners c inside the grid, with the forward's gather weight
+ *       t_c = (wx * wy) * wz:
+ *           max_weight[c] = max(max_weight[c], w_k * t_c)
+ *           max_trans[c]  = max(max_trans[c],  T_k)            where t_c > 0
+ *       (contributions <= 0 or NaN are skipped).  The call ACCUMULATES into max_weight / max_trans (f32 [X,Y,Z], either may be
+ *       NULL): the caller zeroes them before the first call, and their contents must be finite and >= 0.  Both NULL or R == 0:
+ *       VOXE_OK, no launch.  Two properties are part of the contract:
+ *         - order independence, bit for bit: non-negative floats order like their bit patterns, the update is an unsigned
+ *           integer atomic max, so the result does not depend on how lanes, waves or launches meet on a voxel;
+ *         - what a ray contributes depends on that ray and cfg only -- not on R, the ray's position in the batch or
+ *           image_width / image_height (those only choose the ray -> thread mapping): K cameras in one launch, K launches,
+ *           linear and shuffled order all give the same bits.
+ *       Only grid->densities is read; no workspace, no forward record, no voxe_recon_prefetch hint is touched.  Caller's
+ *       stream, no host synchronisation, no allocation.  Validation, the limits on R and the voxel count and the error codes
+ *       are those of voxe_render_normals.
+ *   voxe_visibility_mask: mask[i] (u8 [X,Y,Z]) = 1 iff some voxel j of the grid within Chebyshev distance `dilate` of i has
+ *       vis[j] > threshold, else 0.  The comparison is strict (threshold 0 keeps exactly the voxels that ever contributed) and
+ *       NaN is never kept.  dilate in 0..3 and X * Y * Z < 2^31 (VOXE_ERR_BAD_SHAPE otherwise).  One pass, deterministic.     */
+int voxe_visibility_accumulate(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                               const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                               float* max_weight /* [X,Y,Z] or NULL */, float* max_trans /* [X,Y,Z] or NULL */,
+                               void* stream);
+int voxe_visibility_mask(const float* vis, int32_t X, int32_t Y, int32_t Z, float threshold, int32_t dilate,
+                         uint8_t* mask /* [X,Y,Z] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.
  * ---------------------------------------------------------------------------------------------- */

@@ -1408,6 +1408,25 @@ static int validate_normals_grid(const VoxeGridDesc* g) {
   return VOXE_OK;
 }
 
+// DevCfg of a call that marches the forward's samples without rendering (normals, visibility): the sampling fields make_dev()
+// copies, with make_dev()'s expressions (the forward's depths and jitter stream); everything else 0
+static void sampling_cfg_to_dev(const VoxeRenderCfg* cfg, int64_t R, DevCfg* out) {
+  DevCfg& dc = *out;
+  memset(&dc, 0, sizeof(dc));
+  dc.S = cfg->num_samples;
+  dc.near = cfg->near; dc.far = cfg->far;
+  dc.perturb = cfg->perturb; dc.lindisp = cfg->linear_disparity; dc.aabb_clip = cfg->aabb_clip;
+  dc.key0 = (uint32_t)cfg->seed ^ ((uint32_t)cfg->rng_offset * 0x9E3779B1u);
+  dc.key1 = (uint32_t)(cfg->seed >> 32) ^ (uint32_t)(cfg->rng_offset >> 32) ^ 0x7F4A7C15u;
+  dc.R = R;
+  // image order (pixel tiles) only when the image fields describe R exactly; otherwise (or when absent) linear order
+  const int64_t W = cfg->image_width, H = cfg->image_height > 0 ? cfg->image_height : (W > 0 ? R / W : 0);
+  if (W > 0 && H > 0 && H <= INT32_MAX && R % (W * H) == 0) {
+    dc.image_width = (int)W;
+    dc.image_height = (int)H;
+  }
+}
+
 int voxe_query_normals(const VoxeGridDesc* grid, const float* points, int64_t N, float* normals, void* stream) {
   const int st = validate_normals_grid(grid);
   if (st) return st;
@@ -1431,21 +1450,34 @@ int voxe_render_normals(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, cons
   DevGrid dg;
   grid_to_dev(grid, &dg);
   DevCfg dc;
-  memset(&dc, 0, sizeof(dc));
-  // the sampling fields make_dev() copies, with make_dev()'s expressions: the forward's depths and jitter stream
-  dc.S = cfg->num_samples;
-  dc.near = cfg->near; dc.far = cfg->far;
-  dc.perturb = cfg->perturb; dc.lindisp = cfg->linear_disparity; dc.aabb_clip = cfg->aabb_clip;
-  dc.key0 = (uint32_t)cfg->seed ^ ((uint32_t)cfg->rng_offset * 0x9E3779B1u);
-  dc.key1 = (uint32_t)(cfg->seed >> 32) ^ (uint32_t)(cfg->rng_offset >> 32) ^ 0x7F4A7C15u;
-  dc.R = R;
-  // image order (pixel tiles) only when the image fields describe R exactly; otherwise (or when absent) linear order
-  const int64_t W = cfg->image_width, H = cfg->image_height > 0 ? cfg->image_height : (W > 0 ? R / W : 0);
-  if (W > 0 && H > 0 && H <= INT32_MAX && R % (W * H) == 0) {
-    dc.image_width = (int)W;
-    dc.image_height = (int)H;
-  }
+  sampling_cfg_to_dev(cfg, R, &dc);
   launch_render_normals(dg, dc, grid->densities, rays_o, rays_d, jitter, normals, depth, acc, (hipStream_t)stream);
+  return finish();
+}
+
+// ---- per-voxel visibility ----------------------------------------------------------------------------
+int voxe_visibility_accumulate(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d,
+                               int64_t R, const float* jitter, float* max_weight, float* max_trans, void* stream) {
+  const int st = validate_normals_grid(grid);
+  if (st) return st;
+  if (!cfg) return VOXE_ERR_NULL_POINTER;
+  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
+  if (R == 0 || (!max_weight && !max_trans)) return VOXE_OK;
+  DevGrid dg;
+  grid_to_dev(grid, &dg);
+  DevCfg dc;
+  sampling_cfg_to_dev(cfg, R, &dc);
+  launch_visibility_accumulate(dg, dc, grid->densities, rays_o, rays_d, jitter, max_weight, max_trans, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_visibility_mask(const float* vis, int32_t X, int32_t Y, int32_t Z, float threshold, int32_t dilate, uint8_t* mask,
+                         void* stream) {
+  if (X <= 0 || Y <= 0 || Z <= 0 || (long long)X * Y * Z >= (1LL << 31)) return VOXE_ERR_BAD_SHAPE;
+  if (dilate < 0 || dilate > 3) return VOXE_ERR_BAD_SHAPE;
+  if (!vis || !mask) return VOXE_ERR_NULL_POINTER;
+  launch_visibility_mask(vis, X, Y, Z, threshold, dilate, mask, (hipStream_t)stream);
   return finish();
 }
 

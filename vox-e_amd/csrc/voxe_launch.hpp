@@ -210,4 +210,9 @@ void launch_query_normals(const DevGrid& g, const float* dens, const float* poin
 void launch_render_normals(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                            const float* jitter, float* normals, float* depth, float* acc, hipStream_t st);
 
+// voxe_visibility.hip: per-voxel visibility; accumulate reads the raw densities only, no workspace
+void launch_visibility_accumulate(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
+                                  const float* jitter, float* max_weight, float* max_trans, hipStream_t st);
+void launch_visibility_mask(const float* vis, int X, int Y, int Z, float threshold, int dilate, uint8_t* mask, hipStream_t st);
+
 }  // namespace voxe

@@ -220,6 +220,9 @@ HIP_ONLY = {
     # density-gradient normals (additive, still ABI v13)
     "query_normals": (C.c_int, [_GD, _P, C.c_int64, _P, _P]),
     "render_normals": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    # per-voxel visibility (additive, still ABI v13)
+    "visibility_accumulate": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "visibility_mask": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P]),
 }
 
 CPU_ONLY = {

@@ -1237,3 +1237,63 @@ def render_normals(spec: GridSpec, params: RenderParams, densities: torch.Tensor
         check(lib().voxe_render_normals(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), ptr(normals), ptr(depth),
                                         ptr(acc), stream_ptr(device)), "voxe_render_normals")
     return normals, depth, acc
+
+
+# ------------------------------------------------------------------------------------------------
+# per-voxel visibility (DESIGN.md section 4 "Visibility"): reads the raw densities only, no workspace, not differentiable
+# ------------------------------------------------------------------------------------------------
+def visibility_accumulate_(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor,
+                           rays_d: torch.Tensor, max_weight: Optional[torch.Tensor] = None,
+                           max_trans: Optional[torch.Tensor] = None, jitter: Optional[torch.Tensor] = None,
+                           rng: Optional[Tuple[int, int]] = None) -> None:
+    """Raise, in place, max_weight[c] to w_k * t_c and max_trans[c] to T_k over every sample k of the flat rays and every
+    corner c of its trilinear footprint (t_c the gather weight, w_k = T_k alpha_k, T_k the transmittance on arrival), with the
+    samples and weights `render` uses for the same params, jitter and rng (`rng` follows render's rule).  The buffers
+    ([X,Y,Z] or [X,Y,Z,1] float32, contiguous, either may be None) ACCUMULATE: zero them before the first call.  The result is
+    the same bit for bit however the rays are split over calls or ordered."""
+    _check_densities(densities, "visibility_accumulate_")
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+        require_device(t, f"visibility_accumulate_ ({name})")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_o.shape != rays_d.shape:
+        raise VoxeError(f"rays must be flat [R,3]; got {tuple(rays_o.shape)}, {tuple(rays_d.shape)}")
+    if jitter is not None and tuple(jitter.shape) != (rays_o.shape[0], params.num_samples):
+        raise VoxeError(f"jitter must be [R,S]={rays_o.shape[0], params.num_samples}; got {tuple(jitter.shape)}")
+    device = densities.device
+    nvox = densities.numel()
+    for name, t in (("max_weight", max_weight), ("max_trans", max_trans)):
+        if t is None:
+            continue
+        require_device(t, f"visibility_accumulate_ ({name})")
+        if (t.dtype != torch.float32 or not t.is_contiguous() or t.device != device or t.numel() != nvox
+                or tuple(t.shape[:3]) != tuple(densities.shape[:3])):
+            raise VoxeError(f"visibility_accumulate_: {name} must be a contiguous float32 [X,Y,Z] buffer on the grid's device; "
+                            f"got {tuple(t.shape)} {t.dtype}")
+    if rng is None:
+        rng = _next_rng() if (params.perturb and jitter is None) else (0, 0)
+    ensure_gfx950(device)
+    dens, ro, rd = f32c(densities.detach()), f32c(rays_o.detach()), f32c(rays_d.detach())
+    jit = None if jitter is None else f32c(jitter.detach())
+    g = _normals_grid_desc(spec, dens)
+    c = make_render_cfg(params.num_samples, params.near, params.far, params.perturb, params.linear_disparity, params.aabb_clip,
+                        seed=rng[0], rng_offset=rng[1], image_width=params.image_width, image_height=params.image_height)
+    with torch.cuda.device(device):
+        check(lib().voxe_visibility_accumulate(C.byref(g), C.byref(c), ptr(ro), ptr(rd), ro.shape[0], ptr(jit), ptr(max_weight),
+                                               ptr(max_trans), stream_ptr(device)), "voxe_visibility_accumulate")
+
+
+def visibility_mask(vis: torch.Tensor, threshold: float, dilate: int = 0) -> torch.Tensor:
+    """uint8 [X,Y,Z]: 1 where some voxel within Chebyshev distance `dilate` (0..3) has vis > threshold (strict; NaN never)."""
+    require_device(vis, "visibility_mask (vis)")
+    if vis.dim() == 4 and vis.shape[-1] == 1:
+        vis = vis[..., 0]
+    if vis.dim() != 3:
+        raise VoxeError(f"visibility_mask: vis must be [X,Y,Z]; got {tuple(vis.shape)}")
+    v = f32c(vis.detach())
+    device = v.device
+    ensure_gfx950(device)
+    X, Y, Z = (int(s) for s in v.shape)
+    with torch.cuda.device(device):
+        mask = torch.empty((X, Y, Z), dtype=torch.uint8, device=device)
+        check(lib().voxe_visibility_mask(ptr(v), X, Y, Z, float(threshold), int(dilate), ptr(mask), stream_ptr(device)),
+              "voxe_visibility_mask")
+    return mask
