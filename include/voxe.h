@@ -704,6 +704,46 @@ int voxe_visibility_mask(const float* vis, int32_t X, int32_t Y, int32_t Z, floa
                          uint8_t* mask /* [X,Y,Z] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Distortion loss on rays (additive; still ABI v13), DESIGN.md section 4.11 "Distortion".
+ *   The samples z_k, the inside test, sigma_k, delta_k and the weights w_k = T_k alpha_k (last dl = 1e10) are those of
+ *   voxe_render_fwd / voxe_render_normals / voxe_visibility_accumulate for the same rays, cfg and jitter / (seed, rng_offset);
+ *   the cfg fields honoured and ignored are those of voxe_render_normals.  With s_k = (z_k - near) / (far - near) -- ALWAYS
+ *   cfg's near and far, also under aabb_clip and linear_disparity (far > near for a finite result):
+ *       d_k = s_{k+1} - s_k for k < S-1, d_{S-1} = 0      (the interval the renderer's quadrature gives sample k)
+ *       m_k = s_k + d_k / 2
+ *       L_r = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+ *       loss = (1/R) sum_r L_r
+ *   Samples that fail the AABB test have w = 0 and contribute nothing.  Gradient w.r.t. the raw densities [X,Y,Z,1]:
+ *       g_i = dL_r/dw_i = 2 sum_j w_j |m_i - m_j| + (2/3) w_i d_i
+ *       dL_r/dsigma_k = delta_k [g_k (T_k - w_k) - sum_{i>k} g_i w_i]
+ *   and from there through post_activate', the gather weights t_c = (wx * wy) * wz and pre_activate' * density_scale into the
+ *   8 footprint corners, with the derivative conventions of voxe_render_bwd.  The samples are constants: no gradient flows
+ *   to z.  The kernel evaluates |m_i - m_j| as m_i - m_j for j < i: the renderer's depths never decrease along a ray.
+ *   Outputs (each may be NULL): loss_out  device float[1], the UNWEIGHTED mean (grad_scale does not apply to it);
+ *                               ray_loss  device [R], L_r;
+ *                               d_densities [X,Y,Z,1] = grad_scale * dloss/draw, added to the buffer when accumulate != 0,
+ *                               else the buffer is zeroed first (voxels no sample touches keep an exact 0).
+ *   The running sums per ray are double, the per-sample work float; the gradient goes through float atomics, so it can differ
+ *   in the last bits from run to run (loss and ray_loss do not).  `scratch` (voxe_distortion_scratch_bytes(R), read only when
+ *   loss_out != NULL) carries the per-block partials of the loss; too small: VOXE_ERR_WORKSPACE.  R == 0 or all three outputs
+ *   NULL: VOXE_OK with no launch (accumulate == 0 with a non-NULL d_densities still zeroes it).  Only grid->densities is read
+ *   (SH and attention descriptors both work); no workspace, no forward record, no voxe_recon_prefetch hint is touched.
+ *   Caller's stream, no host synchronisation, no allocation.  Validation, the limits on R and the voxel count and the error
+ *   codes are those of voxe_render_normals.
+ *   voxe_distortion_debug_lanes: test aid.  The kernel splits a ray over 1, 2, 4 or 8 lanes by R; a value of 1 / 2 / 4 / 8 pins
+ *   the split for the calling thread's later calls, 0 restores the choice by R (anything else: VOXE_ERR_BAD_SHAPE).        */
+size_t voxe_distortion_scratch_bytes(int64_t R);
+int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                            const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                            float grad_scale,
+                            float* loss_out      /* device float[1] or NULL: the UNWEIGHTED mean */,
+                            float* ray_loss      /* device [R] or NULL: L_r */,
+                            float* d_densities   /* [X,Y,Z,1] or NULL: grad_scale * dloss/draw */,
+                            int32_t accumulate   /* as voxe_tv_fwd_bwd / voxe_render_bwd */,
+                            void* scratch, size_t scratch_bytes, void* stream);
+int voxe_distortion_debug_lanes(int32_t lanes);
+
+/* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.
  * ---------------------------------------------------------------------------------------------- */

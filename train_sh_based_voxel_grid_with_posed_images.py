@@ -69,6 +69,8 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
 @click.option("--summary_frequency", type=click.INT, default=50, show_default=True)
 @click.option("--verbose_rendering", type=click.BOOL, default=False, show_default=True)
 @click.option("--lpips_weight", type=click.FLOAT, default=0.0, show_default=True)
+@click.option("--distortion_weight", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
+              help="weight of the distortion loss on the ray batch (against floaters); 0 = off")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -105,7 +107,7 @@ def main(**kwargs) -> None:
         apply_diffuse_render_regularization=cfg.apply_diffuse_render_regularization, fast_debug_mode=cfg.fast_debug_mode,
         save_freq=cfg.save_frequency, test_freq=cfg.test_frequency, feedback_freq=cfg.feedback_frequency,
         summary_freq=cfg.summary_frequency, verbose_rendering=cfg.verbose_rendering, lpips_weight=cfg.lpips_weight,
-        num_workers=cfg.num_workers)
+        num_workers=cfg.num_workers, distortion_weight=cfg.distortion_weight)
 
 
 if __name__ == "__main__":

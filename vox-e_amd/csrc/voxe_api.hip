@@ -1481,4 +1481,35 @@ int voxe_visibility_mask(const float* vis, int32_t X, int32_t Y, int32_t Z, floa
   return finish();
 }
 
+// ---- distortion loss on rays -----------------------------------------------------------------------
+size_t voxe_distortion_scratch_bytes(int64_t R) { return distortion_scratch_bytes(R); }
+
+int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
+                            const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_densities,
+                            int32_t accumulate, void* scratch, size_t scratch_bytes, void* stream) {
+  const int st = validate_normals_grid(grid);
+  if (st) return st;
+  if (!cfg) return VOXE_ERR_NULL_POINTER;
+  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
+  if (R > 0 && loss_out && (!scratch || scratch_bytes < distortion_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
+  const bool clear = d_densities && !accumulate;
+  if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
+    return VOXE_ERR_LAUNCH;
+  if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
+  DevGrid dg;
+  grid_to_dev(grid, &dg);
+  DevCfg dc;
+  sampling_cfg_to_dev(cfg, R, &dc);
+  launch_distortion(dg, dc, grid->densities, rays_o, rays_d, jitter, grad_scale, loss_out, ray_loss, d_densities, scratch,
+                    (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_distortion_debug_lanes(int32_t lanes) {
+  if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8) return VOXE_ERR_BAD_SHAPE;
+  tl_distortion_lanes = lanes;
+  return VOXE_OK;
+}
+
 }  // extern "C"

@@ -215,4 +215,12 @@ void launch_visibility_accumulate(const DevGrid& g, const DevCfg& c, const float
                                   const float* jitter, float* max_weight, float* max_trans, hipStream_t st);
 void launch_visibility_mask(const float* vis, int X, int Y, int Z, float threshold, int dilate, uint8_t* mask, hipStream_t st);
 
+// voxe_distortion.hip: distortion loss on rays, value + density gradient; reads the raw densities only
+int distortion_lanes_for(long long R);   // lanes per ray (1, 2, 4 or 8)
+extern thread_local int tl_distortion_lanes;   // test aid (voxe_distortion_debug_lanes): != 0 overrides distortion_lanes_for
+size_t distortion_scratch_bytes(long long R);
+void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
+                       const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
+                       hipStream_t st);
+
 }  // namespace voxe

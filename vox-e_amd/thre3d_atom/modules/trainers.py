@@ -85,6 +85,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     prefetch_batches: bool = True,     # addition of this build (fused_iteration only): the next iteration's pixel batch and its
                                        # segment tables are assembled while this iteration's backward / Adam run
                                        # (voxe_recon_prefetch); same batches, same arithmetic
+    distortion_weight: float = 0.0,    # addition of this build: weight of the distortion loss on the ray batch (mip-NeRF 360's
+                                       # regulariser against floaters, thre3d_reprs/distortion.py); 0 = off, nothing changes.
+                                       # Above 0 the iteration is not the one-call one (voxe_recon_step has no such term)
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
@@ -135,6 +138,10 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
         scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=lr_decay_gamma_per_stage)
         # (the one-call iteration reads RGB targets straight from the image stack)
         one_call = fused_grid_step and fused_iteration and data.images.shape[1] == 3 and data.images.is_contiguous()
+        if distortion_weight > 0.0:
+            if one_call and stage == 1:
+                log.info("distortion_weight > 0: the iterations render, add the term and step separately (no one-call iteration)")
+            one_call = False
         fused_losses = torch.zeros(4, dtype=torch.float32, device=device)
         log.info(f"stage {stage}: grid {vol_mod.thre3d_repr.grid_dims}, images [{intr.height} x {intr.width}], lr {lr:.4f}")
 
@@ -180,6 +187,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                     if apply_diffuse_render_regularization:
                         diffuse = vol_mod.render_rays(rays_batch, render_diffuse=True).colour
                         loss = loss + torch.nn.functional.l1_loss(diffuse, pixels_batch)
+                    if distortion_weight > 0.0:
+                        # (under FusedGridAdam the renders' gradient stays in the workspace and this term's arrives as
+                        #  densities.grad, which step() adds; under VoxeAdam plain autograd sums both)
+                        distortion = vol_mod.distortion_loss(rays_batch)
+                        loss = loss + distortion_weight * distortion
                     optimizer.zero_grad()
                     loss.backward()
                     optimizer.step()
@@ -191,7 +203,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         loss = torch.tensor(l1_spec + (l1_diff if apply_diffuse_render_regularization else 0.0))
                         psnr = mse2psnr(torch.tensor(mse_spec))
                     log.info(f"Stage: {stage} Global Iteration: {global_step} Stage Iteration: {it} "
-                             f"loss: {float(loss.detach()): .3f} psnr: {float(psnr): .3f}")
+                             f"loss: {float(loss.detach()): .3f} psnr: {float(psnr): .3f}"
+                             + (f" distortion: {float(distortion.detach()): .6f}" if distortion_weight > 0.0 else ""))
                 if it % lr_decay_steps_per_stage == 0:
                     scheduler.step()
                 last = it == num_iterations_per_stage

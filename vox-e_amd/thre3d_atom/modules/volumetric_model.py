@@ -104,6 +104,13 @@ class VolumetricModel:
         config = self._update_render_config(self._render_config, kwargs)
         return self._render_procedure_attn(self._thre3d_repr, rays, config, parallel_points_chunk_size, orig_densities)
 
+    def distortion_loss(self, rays: Rays, **kwargs) -> torch.Tensor:
+        """mean distortion loss of flat `rays` (thre3d_reprs.distortion.distortion_loss_on_rays) under the model's render
+        config with `kwargs` applied; differentiable w.r.t. the grid's densities"""
+        from thre3d_atom.thre3d_reprs.distortion import distortion_loss_on_rays
+
+        return distortion_loss_on_rays(self._thre3d_repr, rays, self._update_render_config(self._render_config, kwargs))
+
     # -- whole-camera, no grad --------------------------------------------------------------------
     def _render_camera(self, render_chunk, collate, reshape, camera_pose, camera_intrinsics,
                        parallel_rays_chunk_size, gpu_render, verbose):

@@ -223,6 +223,10 @@ HIP_ONLY = {
     # per-voxel visibility (additive, still ABI v13)
     "visibility_accumulate": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "visibility_mask": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P]),
+    # distortion loss on rays (additive, still ABI v13)
+    "distortion_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "distortion_fwd_bwd": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, C.c_float, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
+    "distortion_debug_lanes": (C.c_int, [C.c_int32]),
 }
 
 CPU_ONLY = {

@@ -1297,3 +1297,85 @@ def visibility_mask(vis: torch.Tensor, threshold: float, dilate: int = 0) -> tor
         check(lib().voxe_visibility_mask(ptr(v), X, Y, Z, float(threshold), int(dilate), ptr(mask), stream_ptr(device)),
               "voxe_visibility_mask")
     return mask
+
+
+# ------------------------------------------------------------------------------------------------
+# distortion loss on rays (DESIGN.md section 4 "Distortion"): reads the raw densities only, no workspace; differentiable w.r.t.
+# the densities
+# ------------------------------------------------------------------------------------------------
+def distortion_fwd_bwd(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                       jitter: Optional[torch.Tensor] = None, rng: Tuple[int, int] = (0, 0), grad_scale: float = 1.0,
+                       want_loss: bool = True, want_ray_loss: bool = False, d_densities: Optional[torch.Tensor] = None,
+                       accumulate: bool = False, lanes: int = 0):
+    """voxe_distortion_fwd_bwd as it stands: (loss [] or None, ray_loss [R] or None); `d_densities` (contiguous float32 of the
+    densities' shape, or None) receives grad_scale * dloss/draw, added to its contents when `accumulate`.  `lanes` (test aid):
+    1 / 2 / 4 / 8 pins the kernel's lanes per ray for this call, 0 = chosen by R."""
+    _check_densities(densities, "distortion_loss")
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+        require_device(t, f"distortion_loss ({name})")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_o.shape != rays_d.shape:
+        raise VoxeError(f"rays must be flat [R,3]; got {tuple(rays_o.shape)}, {tuple(rays_d.shape)}")
+    if jitter is not None and tuple(jitter.shape) != (rays_o.shape[0], params.num_samples):
+        raise VoxeError(f"jitter must be [R,S]={rays_o.shape[0], params.num_samples}; got {tuple(jitter.shape)}")
+    device = densities.device
+    if d_densities is not None:
+        require_device(d_densities, "distortion_loss (d_densities)")
+        if (d_densities.dtype != torch.float32 or not d_densities.is_contiguous() or d_densities.device != device
+                or d_densities.shape != densities.shape):
+            raise VoxeError("distortion_loss: d_densities must be a contiguous float32 buffer of the densities' shape on the "
+                            f"grid's device; got {tuple(d_densities.shape)} {d_densities.dtype}")
+    ensure_gfx950(device)
+    dens, ro, rd = f32c(densities.detach()), f32c(rays_o.detach()), f32c(rays_d.detach())
+    jit = None if jitter is None else f32c(jitter.detach())
+    g = _normals_grid_desc(spec, dens)
+    c = make_render_cfg(params.num_samples, params.near, params.far, params.perturb, params.linear_disparity, params.aabb_clip,
+                        seed=rng[0], rng_offset=rng[1], image_width=params.image_width, image_height=params.image_height)
+    R = ro.shape[0]
+    L = lib()
+    with torch.cuda.device(device):
+        loss = torch.zeros((), dtype=torch.float32, device=device) if want_loss else None
+        ray_loss = torch.empty((R,), dtype=torch.float32, device=device) if want_ray_loss else None
+        sc = _scratch_for(device, L.voxe_distortion_scratch_bytes(R)) if want_loss else None
+        if lanes:
+            check(L.voxe_distortion_debug_lanes(int(lanes)), "voxe_distortion_debug_lanes")
+        try:
+            check(L.voxe_distortion_fwd_bwd(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), float(grad_scale), ptr(loss),
+                                            ptr(ray_loss), ptr(d_densities), 1 if accumulate else 0, ptr(sc),
+                                            sc.numel() if sc is not None else 0, stream_ptr(device)), "voxe_distortion_fwd_bwd")
+        finally:
+            if lanes:
+                L.voxe_distortion_debug_lanes(0)
+    if d_densities is not None:
+        torch.autograd.graph.increment_version(d_densities)
+    return loss, ray_loss
+
+
+class _DistortionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, densities, spec, params, rays_o, rays_d, jitter, rng, return_ray_loss, lanes):
+        d_d = torch.empty_like(f32c(densities.detach())) if ctx.needs_input_grad[0] else None
+        loss, ray_loss = distortion_fwd_bwd(spec, params, densities, rays_o, rays_d, jitter, rng, want_ray_loss=return_ray_loss,
+                                            d_densities=d_d, lanes=lanes)
+        ctx.save_for_backward(d_d)
+        if return_ray_loss:
+            ctx.mark_non_differentiable(ray_loss)
+            return loss, ray_loss
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (d_d,) = ctx.saved_tensors
+        return (None if d_d is None else d_d * g,) + (None,) * 8
+
+
+def distortion_loss(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                    jitter: Optional[torch.Tensor] = None, rng: Optional[Tuple[int, int]] = None, return_ray_loss: bool = False,
+                    _lanes: int = 0):
+    """Distortion loss of flat rays (mip-NeRF 360; DVGOv2's O(S) evaluation): the mean over rays of
+    L_r = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i on depths normalised by params.near / params.far, with the samples
+    and weights `render` uses for the same params, jitter and rng (`rng` follows render's rule: None = a fresh stream when
+    params.perturb and no jitter is given).  A scalar tensor, differentiable w.r.t. `densities` (the gradient is computed in the
+    forward, only when it is needed); return_ray_loss=True: (loss, L_r [R], not differentiable)."""
+    if rng is None:
+        rng = _next_rng() if (params.perturb and jitter is None) else (0, 0)
+    return _DistortionFn.apply(densities, spec, params, rays_o, rays_d, jitter, rng, bool(return_ray_loss), int(_lanes))
