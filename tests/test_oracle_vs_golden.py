@@ -306,3 +306,52 @@ def test_sh_evaluation_host_helper_matches_reference(deg):
     g = load_golden("render_shdeg.npz")
     out = evaluate_spherical_harmonics(deg, torch.from_numpy(g[f"eval_deg{deg}_coeffs"]), torch.from_numpy(g[f"eval_deg{deg}_dirs"]))
     np.testing.assert_allclose(out.numpy(), g[f"eval_deg{deg}_out"], rtol=0, atol=2e-6)
+
+
+# ---- degenerate ray geometry (tests/degenerate_cases.py) on the reference's renders: tests/golden/degenerate_rays.npz, g18 --------
+def _degenerate_names():
+    return [str(n) for n in load_golden("degenerate_rays.npz")["names"]]
+
+
+@pytest.mark.parametrize("name", _degenerate_names())
+def test_degenerate_rays_forward_and_grads(name):
+    """axis-aligned views, samples exactly on voxel planes / AABB faces, ties between march axes, eyes on a face and on a lattice
+    point, launches that miss the grid, 1xN / Nx1 / 1x1 images: the oracle against the reference, with the tolerances of
+    render_sh0.npz above; the disparity's NaN pattern is equal; the cast of a signed-permutation rotation is bit-equal.
+    (The fixture's grid has voxels of 0.5 over the table's box; the table's own preconditions are checked on the table's grids in
+    tests/test_degenerate_host.py.)"""
+    import degenerate_cases as dc
+
+    g = load_golden("degenerate_rays.npz")
+    c = dc.case(name)
+    grid = grid_from_golden(g, "", "softplus_soft")
+    assert grid.densities.shape[:3] == (8, 4, 16) and [tuple(r) for r in g["aabb"]] == dc.LATTICE_AABB
+    c.grid = grid
+    tag = name + "/"
+    o, d = dc.rays(c)
+    R = o.shape[0]
+    if np.array_equal(np.abs(c.rot).sum(0), np.ones(3)) and set(np.unique(np.abs(c.rot))) == {0.0, 1.0}:
+        np.testing.assert_array_equal(d, g[tag + "rays_d"])
+    else:
+        np.testing.assert_allclose(d, g[tag + "rays_d"], rtol=0, atol=3e-7)
+    if "tie" in c.need:
+        mid = g[tag + "rays_d"][R // 2]
+        assert len({abs(float(mid[a])) for a in c.need["tie"]}) == 1       # the reference's own central ray ties too
+    jit = g[tag + "jitter"] if tag + "jitter" in g.files else None
+    assert (jit is not None) == bool(c.kw.get("perturb"))
+    cfg = c.cfg()
+    out = vo.render_fwd(grid, cfg, o, d, jitter=jit)
+    np.testing.assert_allclose(out["colour"], g[tag + "colour"], rtol=0, atol=FWD_ATOL)
+    np.testing.assert_allclose(out["acc"], g[tag + "acc"], rtol=0, atol=FWD_ATOL)
+    np.testing.assert_allclose(out["depth"], g[tag + "depth"], rtol=2e-6, atol=FWD_ATOL)
+    nan_equal(out["disparity"], g[tag + "disparity"], rtol=1e-5, atol=1e-6)
+    gd, gf = vo.render_bwd(grid, cfg, o, d, g[f"R{R}/g_colour"], g[f"R{R}/g_depth"], g[f"R{R}/g_acc"], jitter=jit)
+    if c.need.get("miss"):
+        assert not g[tag + "acc"].any() and np.isnan(g[tag + "disparity"]).all()
+        assert np.array_equal(out["colour"], np.full_like(out["colour"], float(bool(c.kw.get("white_bkgd")))))
+        for got, ref in ((gd, g[tag + "grad_densities"]), (gf, g[tag + "grad_features"])):
+            assert np.array_equal(ref, np.zeros_like(ref)) and np.array_equal(got, np.zeros_like(got))
+    else:
+        assert rel_l2(gd, g[tag + "grad_densities"]) < GRAD_REL_L2
+        assert rel_l2(gf, g[tag + "grad_features"]) < GRAD_REL_L2
+

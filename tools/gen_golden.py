@@ -50,6 +50,7 @@ from thre3d_atom.thre3d_reprs.voxels import (  # noqa: E402
 from thre3d_atom.utils.imaging_utils import (  # noqa: E402
     CameraBounds,
     CameraIntrinsics,
+    CameraPose,
     pose_spherical,
 )
 
@@ -223,8 +224,8 @@ def g4_voxel_forward():
     save("voxel_forward.npz", **out)
 
 
-def render_case(vg, rays, S, white, attn=False, jitter_seed=None, grads=False, **cfg_kw):
-    cfg = SHVoxGridRenderConfig(num_samples_per_ray=S, camera_bounds=BOUNDS,
+def render_case(vg, rays, S, white, attn=False, jitter_seed=None, grads=False, bounds=BOUNDS, **cfg_kw):
+    cfg = SHVoxGridRenderConfig(num_samples_per_ray=S, camera_bounds=bounds,
                                 perturb_sampled_points=jitter_seed is not None, white_bkgd=white, **cfg_kw)
     res = {}
     if jitter_seed is not None:
@@ -682,6 +683,47 @@ def g17_regulariser_modes():
     save("reg_modes.npz", **out)
 
 
+def g18_degenerate_rays():
+    """Degenerate ray geometry (tests/degenerate_cases.py: axis-aligned views, samples exactly on voxel planes and AABB faces, ties
+    between march axes, cameras on a face / on a lattice point, launches that miss the grid, 1xN / Nx1 / 1x1 images) rendered by
+    the reference on a small grid over the lattice AABB: dims (8, 4, 16) at voxel 0.5.  Per camera: colour / depth / acc /
+    disparity and the gradients of the colour + depth + acc loss (near / far per case).  The grid is written once; the upstream
+    gradients (the same generator seed in every render_case call) once per ray count."""
+    sys.path.insert(0, os.path.join(os.path.dirname(OUT), ""))      # tests/
+    root = os.path.dirname(os.path.dirname(OUT))
+    sys.path.extend([root, os.path.join(root, "vox-e_amd")])        # oracle/ and voxe_hip/ of the case table (behind the reference)
+    import degenerate_cases as dc  # noqa: E402
+
+    out = {}
+    vg = make_grid((8, 4, 16), 3, 18, "softplus_soft", voxel_size=VoxelSize(0.5, 0.5, 0.5))
+    assert [tuple(float(v) for v in r) for r in vg.aabb] == dc.LATTICE_AABB
+    out.update(grid_arrays(vg, ""))
+    names = [n for n in dc.NAMES if not n.endswith("_relu") and n not in ("axis-z_hash", "six_views")]
+    for name in names:
+        c = dc.case(name)
+        intr = CameraIntrinsics(c.H, c.W, c.focal)
+        rays = flatten_rays(cast_rays(intr, CameraPose(c.rot, c.eye.reshape(3, 1))))
+        kw = dict(c.kw)
+        res = render_case(vg, rays, c.S, bool(kw.pop("white_bkgd", False)), grads=True, bounds=CameraBounds(c.near, c.far),
+                          jitter_seed=1800 if kw.pop("perturb", False) else None,
+                          optimized_sampling=bool(kw.pop("aabb_clip", False)),
+                          linear_disparity_sampling=bool(kw.pop("linear_disparity", False)))
+        assert not kw, kw
+        tag = name + "/"
+        out[tag + "rays_d"] = np_(rays.directions)
+        for k in ("colour", "depth", "acc", "disparity", "jitter"):
+            if k in res:
+                out[tag + k] = res[k]
+        out[tag + "grad_densities"], out[tag + "grad_features"] = res["grad2_densities"], res["grad2_features"]
+        for k in ("g_colour", "g_depth", "g_acc"):
+            key = f"R{len(rays.origins)}/{k}"
+            assert key not in out or np.array_equal(out[key], res[k])
+            out[key] = res[k]
+    out["names"] = np.array(names)
+    save("degenerate_rays.npz", **out)
+    assert os.path.getsize(os.path.join(OUT, "degenerate_rays.npz")) < 512 * 1024
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if len(sys.argv) > 1:      # python tools/gen_golden.py g17_regulariser_modes  -> only that fixture
@@ -704,3 +746,4 @@ if __name__ == "__main__":
     g15_attention_maps()
     g16_sds_boundary()
     g17_regulariser_modes()
+    g18_degenerate_rays()
