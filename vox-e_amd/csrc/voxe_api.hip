@@ -40,13 +40,31 @@ struct Variant {
   bool attn;
 };
 
+// the checks every grid-taking entry point shares: extents and index widths of a grid read with `channels` floats per voxel ...
+int grid_extent_status(const VoxeGridDesc* g, int channels) {
+  if (g->X <= 0 || g->Y <= 0 || g->Z <= 0 || channels <= 0) return VOXE_ERR_BAD_SHAPE;
+  if ((long long)g->X * g->Y * g->Z * channels >= (1LL << 31)) return VOXE_ERR_BAD_SHAPE;
+  if ((long long)g->X * g->Y >= (1LL << 24) || (long long)g->Y * g->Z >= (1LL << 24) || g->Z >= (1 << 24)) return VOXE_ERR_BAD_SHAPE;  // 24-bit index multiplies (cell addresses; strides in the window flush)
+  return VOXE_OK;
+}
+// ... of a call that reads densities and features ...
+int grid_shape_status(const VoxeGridDesc* g) {
+  if (!g || !g->densities || !g->features) return VOXE_ERR_NULL_POINTER;
+  return g->F <= 0 ? VOXE_ERR_BAD_SHAPE : grid_extent_status(g, g->F + 1);
+}
+// ... and the density activations
+int grid_acts_status(const VoxeGridDesc* g) {
+  if (g->density_pre_act != VOXE_ACT_IDENTITY && g->density_pre_act != VOXE_ACT_ABS) return VOXE_ERR_UNSUPPORTED;
+  if (g->density_post_act != VOXE_ACT_IDENTITY && g->density_post_act != VOXE_ACT_RELU &&
+      g->density_post_act != VOXE_ACT_SOFTPLUS)
+    return VOXE_ERR_UNSUPPORTED;
+  return VOXE_OK;
+}
+
 int validate(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, Variant* v) {
   if (!g || !c) return VOXE_ERR_NULL_POINTER;
-  if (!g->densities || !g->features) return VOXE_ERR_NULL_POINTER;
-  if (g->X <= 0 || g->Y <= 0 || g->Z <= 0 || g->F <= 0 || R < 0 || c->num_samples <= 0)
-    return VOXE_ERR_BAD_SHAPE;
-  if ((long long)g->X * g->Y * g->Z * (g->F + 1) >= (1LL << 31)) return VOXE_ERR_BAD_SHAPE;
-  if ((long long)g->X * g->Y >= (1LL << 24) || (long long)g->Y * g->Z >= (1LL << 24) || g->Z >= (1 << 24)) return VOXE_ERR_BAD_SHAPE;  // 24-bit index multiplies (cell addresses; strides in the window flush)
+  if (const int st = grid_shape_status(g)) return st;
+  if (R < 0 || c->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
   if (g->feature_kind == VOXE_FEAT_ATTN) {
     if (g->F != 1) return VOXE_ERR_BAD_SHAPE;
     v->cout = 1; v->ncoef_mem = 1; v->attn = true;
@@ -59,16 +77,20 @@ int validate(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, Variant* 
     return VOXE_ERR_UNSUPPORTED;
   }
   v->C = g->F + 1;
-  if (g->density_pre_act != VOXE_ACT_IDENTITY && g->density_pre_act != VOXE_ACT_ABS)
-    return VOXE_ERR_UNSUPPORTED;
-  if (g->density_post_act != VOXE_ACT_IDENTITY && g->density_post_act != VOXE_ACT_RELU &&
-      g->density_post_act != VOXE_ACT_SOFTPLUS)
-    return VOXE_ERR_UNSUPPORTED;
+  if (const int st = grid_acts_status(g)) return st;
   if (c->image_width < 0 || (c->image_width > 0 && R % c->image_width != 0))
     return VOXE_ERR_BAD_SHAPE;
   if (c->image_height < 0 || (c->image_height > 0 && (c->image_width <= 0 || R % ((int64_t)c->image_height * c->image_width) != 0)))
     return VOXE_ERR_BAD_SHAPE;
   return VOXE_OK;
+}
+
+// a call that takes a grid and no render cfg (point queries): the shared checks + a channel count the pack kernels know
+int validate_grid_only(const VoxeGridDesc* g) {
+  if (const int st = grid_shape_status(g)) return st;
+  const int C = g->F + 1;
+  if (C != 2 && C != 4 && C != 13 && C != 28 && C != 49) return VOXE_ERR_BAD_SHAPE;
+  return grid_acts_status(g);
 }
 
 // voxe_recon_step's paired render (two renders of the same batch with independent jitter streams in ONE launch of 2 B rays):
@@ -80,6 +102,16 @@ struct PairScope {
   ~PairScope() { tl_pair = nullptr; }
 };
 
+void grid_to_dev(const VoxeGridDesc* g, DevGrid* dg) {
+  dg->X = g->X; dg->Y = g->Y; dg->Z = g->Z;
+  for (int a = 0; a < 3; ++a) {
+    dg->lo[a] = g->aabb_lo[a]; dg->hi[a] = g->aabb_hi[a];
+    dg->scale[a] = g->norm_scale[a]; dg->bias[a] = g->norm_bias[a];
+  }
+  dg->density_scale = g->density_scale;
+  dg->pre_act = g->density_pre_act; dg->post_act = g->density_post_act;
+}
+
 void make_dev(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const Variant& v, DevGrid* dg,
               HostCfg* dc) {
   dc->disp = disp_of(c);
@@ -89,13 +121,7 @@ void make_dev(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const Va
     dc->key0b = (uint32_t)c->seed ^ ((uint32_t)tl_pair->rng_offset * 0x9E3779B1u);
     dc->key1b = (uint32_t)(c->seed >> 32) ^ (uint32_t)(tl_pair->rng_offset >> 32) ^ 0x7F4A7C15u;
   }
-  dg->X = g->X; dg->Y = g->Y; dg->Z = g->Z;
-  for (int a = 0; a < 3; ++a) {
-    dg->lo[a] = g->aabb_lo[a]; dg->hi[a] = g->aabb_hi[a];
-    dg->scale[a] = g->norm_scale[a]; dg->bias[a] = g->norm_bias[a];
-  }
-  dg->density_scale = g->density_scale;
-  dg->pre_act = g->density_pre_act; dg->post_act = g->density_post_act;
+  grid_to_dev(g, dg);
   dc->S = c->num_samples;
   dc->near = c->near; dc->far = c->far;
   dc->perturb = c->perturb; dc->lindisp = c->linear_disparity; dc->aabb_clip = c->aabb_clip;
@@ -111,84 +137,160 @@ void make_dev(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const Va
   dc->seg_len = seg_len_for(R);
 }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// workspace = [ packed grid | packed gradient | per-ray depth-segment states ]
-struct WsLayout {
-  size_t packed_off, grad_off, state_off, seg_off, prec_off, sched_off, src_off, fwdval_off, planar_off, det_off, region_off, fwd_total, total, total_with_src;
-  bool region;   // the space-binned backward applies to (grid, cfg, R): its scratch is part of the workspace
+// ---- carving bytes: the one way this file lays buffers out in a caller's workspace / scratch ---------------------------------
+// take() hands out the offset of the next buffer and moves on by its size rounded up to 256 bytes (a size of 0 takes nothing)
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t here = off; off += (bytes + 255) / 256 * 256; return here; }
 };
-WsLayout ws_layout(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R) {
-  const size_t nvox = (size_t)g->X * g->Y * g->Z;
-  const size_t bytes = align_up(nvox * (size_t)(g->F + 1) * sizeof(float), 256);
-  const int cout = g->feature_kind == VOXE_FEAT_ATTN ? 1 : 3;
-  const int nseg = c ? num_segments(c->num_samples, seg_len_for(R)) : 1;
-  const size_t state = align_up((size_t)(nseg - 1) * (size_t)(cout + 3) * (size_t)(R > 0 ? R : 0) * sizeof(float), 256);
+template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+
+// workspace = [ packed grid | packed gradient | per-ray depth-segment states | segment partials | precise sums | schedule list ]
+//             (`total`) [ two-phase sources | forward values | planar gradient | deterministic scratch | region scratch ]
+// (`total_with_src`).  A call with a NULL cfg (grid step, point queries) has the first two only.
+struct WsLayout {
+  size_t packed_off, grad_off, state_off, seg_off, prec_off, sched_off, src_off, fwdval_off, planar_off, det_off, det_scale_off, region_off;
+  size_t det_bytes;                          // fixed-point gradient + its scales (contiguous from det_off)
+  size_t fwd_total, total, total_with_src;   // what a forward alone / a backward / every optional buffer needs
+  bool has_precise, has_sched, has_src;      // the layout holds precise_grad sums / a schedule list / two-phase sources
+  size_t grad_bytes() const { return state_off - grad_off; }
+};
+// `region`: the space-binned route applies to (grid, cfg, R) -- its scratch is part of the workspace.  A grid without extents: all 0.
+WsLayout ws_layout(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, bool region) {
+  if (!g || g->X <= 0 || g->Y <= 0 || g->Z <= 0 || g->F <= 0) return WsLayout{};
+  const size_t nvox = (size_t)g->X * g->Y * g->Z, C = (size_t)(g->F + 1), rays = (size_t)(R > 0 ? R : 0);
+  const bool attn = g->feature_kind == VOXE_FEAT_ATTN;
+  const size_t per_ray = (size_t)(attn ? 1 : 3) + 3;   // floats of one state / one segment partial
+  const size_t nseg = c ? (size_t)num_segments(c->num_samples, seg_len_for(R)) : 1;
+  WsLayout l{};
+  Carve cv;
+  l.packed_off = cv.take(nvox * C * sizeof(float));
+  l.fwd_total = cv.off;  // the forward alone needs only the packed grid (states / segments are used when they fit)
   // the gradient region also fits the 2x2x2-bricked layout of the scatter backward (dims rounded up to even)
   const size_t bvox = (size_t)((g->X + 1) / 2) * ((g->Y + 1) / 2) * ((g->Z + 1) / 2) * 8;
-  const size_t gbytes = align_up(bvox * (size_t)(g->F + 1) * sizeof(float), 256);
-  WsLayout l;
-  l.packed_off = 0;
-  l.grad_off = bytes;
-  l.state_off = bytes + gbytes;
+  l.grad_off = cv.take(bvox * C * sizeof(float));
+  l.state_off = cv.take((nseg - 1) * per_ray * rays * sizeof(float));
   // partial results of the depth-segmented forward: nseg x (cout + 3) floats per ray
-  const size_t seg = align_up((size_t)nseg * (size_t)(cout + 3) * (size_t)(R > 0 ? R : 0) * sizeof(float), 256);
-  l.seg_off = bytes + gbytes + state;
-  l.fwd_total = bytes;  // the forward alone needs only the packed grid (states / segments are used when they fit)
+  l.seg_off = cv.take(nseg * per_ray * rays * sizeof(float));
   // VoxeDispatch::precise_grad: segment-local sums of the forward in double, nseg x 5 doubles per ray (lean tile kernels)
-  const bool precise = c && disp_of(c).precise_grad > 0 && c->image_width > 0 && cout == 3;
-  const size_t prec = precise ? align_up((size_t)nseg * 5 * (size_t)(R > 0 ? R : 0) * sizeof(double), 256) : 0;
-  l.prec_off = bytes + gbytes + state + seg;
+  const bool precise = c && disp_of(c).precise_grad > 0 && c->image_width > 0 && !attn;
+  const size_t prec = precise ? nseg * 5 * rays * sizeof(double) : 0;
+  l.prec_off = cv.take(prec);
+  l.has_precise = prec > 0;
   // cost-ordered block list of the lean tile kernels, next to the states it is valid with
-  const size_t sched = c ? align_up(tile_sched_bytes(R, c->image_width, c->image_height, c->num_samples), 256) : 0;
-  l.sched_off = bytes + gbytes + state + seg + prec;
-  l.total = bytes + gbytes + state + seg + prec + sched;
+  const size_t sched = c ? tile_sched_bytes(R, c->image_width, c->image_height, c->num_samples) : 0;
+  l.sched_off = cv.take(sched);
+  l.has_sched = sched > 0;
+  l.total = cv.off;
   // per-sample gradient sources of the two-phase backward of view-dependent grids (optional: without it the channel
-  // groups re-march the segment)
-  l.src_off = l.total;
-  const size_t srcb = c ? align_up(tile_src_bytes(R, c->image_width, c->image_height, c->num_samples, c->sh_degree, c->render_diffuse,
-                                                  g->feature_kind == VOXE_FEAT_ATTN), 256) : 0;
+  // groups re-march the segment) ...
+  const size_t srcb = c ? tile_src_bytes(R, c->image_width, c->image_height, c->num_samples, c->sh_degree, c->render_diffuse, attn) : 0;
+  l.has_src = srcb > 0;
+  l.src_off = cv.take(srcb);
   // ... and, behind the sources, the forward's per-sample (rad, v) in the same layout (r04: the source pass reads them instead of
   // gathering the wide texels again)
-  l.fwdval_off = l.total + srcb;
+  l.fwdval_off = cv.take(srcb);
   // ... and the group-planar staging gradient of the lean deposit passes (r05: [group][voxel][4], 16 bytes per voxel and group)
-  l.planar_off = l.total + 2 * srcb;
-  const size_t planarb = srcb ? align_up(tile_planar_bytes((long long)nvox, g->F + 1), 256) : 0;
-  l.total_with_src = l.total + 2 * srcb + planarb;
-  // deterministic mode: the fixed-point gradient and its scales behind everything else
-  l.det_off = l.total_with_src;
-  if (c && c->deterministic) l.total_with_src += det_bytes((long long)nvox, g->F + 1);
+  l.planar_off = cv.take(srcb ? tile_planar_bytes((long long)nvox, g->F + 1) : 0);
+  // deterministic mode: the fixed-point gradient and, in its last 256 bytes, its scales behind everything else
+  l.det_bytes = (c && c->deterministic) ? det_bytes((long long)nvox, g->F + 1) : 0;
+  l.det_off = cv.take(l.det_bytes ? l.det_bytes - 256 : 0);
+  l.det_scale_off = cv.take(l.det_bytes ? 256 : 0);
   // space-binned backward (voxe_render_region.hip): per-sample sources + segment tables
-  l.region_off = l.total_with_src;
-  l.region = false;
-  if (c && R > 0 && !c->deterministic && !force_no_tile_bwd(disp_of(c))) {
-    Variant v;
-    if (validate(g, c, R, &v) == VOXE_OK) {
-      DevGrid dg; HostCfg dc;
-      make_dev(g, c, R, v, &dg, &dc);
-      const bool tiled = tile_bwd_supported(dc, c->sh_degree);
-      l.region = region_bwd_supported(dg, dc, c->sh_degree, c->render_diffuse, tiled);
-      if (l.region)
-        l.total_with_src += region_scratch_bytes(g->X, g->Y, g->Z, R, c->num_samples,
-                                                 g->feature_kind != VOXE_FEAT_ATTN && c->sh_degree > 0 && !c->render_diffuse);
-    }
-  }
+  l.region_off = cv.take(region ? region_scratch_bytes(g->X, g->Y, g->Z, R, c->num_samples, !attn && c->sh_degree > 0 && !c->render_diffuse) : 0);
+  l.total_with_src = cv.off;
   return l;
 }
+// the part every call on a grid shares (grid step, point queries): packed grid + gradient region
+WsLayout grid_layout(const VoxeGridDesc* g) { return ws_layout(g, nullptr, 0, false); }
 
 int finish() { return hipGetLastError() == hipSuccess ? VOXE_OK : VOXE_ERR_LAUNCH; }
 
-// VoxeDispatch::precise_grad: the double segment sums exist only when the forward of these rays is
-// render_fwd_tile4_kernel<3, true> -- launch_fwd_t's condition, restated ONCE here for the forward, the re-march and the backward:
-// a depth-segmented march (nseg > 1), one segment per task, the lean forward's own conditions.  Everywhere else (S <= one segment,
-// fwd_segments_per_thread > 1, caller jitter, AABB clip, ...) the backward runs its default suffix arithmetic.
-bool precise_sums_apply(const WsLayout& l, const DevGrid& dg, const HostCfg& dc, const VoxeRenderCfg* cfg, const float* jitter) {
-  if (!(l.sched_off > l.prec_off) || cfg->sh_degree != 0 || dc.attn) return false;
-  if (num_segments(cfg->num_samples, dc.seg_len) <= 1 || dc.disp.fwd_segments_per_thread > 1) return false;
-  FwdArgs probe{};
-  probe.jitter = jitter;
-  probe.segbuf = reinterpret_cast<float*>(1);   // (the segment partials live in the same workspace tier as the sums)
-  return fwd_tile4_supported(dg, dc, probe, 3, 1);
+// ---- the plan of one render call -----------------------------------------------------------------------------------------------
+// Everything the entry points decide about a call -- which route it takes, how the workspace is carved, which optional buffers
+// exist -- is decided ONCE, in plan_render(); the forward, the backward, its re-march and the query functions read the plan.  The
+// forward and the backward of one render therefore agree on every buffer: both ask the same plan with the same workspace_bytes.
+//
+// Nominal vs effective: `route` / `region` are what the call does given the workspace voxe_workspace_bytes asks for.  A caller
+// may pass less; tier() says what a workspace of `workspace_bytes` holds and which route the call then takes: states and segment
+// partials need `total`, the region route, the two-phase buffers and the deterministic scratch need `total_with_src`.
+struct RenderPlan {
+  Variant v; DevGrid dg; HostCfg dc; WsLayout l;
+  int route = VOXE_ROUTE_NONE;   // nominal VOXE_ROUTE_*
+  int nseg = 1;                  // depth segments of a march
+  bool det = false, region = false, tiled = false, packed_bwd = false;   // deterministic | space-binned | LDS-window | line-dense scatter backward
+  bool two_phase_ok = false;     // view-dependent grid on the tile route with room planned for the per-sample sources
+  // VoxeDispatch::precise_grad: the double segment sums exist only when the forward of these rays is
+  // render_fwd_tile4_kernel<3, true> (launch_fwd_t's condition): a depth-segmented march (nseg > 1), one segment per task, the lean
+  // forward's own conditions.  Everywhere else (S <= one segment, fwd_segments_per_thread > 1, caller jitter, AABB clip, ...) the
+  // backward runs its default suffix arithmetic.
+  bool precise_sums_apply = false;
+
+  struct Tier {
+    bool full, with_src;         // workspace_bytes >= total | >= total_with_src
+    bool region, two_phase;      // the region route / the two-phase buffers are live
+    int route;                   // effective VOXE_ROUTE_*
+  };
+  Tier tier(size_t workspace_bytes) const {
+    const bool full = workspace_bytes >= l.total, with_src = workspace_bytes >= l.total_with_src;
+    Tier t{full, with_src, region && with_src, two_phase_ok && with_src, 0};
+    t.route = dc.R == 0 ? VOXE_ROUTE_NONE : det ? VOXE_ROUTE_DETERMINISTIC : t.region ? VOXE_ROUTE_REGION : tiled ? VOXE_ROUTE_TILE
+              : packed_bwd ? VOXE_ROUTE_PACKED_SCATTER : VOXE_ROUTE_SCATTER;
+    return t;
+  }
+  // layout of the gradient the backward leaves in the workspace (given the workspace voxe_workspace_bytes asks for)
+  int grad_layout() const {
+    if (dc.R == 0) return VOXE_GRAD_ANY;
+    return (route == VOXE_ROUTE_PACKED_SCATTER && !dc.linear_grad) ? VOXE_GRAD_BRICKED : VOXE_GRAD_LINEAR;
+  }
+};
+
+// Status of validate(); on VOXE_OK the whole plan is filled, otherwise only the layout (voxe_workspace_bytes answers for
+// descriptors a render call would refuse).  Reads tl_pair: call it inside the PairScope of the
+// launches it plans.  `jitter`: the caller's jitter array (the lean forward, hence the precise sums, exist only without one).
+int plan_render(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const float* jitter, RenderPlan* p) {
+  *p = RenderPlan();   // (zeroes dg / dc: a plan that was refused has R = 0)
+  const int st = validate(g, c, R, &p->v);
+  if (st == VOXE_OK) {
+    make_dev(g, c, R, p->v, &p->dg, &p->dc);
+    const VoxeDispatch& d = p->dc.disp;
+    p->nseg = num_segments(c->num_samples, p->dc.seg_len);
+    p->det = c->deterministic != 0;
+    p->tiled = tile_bwd_supported(p->dc, c->sh_degree) && !force_no_tile_bwd(d);
+    p->packed_bwd = !p->tiled && packed_scatter_supported(c->sh_degree) && !force_scatter_bwd(d);
+    p->region = R > 0 && !p->det && !force_no_tile_bwd(d) && region_bwd_supported(p->dg, p->dc, c->sh_degree, c->render_diffuse, p->tiled);
+  }
+  p->l = ws_layout(g, c, R, p->region);
+  if (st != VOXE_OK) return st;
+  p->route = p->tier(p->l.total_with_src).route;
+  p->two_phase_ok = p->tiled && p->l.has_src && !two_phase_disabled(p->dc.disp);
+  if (p->l.has_precise && c->sh_degree == 0 && !p->dc.attn && p->nseg > 1 && p->dc.disp.fwd_segments_per_thread <= 1) {
+    FwdArgs probe{};
+    probe.jitter = jitter;
+    probe.segbuf = reinterpret_cast<float*>(1);   // (the segment partials live in the same workspace tier as the sums)
+    p->precise_sums_apply = fwd_tile4_supported(p->dg, p->dc, probe, 3, 1);
+  }
+  return VOXE_OK;
+}
+
+// The FwdArgs of one march of the plan's rays through `workspace`: the forward itself (`out` = its outputs; keep = the caller
+// keeps the workspace for a backward of these rays) or a re-march of the backward (`out` = null: no outputs, everything a backward
+// reads is rebuilt).  One function, so that the two cannot disagree about sample_fwd, segsum_d, sched, ray_state or segbuf.
+struct FwdOutputs { float *colour, *depth, *acc, *disparity; };
+FwdArgs fwd_args(const RenderPlan& p, const RenderPlan::Tier& t, void* workspace, const float* rays_o, const float* rays_d,
+                 const float* jitter, const FwdOutputs* out, bool keep) {
+  const WsLayout& l = p.l;
+  const FwdOutputs o = out ? *out : FwdOutputs{};
+  FwdArgs a{at<float>(workspace, l.packed_off), rays_o, rays_d, jitter, o.colour, o.depth, o.acc, o.disparity, nullptr, nullptr};
+  a.keep_samples = keep;
+  if (t.region) return a;   // (the region kernels keep their states and tables in their own scratch)
+  // depth-segment states for the segmented backward, when that backward applies (a re-march runs only for a backward that reads them)
+  if (t.full && (p.tiled || p.packed_bwd || !out)) a.ray_state = at<float>(workspace, l.state_off);
+  if (t.full) a.segbuf = at<float>(workspace, l.seg_off);
+  if (t.full && keep && p.precise_sums_apply) a.segsum_d = at<double>(workspace, l.prec_off);
+  if (t.full && l.has_sched) a.sched = at<int>(workspace, l.sched_off);
+  if (keep && t.two_phase) a.sample_fwd = at<float>(workspace, l.fwdval_off);   // (what the two-phase backward will read)
+  return a;
 }
 
 // ---- what the last forward left in a workspace --------------------------------------------------------------------
@@ -375,43 +477,38 @@ int voxe_random_subset(int64_t n, int64_t count, uint64_t seed, uint64_t rng_off
 // test aid (not part of voxe.h): where the cost-ordered block list of the lean tile kernels lives in the workspace of this render --
 // out = (1 when launches of this configuration build one, byte offset, blocks of a launch, tile slots of a launch)
 int voxe_tile_sched_debug_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, int64_t out[4]) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, nullptr, &p);
   if (st) return st;
   if (!out) return VOXE_ERR_NULL_POINTER;
-  DevGrid dg; HostCfg dc;
-  make_dev(grid, cfg, R, v, &dg, &dc);
-  const WsLayout l = ws_layout(grid, cfg, R);
+  const HostCfg& dc = p.dc;
   const int64_t ntp = dc.image_width > 0 ? blocks_for_tiles(dc.map_mode, (dc.image_width + 7) / 8, tile_rows_total(dc, 8)) : 0;
-  out[0] = (l.total > l.sched_off && tile_sched_applies(dc)) ? 1 : 0;
-  out[1] = (int64_t)l.sched_off;
-  out[2] = ntp * num_segments(dc.S, dc.seg_len);
+  out[0] = (p.l.has_sched && tile_sched_applies(dc)) ? 1 : 0;
+  out[1] = (int64_t)p.l.sched_off;
+  out[2] = ntp * p.nseg;
   out[3] = ntp;
   return VOXE_OK;
 }
 
 size_t voxe_workspace_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
-  if (!grid || grid->X <= 0 || grid->Y <= 0 || grid->Z <= 0 || grid->F <= 0) return 0;
-  const WsLayout l = ws_layout(grid, cfg, R);
+  RenderPlan p;
+  (void)plan_render(grid, cfg, R, nullptr, &p);   // (sizes are answered for descriptors a render call would refuse, too)
   // ray_state_valid = -1 (inference: no backward of these rays follows): the packed grid and the segmented forward's states /
   // partials -- none of the backward's per-sample sources, staging gradient or binning scratch (gigabytes at large R)
-  if (cfg && cfg->ray_state_valid < 0) return l.total;
-  return l.total_with_src;
+  return (cfg && cfg->ray_state_valid < 0) ? p.l.total : p.l.total_with_src;
 }
 
 int voxe_render_fwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o,
                     const float* rays_d, int64_t R, const float* jitter, float* colour, float* depth,
                     float* acc, float* disparity, void* workspace, size_t workspace_bytes,
                     void* stream) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, jitter, &p);
   if (st) return st;
   if (R > 0 && (!rays_o || !rays_d || !colour)) return VOXE_ERR_NULL_POINTER;
-  const WsLayout l = ws_layout(grid, cfg, R);
-  if (!workspace || workspace_bytes < l.fwd_total) return VOXE_ERR_WORKSPACE;
+  if (!workspace || workspace_bytes < p.l.fwd_total) return VOXE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  float* packed = (float*)((char*)workspace + l.packed_off);
-  if (!cfg->reuse_packed_grid) { PhaseTimer t(PH_PACK, s); launch_pack_any(grid, packed, s); }
+  if (!cfg->reuse_packed_grid) { PhaseTimer t(PH_PACK, s); launch_pack_any(grid, at<float>(workspace, p.l.packed_off), s); }
   if (R == 0) return finish();
   {
     // what this workspace holds from now on (a backward's ray_state_valid = 1 is checked against it)
@@ -419,120 +516,101 @@ int voxe_render_fwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const fl
     k.kept = cfg->ray_state_valid >= 0 ? 1 : 0;
     record_stamp(workspace, k);
   }
-  DevGrid dg; HostCfg dc;
-  make_dev(grid, cfg, R, v, &dg, &dc);
-  // depth-segment states for the segmented backward, when that backward applies and the workspace holds them
-  float* state = nullptr;
-  const bool tiled = tile_bwd_supported(dc, cfg->sh_degree) && !force_no_tile_bwd(dc.disp);
-  const bool packed_bwd = !tiled && packed_scatter_supported(cfg->sh_degree) && !force_scatter_bwd(dc.disp);
-  if ((tiled || packed_bwd) && workspace_bytes >= l.total) state = (float*)((char*)workspace + l.state_off);
-  float* segbuf = workspace_bytes >= l.total ? (float*)((char*)workspace + l.seg_off) : nullptr;
-  FwdArgs a{packed, rays_o, rays_d, jitter, colour, depth, acc, disparity, state, segbuf};
-  a.keep_samples = cfg->ray_state_valid >= 0;
-  if (segbuf && cfg->ray_state_valid >= 0 && precise_sums_apply(l, dg, dc, cfg, jitter)) a.segsum_d = (double*)((char*)workspace + l.prec_off);
-  if (segbuf && l.total > l.sched_off) a.sched = (int*)((char*)workspace + l.sched_off);
-  if (cfg->ray_state_valid >= 0 && tiled && l.fwdval_off > l.src_off && workspace_bytes >= l.total_with_src && !two_phase_disabled(dc.disp))
-    a.sample_fwd = (float*)((char*)workspace + l.fwdval_off);   // (what render_bwd_common's two-phase backward will read)
-  if (l.region && workspace_bytes >= l.total_with_src) {
+  const RenderPlan::Tier tier = p.tier(workspace_bytes);
+  const FwdOutputs out{colour, depth, acc, disparity};
+  const FwdArgs a = fwd_args(p, tier, workspace, rays_o, rays_d, jitter, &out, cfg->ray_state_valid >= 0);
+  if (tier.region) {
     // space-binned path (unordered / sparse rays): forward through the region kernels; the segment tables and per-segment
     // states stay in the workspace for the backward of the same call (cfg->ray_state_valid)
     PhaseTimer t(PH_FWD, s);
-    launch_fwd_region(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, (char*)workspace + l.region_off, s);
+    launch_fwd_region(p.dg, p.dc, cfg->sh_degree, cfg->render_diffuse, a, at<char>(workspace, p.l.region_off), s);
     return finish();
   }
-  { PhaseTimer t(PH_FWD, s); launch_fwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s); }
+  { PhaseTimer t(PH_FWD, s); launch_fwd(p.dg, p.dc, cfg->sh_degree, cfg->render_diffuse, a, s); }
   return finish();
 }
 
 }  // extern "C" (reopened below)
 
 namespace {
+// what the three backward entry points check before anything else; on VOXE_OK *p is the plan of the call
+int plan_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, const float* jitter, const float* rays_o,
+             const float* rays_d, const float* colour, const float* depth, const float* acc, const float* d_colour, RenderPlan* p) {
+  const int st = plan_render(grid, cfg, R, jitter, p);
+  if (st) return st;
+  if (R > 0 && (!rays_o || !rays_d || !colour || !depth || !acc || !d_colour)) return VOXE_ERR_NULL_POINTER;
+  return VOXE_OK;
+}
+
 // memset (optional) + backward kernel into the workspace's packed gradient region; *bricked = layout of that region
-int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Variant& v, const float* rays_o,
+int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const RenderPlan& p, const float* rays_o,
                       const float* rays_d, int64_t R, const float* jitter, const float* colour, const float* depth,
                       const float* acc, const float* d_colour, const float* d_depth, const float* d_acc, bool want_d,
                       bool want_f, bool zero_first, bool* bricked, void* workspace, size_t workspace_bytes,
-                      hipStream_t s, void* grad_workspace = nullptr, size_t grad_workspace_bytes = 0) {
-  const WsLayout l = ws_layout(grid, cfg, R);
+                      hipStream_t s, void* grad_workspace, size_t grad_workspace_bytes) {
+  const WsLayout& l = p.l;
   if (!workspace || workspace_bytes < l.total) return VOXE_ERR_WORKSPACE;
   if (grad_workspace && grad_workspace_bytes < l.state_off) return VOXE_ERR_WORKSPACE;   // (packed grid + gradient region)
-  float* packed = (float*)((char*)workspace + l.packed_off);
-  float* gpacked = (float*)((char*)(grad_workspace ? grad_workspace : workspace) + l.grad_off);
-  float* state = (float*)((char*)workspace + l.state_off);
+  float* packed = at<float>(workspace, l.packed_off);
+  float* gpacked = at<float>(grad_workspace ? grad_workspace : workspace, l.grad_off);
   if (!cfg->reuse_packed_grid) { PhaseTimer t(PH_PACK, s); launch_pack_any(grid, packed, s); }
   if (zero_first) {
     PhaseTimer t(PH_MEMSET, s);
-    if (hipMemsetAsync(gpacked, 0, l.state_off - l.grad_off, s) != hipSuccess) return VOXE_ERR_LAUNCH;
+    if (hipMemsetAsync(gpacked, 0, l.grad_bytes(), s) != hipSuccess) return VOXE_ERR_LAUNCH;
   }
   *bricked = false;
-  if (R > 0) {
-    DevGrid dg; HostCfg dc;
-    make_dev(grid, cfg, R, v, &dg, &dc);
-    const bool tiled = tile_bwd_supported(dc, cfg->sh_degree) && !force_no_tile_bwd(dc.disp);
-    const bool packed_bwd = !tiled && packed_scatter_supported(cfg->sh_degree) && !force_scatter_bwd(dc.disp);
-    BwdArgs a{packed, rays_o, rays_d, jitter, colour, depth, acc, d_colour, d_depth, d_acc, gpacked,
-              want_d, want_f, (tiled || packed_bwd) ? state : nullptr};
-    const bool precise = precise_sums_apply(l, dg, dc, cfg, jitter);
-    if (precise) a.segsum_d = (const double*)((char*)workspace + l.prec_off);
-    // (the forward of these rays -- voxe_render_fwd with this workspace or the re-march below -- built the list whenever it ran
-    // the lean forward)
-    if (l.total > l.sched_off) a.sched = (const int*)((char*)workspace + l.sched_off);
-    const bool two_phase = tiled && l.fwdval_off > l.src_off && workspace_bytes >= l.total_with_src && !two_phase_disabled(dc.disp);
-    if (two_phase) {
-      a.sample_src = (float*)((char*)workspace + l.src_off);
-      // the forward of these rays (voxe_render_fwd with this workspace, or the re-march below) wrote its per-sample values when it
-      // ran the depth-segmented kernel: launch_fwd_t's condition
-      if (num_segments(cfg->num_samples, dc.seg_len) > 1) a.sample_fwd = (const float*)((char*)workspace + l.fwdval_off);
-      a.grad_planar = (float*)((char*)workspace + l.planar_off);
-    }
-    if (cfg->deterministic) {
-      if (!det_bwd_supported(dc, cfg->sh_degree, cfg->render_diffuse)) return VOXE_ERR_UNSUPPORTED;
-      if (workspace_bytes < l.total_with_src) return VOXE_ERR_WORKSPACE;
-      a.gdet = (unsigned long long*)((char*)workspace + l.det_off);
-      a.det_scale = (float*)((char*)workspace + l.det_off + det_bytes((long long)grid->X * grid->Y * grid->Z, grid->F + 1) - 256);
-      a.ray_state = state;
-    }
-    const bool det = cfg->deterministic != 0;
-    const bool region = l.region && !det && workspace_bytes >= l.total_with_src;
-    // the caller's claim that the workspace holds this render's forward is only believed when the forward's record says so
-    const FwdStamp stamp = make_stamp(grid, cfg, rays_o, rays_d, R, jitter, workspace_bytes);
-    const bool states_valid = cfg->ray_state_valid > 0 && stamp_matches(workspace, stamp);
-    if (!states_valid) {
-      // (the re-march below writes everything a backward reads: from here on the workspace holds THIS render)
-      FwdStamp k = stamp;
-      k.kept = 1;
-      record_stamp(workspace, k);
-    }
-    if (region && !states_valid) {
-      // the caller's workspace does not hold this call's segment tables / states: rebuild them (no outputs)
-      PhaseTimer t(PH_FWD, s);
-      FwdArgs f{packed, rays_o, rays_d, jitter, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      launch_fwd_region(dg, dc, cfg->sh_degree, cfg->render_diffuse, f, (char*)workspace + l.region_off, s);
-    } else if ((tiled || packed_bwd || det) && !states_valid) {
-      // the caller's workspace does not hold this call's forward states: re-march to rebuild them
-      PhaseTimer t(PH_FWD, s);
-      FwdArgs f{packed, rays_o, rays_d, jitter, nullptr, nullptr, nullptr, nullptr, state,
-                (float*)((char*)workspace + l.seg_off)};
-      if (two_phase) f.sample_fwd = (float*)((char*)workspace + l.fwdval_off);
-      if (precise) f.segsum_d = (double*)((char*)workspace + l.prec_off);
-      if (l.total > l.sched_off) f.sched = (int*)((char*)workspace + l.sched_off);
-      launch_fwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, f, s);
-    }
-    PhaseTimer t(PH_BWD, s);
-    if (det) {
-      // (the fixed-point region must start cleared: the finalize pass leaves it so, the first use clears it here)
-      if (hipMemsetAsync(a.gdet, 0, det_bytes((long long)grid->X * grid->Y * grid->Z, grid->F + 1), s) != hipSuccess)
-        return VOXE_ERR_LAUNCH;
-      launch_bwd_tile(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
-    } else if (region) {
-      launch_bwd_region(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, (char*)workspace + l.region_off, s);
-    } else if (tiled)
-      launch_bwd_tile(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
-    else if (packed_bwd) {
-      launch_bwd_packed_scatter(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
-      *bricked = !cfg->linear_grad;  // that kernel accumulates into the bricked layout unless asked otherwise
-    } else
-      launch_bwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
+  if (R == 0) return VOXE_OK;
+  const DevGrid& dg = p.dg; const HostCfg& dc = p.dc;
+  const RenderPlan::Tier tier = p.tier(workspace_bytes);
+  float* state = at<float>(workspace, l.state_off);
+  BwdArgs a{packed, rays_o, rays_d, jitter, colour, depth, acc, d_colour, d_depth, d_acc, gpacked,
+            want_d, want_f, (p.tiled || p.packed_bwd) ? state : nullptr};
+  // (the forward of these rays -- voxe_render_fwd with this workspace or the re-march below -- wrote the sums, the list and its
+  // per-sample values under the same plan: fwd_args())
+  if (p.precise_sums_apply) a.segsum_d = at<const double>(workspace, l.prec_off);
+  if (l.has_sched) a.sched = at<const int>(workspace, l.sched_off);
+  if (tier.two_phase) {
+    a.sample_src = at<float>(workspace, l.src_off);
+    if (p.nseg > 1) a.sample_fwd = at<const float>(workspace, l.fwdval_off);   // (only the depth-segmented forward writes them)
+    a.grad_planar = at<float>(workspace, l.planar_off);
+  }
+  if (p.det) {
+    if (!det_bwd_supported(dc, cfg->sh_degree, cfg->render_diffuse)) return VOXE_ERR_UNSUPPORTED;
+    if (!tier.with_src) return VOXE_ERR_WORKSPACE;
+    a.gdet = at<unsigned long long>(workspace, l.det_off);
+    a.det_scale = at<float>(workspace, l.det_scale_off);
+    a.ray_state = state;
+  }
+  // the caller's claim that the workspace holds this render's forward is only believed when the forward's record says so
+  const FwdStamp stamp = make_stamp(grid, cfg, rays_o, rays_d, R, jitter, workspace_bytes);
+  const bool states_valid = cfg->ray_state_valid > 0 && stamp_matches(workspace, stamp);
+  if (!states_valid) {
+    // (the re-march below writes everything a backward reads: from here on the workspace holds THIS render)
+    FwdStamp k = stamp;
+    k.kept = 1;
+    record_stamp(workspace, k);
+  }
+  if (!states_valid && tier.route != VOXE_ROUTE_SCATTER) {
+    // the caller's workspace does not hold this call's forward states (region route: segment tables too): re-march, no outputs
+    PhaseTimer t(PH_FWD, s);
+    const FwdArgs f = fwd_args(p, tier, workspace, rays_o, rays_d, jitter, nullptr, true);
+    if (tier.region) launch_fwd_region(dg, dc, cfg->sh_degree, cfg->render_diffuse, f, at<char>(workspace, l.region_off), s);
+    else launch_fwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, f, s);
+  }
+  PhaseTimer t(PH_BWD, s);
+  if (tier.route == VOXE_ROUTE_DETERMINISTIC) {
+    // (the fixed-point region must start cleared: the finalize pass leaves it so, the first use clears it here)
+    if (hipMemsetAsync(a.gdet, 0, l.det_bytes, s) != hipSuccess) return VOXE_ERR_LAUNCH;
+    launch_bwd_tile(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
+  } else if (tier.route == VOXE_ROUTE_REGION) {
+    launch_bwd_region(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, at<char>(workspace, l.region_off), s);
+  } else if (tier.route == VOXE_ROUTE_TILE) {
+    launch_bwd_tile(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
+  } else if (tier.route == VOXE_ROUTE_PACKED_SCATTER) {
+    launch_bwd_packed_scatter(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
+    *bricked = !cfg->linear_grad;  // that kernel accumulates into the bricked layout unless asked otherwise
+  } else {
+    launch_bwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
   }
   return VOXE_OK;
 }
@@ -545,24 +623,17 @@ int voxe_render_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const fl
                     const float* depth, const float* acc, const float* d_colour, const float* d_depth,
                     const float* d_acc, float* d_densities, float* d_features, int32_t accumulate,
                     void* workspace, size_t workspace_bytes, void* stream) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_bwd(grid, cfg, R, jitter, rays_o, rays_d, colour, depth, acc, d_colour, &p);
   if (st) return st;
-  if (R > 0 && (!rays_o || !rays_d || !colour || !depth || !acc || !d_colour))
-    return VOXE_ERR_NULL_POINTER;
   if (!d_densities && !d_features) return VOXE_OK;
   hipStream_t s = (hipStream_t)stream;
   bool bricked = false;
-  const int rc = render_bwd_common(grid, cfg, v, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc,
+  const int rc = render_bwd_common(grid, cfg, p, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc,
                                    d_densities != nullptr, d_features != nullptr, true, &bricked, workspace,
-                                   workspace_bytes, s);
+                                   workspace_bytes, s, nullptr, 0);
   if (rc) return rc;
-  {
-    const WsLayout l = ws_layout(grid, cfg, R);
-    PhaseTimer t(PH_UNPACK, s);
-    launch_unpack_any(grid, (const float*)((char*)workspace + l.grad_off), d_densities, d_features, accumulate,
-                      bricked ? 1 : 0, s);
-  }
+  { PhaseTimer t(PH_UNPACK, s); launch_unpack_any(grid, at<const float>(workspace, p.l.grad_off), d_densities, d_features, accumulate, bricked ? 1 : 0, s); }
   return finish();
 }
 
@@ -571,18 +642,8 @@ int voxe_render_bwd_acc(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, cons
                         const float* d_colour, const float* d_depth, const float* d_acc, int32_t want_densities,
                         int32_t want_features, int32_t zero_first, int32_t* grad_layout, void* workspace,
                         size_t workspace_bytes, void* stream) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
-  if (st) return st;
-  if (!grad_layout || (R > 0 && (!rays_o || !rays_d || !colour || !depth || !acc || !d_colour)))
-    return VOXE_ERR_NULL_POINTER;
-  bool bricked = false;
-  const int rc = render_bwd_common(grid, cfg, v, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc,
-                                   want_densities != 0, want_features != 0, zero_first != 0, &bricked, workspace,
-                                   workspace_bytes, (hipStream_t)stream);
-  if (rc) return rc;
-  *grad_layout = R > 0 ? (bricked ? VOXE_GRAD_BRICKED : VOXE_GRAD_LINEAR) : VOXE_GRAD_ANY;
-  return finish();
+  return voxe_render_bwd_acc_into(grid, cfg, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc, want_densities,
+                                  want_features, zero_first, grad_layout, workspace, workspace_bytes, nullptr, 0, stream);
 }
 
 int voxe_render_bwd_acc_into(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d,
@@ -590,13 +651,12 @@ int voxe_render_bwd_acc_into(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
                              const float* d_colour, const float* d_depth, const float* d_acc, int32_t want_densities,
                              int32_t want_features, int32_t zero_first, int32_t* grad_layout, void* workspace,
                              size_t workspace_bytes, void* grad_workspace, size_t grad_workspace_bytes, void* stream) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_bwd(grid, cfg, R, jitter, rays_o, rays_d, colour, depth, acc, d_colour, &p);
   if (st) return st;
-  if (!grad_layout || (R > 0 && (!rays_o || !rays_d || !colour || !depth || !acc || !d_colour)))
-    return VOXE_ERR_NULL_POINTER;
+  if (!grad_layout) return VOXE_ERR_NULL_POINTER;
   bool bricked = false;
-  const int rc = render_bwd_common(grid, cfg, v, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc,
+  const int rc = render_bwd_common(grid, cfg, p, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc,
                                    want_densities != 0, want_features != 0, zero_first != 0, &bricked, workspace,
                                    workspace_bytes, (hipStream_t)stream, grad_workspace, grad_workspace_bytes);
   if (rc) return rc;
@@ -604,32 +664,19 @@ int voxe_render_bwd_acc_into(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
   return finish();
 }
 
+// the two answers below are nominal: given the workspace voxe_workspace_bytes asks for
 int voxe_render_bwd_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, nullptr, &p);
   if (st) return st < -1 ? st : VOXE_ERR_BAD_SHAPE;
-  if (R == 0) return VOXE_GRAD_ANY;
-  DevGrid dg; HostCfg dc;
-  make_dev(grid, cfg, R, v, &dg, &dc);
-  if (cfg->deterministic) return VOXE_GRAD_LINEAR;
-  const bool tiled = tile_bwd_supported(dc, cfg->sh_degree) && !force_no_tile_bwd(dc.disp);
-  const bool packed_bwd = !tiled && packed_scatter_supported(cfg->sh_degree) && !force_scatter_bwd(dc.disp);
-  if (ws_layout(grid, cfg, R).region) return VOXE_GRAD_LINEAR;   // (given the workspace voxe_workspace_bytes asks for)
-  return (packed_bwd && !cfg->linear_grad) ? VOXE_GRAD_BRICKED : VOXE_GRAD_LINEAR;
+  return p.grad_layout();
 }
 
 int voxe_render_route(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, nullptr, &p);
   if (st) return st < -1 ? st : VOXE_ERR_BAD_SHAPE;
-  if (R == 0) return VOXE_ROUTE_NONE;
-  DevGrid dg; HostCfg dc;
-  make_dev(grid, cfg, R, v, &dg, &dc);
-  if (cfg->deterministic) return VOXE_ROUTE_DETERMINISTIC;
-  if (ws_layout(grid, cfg, R).region) return VOXE_ROUTE_REGION;
-  if (tile_bwd_supported(dc, cfg->sh_degree) && !force_no_tile_bwd(dc.disp)) return VOXE_ROUTE_TILE;
-  if (packed_scatter_supported(cfg->sh_degree) && !force_scatter_bwd(dc.disp)) return VOXE_ROUTE_PACKED_SCATTER;
-  return VOXE_ROUTE_SCATTER;
+  return p.route;
 }
 
 int voxe_disparity_bwd(const float* depth, const float* acc, const float* d_disparity, const float* d_depth_in,
@@ -644,26 +691,25 @@ namespace {
 #ifndef VOXE_RECON_PAIRED
 #define VOXE_RECON_PAIRED 1
 #endif
-inline size_t up256b(size_t x) { return (x + 255) / 256 * 256; }
 struct ReconLayout { size_t subset, rays_o, rays_d, target, out[2], d_colour[2], partial, out2, d_colour2, batch2, total; };
 ReconLayout recon_layout(int64_t B) {
   ReconLayout l;
-  size_t off = 0;
+  Carve cv;
   const size_t b = (size_t)(B > 0 ? B : 0);
-  l.subset = off; off += up256b(b * sizeof(int64_t));
-  l.rays_o = off; off += up256b(b * 3 * sizeof(float));
-  l.rays_d = off; off += up256b(b * 3 * sizeof(float));
-  l.target = off; off += up256b(b * 3 * sizeof(float));
-  l.batch2 = off;   // (the same four buffers again, behind everything else: the batch voxe_recon_prefetch assembles ahead of its iteration)
-  for (int i = 0; i < 2; ++i) { l.out[i] = off; off += up256b(b * 5 * sizeof(float)); }        // colour [B,3] | depth [B] | acc [B]
-  for (int i = 0; i < 2; ++i) { l.d_colour[i] = off; off += up256b(b * 3 * sizeof(float)); }
-  l.partial = off; off += up256b(l1_scratch_bytes());
+  l.subset = cv.take(b * sizeof(int64_t));
+  l.rays_o = cv.take(b * 3 * sizeof(float));
+  l.rays_d = cv.take(b * 3 * sizeof(float));
+  l.target = cv.take(b * 3 * sizeof(float));
+  const size_t batch_bytes = cv.off;
+  for (int i = 0; i < 2; ++i) l.out[i] = cv.take(b * 5 * sizeof(float));        // colour [B,3] | depth [B] | acc [B]
+  for (int i = 0; i < 2; ++i) l.d_colour[i] = cv.take(b * 3 * sizeof(float));
+  l.partial = cv.take(l1_scratch_bytes());
   // paired render: colour [2B,3] | depth [2B] | acc [2B], d_colour [2B,3]
-  l.out2 = off; off += up256b(2 * b * 5 * sizeof(float));
-  l.d_colour2 = off; off += up256b(2 * b * 3 * sizeof(float));
-  const size_t batch_bytes = l.batch2;
-  l.batch2 = off; off += batch_bytes;
-  l.total = off;
+  l.out2 = cv.take(2 * b * 5 * sizeof(float));
+  l.d_colour2 = cv.take(2 * b * 3 * sizeof(float));
+  // the same four buffers again, behind everything else: the batch voxe_recon_prefetch assembles ahead of its iteration
+  l.batch2 = cv.take(batch_bytes);
+  l.total = cv.off;
   return l;
 }
 
@@ -733,8 +779,8 @@ VoxeRenderCfg recon_pair_cfg(const VoxeRenderCfg* cfg) {
 }
 struct ReconBatchPtrs { int64_t* subset; float *rays_o, *rays_d, *target; };
 ReconBatchPtrs recon_batch_ptrs(const ReconLayout& l, void* scratch, int slot) {
-  char* sc = (char*)scratch + (slot ? l.batch2 : 0);
-  return ReconBatchPtrs{(int64_t*)(sc + l.subset), (float*)(sc + l.rays_o), (float*)(sc + l.rays_d), (float*)(sc + l.target)};
+  void* sc = at<char>(scratch, slot ? l.batch2 : 0);
+  return ReconBatchPtrs{at<int64_t>(sc, l.subset), at<float>(sc, l.rays_o), at<float>(sc, l.rays_d), at<float>(sc, l.target)};
 }
 int recon_check(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const VoxeReconStep* rs) {
   if (!grid || !cfg || !rs || !rs->poses || !rs->images || !rs->losses) return VOXE_ERR_NULL_POINTER;
@@ -763,11 +809,9 @@ int voxe_recon_prefetch(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, cons
   const VoxeRenderCfg pc = recon_pair_cfg(cfg);
   const PairSpec pair{B, cfg->rng_offset + 2};
   PairScope scope(&pair);
-  const WsLayout wl = ws_layout(grid, &pc, 2 * B);
-  if (!wl.region || workspace_bytes < wl.total_with_src || workspace2_bytes < wl.total_with_src) return VOXE_OK;
-  Variant v;
-  const int st = validate(grid, &pc, 2 * B, &v);
-  if (st) return st;
+  RenderPlan plan;
+  (void)plan_render(grid, &pc, 2 * B, nullptr, &plan);   // (a render the plan refuses takes no region route: the hint is dropped)
+  if (!plan.tier(workspace_bytes).region || !plan.tier(workspace2_bytes).region) return VOXE_OK;
   hipStream_t s = (hipStream_t)stream;
   std::lock_guard<std::mutex> lock(g_recon_mu);
   if (g_recon.size() >= kMaxReconSides && g_recon.find(workspace) == g_recon.end()) {
@@ -803,12 +847,10 @@ int voxe_recon_prefetch(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, cons
   const ReconBatchPtrs bp = recon_batch_ptrs(l, scratch, slot);
   launch_recon_batch(B, cfg->seed, cfg->rng_offset, rs->H, rs->W, rs->focal, rs->K, rs->poses, rs->images,
                      (const long long*)rs->image_rows, rs->num_images, (long long*)bp.subset, bp.rays_o, bp.rays_d, bp.target, rsd.side);
-  DevGrid dg; HostCfg dc;
-  make_dev(grid, &pc, 2 * B, v, &dg, &dc);
-  void* const tables = (char*)(slot ? workspace2 : workspace) + wl.region_off;
-  launch_bin_region(dg, dc, bp.rays_o, bp.rays_d, nullptr, tables, rsd.side, /*phase=*/1);      // counters cleared
+  void* const tables = at<char>(slot ? workspace2 : workspace, plan.l.region_off);
+  launch_bin_region(plan.dg, plan.dc, bp.rays_o, bp.rays_d, nullptr, tables, rsd.side, /*phase=*/1);      // counters cleared
   if (VOXE_RECON_FORK == 2 || VOXE_RECON_FORK == 3) (void)hipStreamWaitEvent(rsd.side, rsd.fork, 0);
-  launch_bin_region(dg, dc, bp.rays_o, bp.rays_d, nullptr, tables, rsd.side, /*phase=*/2);      // segments -> sorted tables
+  launch_bin_region(plan.dg, plan.dc, bp.rays_o, bp.rays_d, nullptr, tables, rsd.side, /*phase=*/2);      // segments -> sorted tables
   (void)hipEventRecord(rsd.pend.done, rsd.side);
   rsd.pend.valid = true;
   rsd.pend.slot = slot;
@@ -834,7 +876,6 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
   const ReconLayout l = recon_layout(rs->batch);
   if (!scratch || scratch_bytes < l.total) return VOXE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  char* sc = (char*)scratch;
   const int64_t B = rs->batch;
   int st = VOXE_OK;
   // a prefetch pending on this workspace: the step waits for the side stream whether or not it takes the tables (they may be
@@ -866,8 +907,9 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
     pc.reuse_packed_grid = cfg->reuse_packed_grid;
     const PairSpec pair{B, cfg->rng_offset + 2};
     PairScope scope(&pair);
-    const WsLayout wl = ws_layout(grid, &pc, 2 * B);
-    if (wl.region && workspace_bytes >= wl.total_with_src) {
+    RenderPlan plan;
+    (void)plan_render(grid, &pc, 2 * B, nullptr, &plan);
+    if (plan.tier(workspace_bytes).region) {
       int slot = 0;
       if (pending) {
         const ReconBatchPtrs pp = recon_batch_ptrs(l, scratch, pend_slot);
@@ -898,11 +940,11 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
         const auto it = g_recon.find(workspace);
         if (it != g_recon.end()) mid = it->second.fork;
       }
-      const RegionBins bins{slot ? (void*)((char*)workspace2 + wl.region_off) : nullptr, prebinned ? 1 : 0, mid};
+      const RegionBins bins{slot ? at<void>(workspace2, plan.l.region_off) : nullptr, prebinned ? 1 : 0, mid};
       struct BinsScope { explicit BinsScope(const RegionBins* b) { tl_region_bins = b; } ~BinsScope() { tl_region_bins = nullptr; } } bscope(&bins);
-      float* colour = (float*)(sc + l.out2);
+      float* colour = at<float>(scratch, l.out2);
       float *depth = colour + 6 * B, *acc = depth + 2 * B;
-      float* d_colour = (float*)(sc + l.d_colour2);
+      float* d_colour = at<float>(scratch, l.d_colour2);
       st = voxe_render_fwd(grid, &pc, bp.rays_o, bp.rays_d, 2 * B, nullptr, colour, depth, acc, nullptr, workspace, workspace_bytes, stream);
       if (st) return st;
       if (have_side) {
@@ -915,7 +957,7 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
           else if (VOXE_RECON_FORK != 0) { (void)hipEventRecord(rsd.fork, s); rsd.forked = true; }
         }
       }
-      launch_l1_loss_grad_n(colour, bp.target, 3 * B, 2, d_colour, rs->losses, sc + l.partial, s);   // both renders, one launch pair
+      launch_l1_loss_grad_n(colour, bp.target, 3 * B, 2, d_colour, rs->losses, at<char>(scratch, l.partial), s);   // both renders, one launch pair
       pc.ray_state_valid = 1;
       pc.reuse_packed_grid = 1;
       int32_t layout = VOXE_GRAD_ANY;
@@ -930,10 +972,10 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
                                  stream);
     }
   }
-  int64_t* subset = (int64_t*)(sc + l.subset);
-  float* rays_o = (float*)(sc + l.rays_o);
-  float* rays_d = (float*)(sc + l.rays_d);
-  float* target = (float*)(sc + l.target);
+  int64_t* subset = at<int64_t>(scratch, l.subset);
+  float* rays_o = at<float>(scratch, l.rays_o);
+  float* rays_d = at<float>(scratch, l.rays_d);
+  float* target = at<float>(scratch, l.target);
   launch_recon_batch(B, cfg->seed, cfg->rng_offset, rs->H, rs->W, rs->focal, rs->K, rs->poses, rs->images,
                      (const long long*)rs->image_rows, rs->num_images, (long long*)subset, rays_o, rays_d, target, s);
   VoxeRenderCfg rc[2] = {*cfg, *cfg};
@@ -945,19 +987,19 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
     rc[i].render_diffuse = i == 1 ? 1 : cfg->render_diffuse;
     rc[i].linear_grad = 1;                         // both renders write ONE gradient layout, whatever kernel runs
     if (i == 1) rc[i].reuse_packed_grid = 0;       // the second workspace still holds the previous iteration's grid
-    float* colour = (float*)(sc + l.out[i]);
+    float* colour = at<float>(scratch, l.out[i]);
     float *depth = colour + 3 * B, *acc = depth + B;
     st = voxe_render_fwd(grid, &rc[i], rays_o, rays_d, B, nullptr, colour, depth, acc, nullptr, ws[i], wsb[i], stream);
     if (st) return st;
-    launch_l1_loss_grad(colour, target, 3 * B, (float*)(sc + l.d_colour[i]), rs->losses + 2 * i, sc + l.partial, s);
+    launch_l1_loss_grad(colour, target, 3 * B, at<float>(scratch, l.d_colour[i]), rs->losses + 2 * i, at<char>(scratch, l.partial), s);
   }
   for (int i = 0; i < nrender; ++i) {
-    float* colour = (float*)(sc + l.out[i]);
+    float* colour = at<float>(scratch, l.out[i]);
     float *depth = colour + 3 * B, *acc = depth + B;
     rc[i].ray_state_valid = 1;                     // the forward above left this render's states in ws[i]
     rc[i].reuse_packed_grid = 1;
     int32_t layout = VOXE_GRAD_ANY;
-    st = voxe_render_bwd_acc_into(grid, &rc[i], rays_o, rays_d, B, nullptr, colour, depth, acc, (const float*)(sc + l.d_colour[i]),
+    st = voxe_render_bwd_acc_into(grid, &rc[i], rays_o, rays_d, B, nullptr, colour, depth, acc, at<const float>(scratch, l.d_colour[i]),
                                   nullptr, nullptr, rs->exp_avg_densities != nullptr, rs->exp_avg_features != nullptr,
                                   /*zero_first=*/(i == 0 && rs->zero_gradient_first) ? 1 : 0, &layout, ws[i], wsb[i], i == 0 ? nullptr : workspace,
                                   i == 0 ? 0 : workspace_bytes, stream);
@@ -973,14 +1015,14 @@ namespace {
 struct RefineLayout { size_t out, d_render, tv_grad, tv_scratch, l1_scratch, total; };
 RefineLayout refine_layout(const VoxeGridDesc* g, int64_t R) {
   RefineLayout l;
-  size_t off = 0;
+  Carve cv;
   const size_t r = (size_t)(R > 0 ? R : 0);
-  l.out = off; off += up256b(r * 4 * sizeof(float));          // attn [R] | depth [R] | acc [R] | (spare)
-  l.d_render = off; off += up256b(r * sizeof(float));
-  l.tv_grad = off; off += up256b((size_t)g->X * g->Y * g->Z * sizeof(float));
-  l.tv_scratch = off; off += up256b(tv_scratch_bytes(g->X, g->Y, g->Z, 1));
-  l.l1_scratch = off; off += up256b(attn_l1_scratch_bytes());
-  l.total = off;
+  l.out = cv.take(r * 4 * sizeof(float));          // attn [R] | depth [R] | acc [R] | (spare)
+  l.d_render = cv.take(r * sizeof(float));
+  l.tv_grad = cv.take((size_t)g->X * g->Y * g->Z * sizeof(float));
+  l.tv_scratch = cv.take(tv_scratch_bytes(g->X, g->Y, g->Z, 1));
+  l.l1_scratch = cv.take(attn_l1_scratch_bytes());
+  l.total = cv.off;
   return l;
 }
 }  // namespace
@@ -1012,16 +1054,15 @@ int voxe_attn_refine_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, co
   const RefineLayout l = refine_layout(grid, R);
   if (!scratch || scratch_bytes < l.total) return VOXE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  char* sc = (char*)scratch;
-  float* attn = rs->attn_render ? rs->attn_render : (float*)(sc + l.out);
-  float *depth = (float*)(sc + l.out) + R, *acc = depth + R;
-  float* d_render = (float*)(sc + l.d_render);
-  float* tv_grad = (float*)(sc + l.tv_grad);
+  float* attn = rs->attn_render ? rs->attn_render : at<float>(scratch, l.out);
+  float *depth = at<float>(scratch, l.out) + R, *acc = depth + R;
+  float* d_render = at<float>(scratch, l.d_render);
+  float* tv_grad = at<float>(scratch, l.tv_grad);
   VoxeRenderCfg rc = *cfg;
   rc.ray_state_valid = 0;
   int st = voxe_render_fwd(grid, &rc, rays_o, rays_d, R, nullptr, attn, depth, acc, nullptr, workspace, workspace_bytes, stream);
   if (st) return st;
-  launch_attn_masked_l1(attn, rs->attn_map, R, d_render, rs->losses, sc + l.l1_scratch, s);
+  launch_attn_masked_l1(attn, rs->attn_map, R, d_render, rs->losses, at<char>(scratch, l.l1_scratch), s);
   rc.ray_state_valid = 1;
   rc.reuse_packed_grid = 1;
   int32_t layout = VOXE_GRAD_ANY;
@@ -1033,7 +1074,7 @@ int voxe_attn_refine_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, co
   const float* extra = nullptr;
   if (rs->tv_weight != 0.0f || (rs->losses && rs->tv_loss_always)) {
     launch_tv(grid->features, grid->X, grid->Y, grid->Z, 1, rs->tv_weight, rs->losses ? rs->losses + 1 : nullptr,
-              rs->tv_weight != 0.0f ? tv_grad : nullptr, 0, sc + l.tv_scratch, s);
+              rs->tv_weight != 0.0f ? tv_grad : nullptr, 0, at<char>(scratch, l.tv_scratch), s);
     if (rs->tv_weight != 0.0f) extra = tv_grad;
   }
   return voxe_grid_adam_step(grid, layout, 0, grid->X, nullptr, extra, nullptr, nullptr, rs->exp_avg, rs->exp_avg_sq, rs->lr,
@@ -1048,27 +1089,19 @@ int voxe_clock_probe(int32_t spin, double* shader_hz, void* stream) {
 
 int voxe_region_debug_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, int64_t out[17]) {
   if (!out) return VOXE_ERR_NULL_POINTER;
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, nullptr, &p);
   if (st) return st;
-  const WsLayout l = ws_layout(grid, cfg, R);
-  if (!l.region) return VOXE_ERR_UNSUPPORTED;   // (grid, cfg, R) does not take the space-binned route
+  if (!p.region) return VOXE_ERR_UNSUPPORTED;   // (grid, cfg, R) does not take the space-binned route
   long long t[16];
   region_debug_layout(grid->X, grid->Y, grid->Z, R, cfg->num_samples, t);
-  out[0] = (int64_t)l.region_off;
+  out[0] = (int64_t)p.l.region_off;
   for (int i = 0; i < 16; ++i) out[1 + i] = t[i];
   return VOXE_OK;
 }
 
-size_t voxe_workspace_grad_offset(const VoxeGridDesc* grid) {
-  if (!grid || grid->X <= 0 || grid->Y <= 0 || grid->Z <= 0 || grid->F <= 0) return 0;
-  return ws_layout(grid, nullptr, 0).grad_off;
-}
-size_t voxe_workspace_grad_bytes(const VoxeGridDesc* grid) {
-  if (!grid || grid->X <= 0 || grid->Y <= 0 || grid->Z <= 0 || grid->F <= 0) return 0;
-  const WsLayout l = ws_layout(grid, nullptr, 0);
-  return l.state_off - l.grad_off;
-}
+size_t voxe_workspace_grad_offset(const VoxeGridDesc* grid) { return grid_layout(grid).grad_off; }
+size_t voxe_workspace_grad_bytes(const VoxeGridDesc* grid) { return grid_layout(grid).grad_bytes(); }
 
 int voxe_grid_adam_step(const VoxeGridDesc* grid, int32_t grad_layout, int32_t x_begin, int32_t x_end,
                         const float* extra_d_densities,
@@ -1085,7 +1118,7 @@ int voxe_grid_adam_step(const VoxeGridDesc* grid, int32_t grad_layout, int32_t x
     return VOXE_ERR_NULL_POINTER;
   if (grad_layout != VOXE_GRAD_LINEAR && grad_layout != VOXE_GRAD_BRICKED && grad_layout != VOXE_GRAD_ANY)
     return VOXE_ERR_UNSUPPORTED;
-  const WsLayout l = ws_layout(grid, nullptr, 0);
+  const WsLayout l = grid_layout(grid);
   if (!workspace || workspace_bytes < l.state_off) return VOXE_ERR_WORKSPACE;
   DclTerm dcl;
   const long long nvox_all = (long long)grid->X * grid->Y * grid->Z;
@@ -1135,10 +1168,10 @@ int voxe_grid_adam_step(const VoxeGridDesc* grid, int32_t grad_layout, int32_t x
   forget_stamp(workspace);
   forget_stamps_of(grid->densities);   // (sibling workspaces / a grad_workspace's owner rendered the same tensors)
   forget_stamps_of(grid->features);
-  if (!launch_grid_adam(grid, grad_layout == VOXE_GRAD_BRICKED, x_begin, x_end, (float*)((char*)workspace + l.grad_off),
+  if (!launch_grid_adam(grid, grad_layout == VOXE_GRAD_BRICKED, x_begin, x_end, at<float>(workspace, l.grad_off),
                         extra_d_densities, extra_d_features, exp_avg_d, exp_avg_sq_d, exp_avg_f, exp_avg_sq_f, lr, beta1,
                         beta2, eps, step, step_features > 0 ? step_features : step,
-                        (float*)((char*)workspace + l.packed_off), (hipStream_t)stream, dcl))
+                        at<float>(workspace, l.packed_off), (hipStream_t)stream, dcl))
     return VOXE_ERR_UNSUPPORTED;
   return finish();
 }
@@ -1147,47 +1180,19 @@ int voxe_sample_probe(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
                       const float* rays_d, int64_t R, const float* jitter, int32_t* idx,
                       uint8_t* inside, float* zvals, float* sigma, float* rad, void* workspace,
                       size_t workspace_bytes, void* stream) {
-  Variant v;
-  const int st = validate(grid, cfg, R, &v);
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, jitter, &p);
   if (st) return st;
   if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
-  const WsLayout l = ws_layout(grid, cfg, R);
-  if (!workspace || workspace_bytes < l.fwd_total) return VOXE_ERR_WORKSPACE;
+  if (!workspace || workspace_bytes < p.l.fwd_total) return VOXE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  float* packed = (float*)((char*)workspace + l.packed_off);
+  float* packed = at<float>(workspace, p.l.packed_off);
   if (!cfg->reuse_packed_grid) launch_pack_any(grid, packed, s);
   if (R == 0) return finish();
-  DevGrid dg; HostCfg dc;
-  make_dev(grid, cfg, R, v, &dg, &dc);
   ProbeArgs a{packed, rays_o, rays_d, jitter, idx, inside, zvals, sigma, rad};
-  launch_probe(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
+  launch_probe(p.dg, p.dc, cfg->sh_degree, cfg->render_diffuse, a, s);
   return finish();
 }
-
-namespace {
-int validate_grid_only(const VoxeGridDesc* g) {
-  if (!g || !g->densities || !g->features) return VOXE_ERR_NULL_POINTER;
-  if (g->X <= 0 || g->Y <= 0 || g->Z <= 0 || g->F <= 0) return VOXE_ERR_BAD_SHAPE;
-  const int C = g->F + 1;
-  if (C != 2 && C != 4 && C != 13 && C != 28 && C != 49) return VOXE_ERR_BAD_SHAPE;
-  if ((long long)g->X * g->Y * g->Z * C >= (1LL << 31)) return VOXE_ERR_BAD_SHAPE;
-  if ((long long)g->X * g->Y >= (1LL << 24) || (long long)g->Y * g->Z >= (1LL << 24) || g->Z >= (1 << 24)) return VOXE_ERR_BAD_SHAPE;
-  if (g->density_pre_act != VOXE_ACT_IDENTITY && g->density_pre_act != VOXE_ACT_ABS) return VOXE_ERR_UNSUPPORTED;
-  if (g->density_post_act != VOXE_ACT_IDENTITY && g->density_post_act != VOXE_ACT_RELU &&
-      g->density_post_act != VOXE_ACT_SOFTPLUS)
-    return VOXE_ERR_UNSUPPORTED;
-  return VOXE_OK;
-}
-void grid_to_dev(const VoxeGridDesc* g, DevGrid* dg) {
-  dg->X = g->X; dg->Y = g->Y; dg->Z = g->Z;
-  for (int a = 0; a < 3; ++a) {
-    dg->lo[a] = g->aabb_lo[a]; dg->hi[a] = g->aabb_hi[a];
-    dg->scale[a] = g->norm_scale[a]; dg->bias[a] = g->norm_bias[a];
-  }
-  dg->density_scale = g->density_scale;
-  dg->pre_act = g->density_pre_act; dg->post_act = g->density_post_act;
-}
-}  // namespace
 
 int voxe_query_fwd(const VoxeGridDesc* grid, const float* points, int64_t N, float* out,
                    int32_t reuse_packed_grid, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1195,10 +1200,10 @@ int voxe_query_fwd(const VoxeGridDesc* grid, const float* points, int64_t N, flo
   if (st) return st;
   if (N < 0) return VOXE_ERR_BAD_SHAPE;
   if (N > 0 && (!points || !out)) return VOXE_ERR_NULL_POINTER;
-  const WsLayout l = ws_layout(grid, nullptr, 0);
+  const WsLayout l = grid_layout(grid);
   if (!workspace || workspace_bytes < l.fwd_total) return VOXE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  float* packed = (float*)((char*)workspace + l.packed_off);
+  float* packed = at<float>(workspace, l.packed_off);
   if (!reuse_packed_grid) launch_pack_any(grid, packed, s);
   if (N == 0) return finish();
   DevGrid dg;
@@ -1215,13 +1220,13 @@ int voxe_query_bwd(const VoxeGridDesc* grid, const float* points, int64_t N, con
   if (N < 0) return VOXE_ERR_BAD_SHAPE;
   if (N > 0 && (!points || !d_out)) return VOXE_ERR_NULL_POINTER;
   if (!d_densities && !d_features) return VOXE_OK;
-  const WsLayout l = ws_layout(grid, nullptr, 0);
+  const WsLayout l = grid_layout(grid);
   if (!workspace || workspace_bytes < l.total) return VOXE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  float* packed = (float*)((char*)workspace + l.packed_off);
-  float* gpacked = (float*)((char*)workspace + l.grad_off);
+  float* packed = at<float>(workspace, l.packed_off);
+  float* gpacked = at<float>(workspace, l.grad_off);
   if (!reuse_packed_grid) launch_pack_any(grid, packed, s);
-  if (hipMemsetAsync(gpacked, 0, l.state_off - l.grad_off, s) != hipSuccess) return VOXE_ERR_LAUNCH;
+  if (hipMemsetAsync(gpacked, 0, l.grad_bytes(), s) != hipSuccess) return VOXE_ERR_LAUNCH;
   if (N > 0) {
     DevGrid dg;
     grid_to_dev(grid, &dg);
@@ -1358,10 +1363,7 @@ int validate_mesh(const VoxeGridDesc* g, float level, void* scratch, size_t scra
   if (!g || !g->densities) return VOXE_ERR_NULL_POINTER;
   if (!mesh_dims_ok(g->X, g->Y, g->Z)) return VOXE_ERR_BAD_SHAPE;
   if (g->feature_kind != VOXE_FEAT_SH && g->feature_kind != VOXE_FEAT_ATTN) return VOXE_ERR_UNSUPPORTED;
-  if (g->density_pre_act != VOXE_ACT_IDENTITY && g->density_pre_act != VOXE_ACT_ABS) return VOXE_ERR_UNSUPPORTED;
-  if (g->density_post_act != VOXE_ACT_IDENTITY && g->density_post_act != VOXE_ACT_RELU &&
-      g->density_post_act != VOXE_ACT_SOFTPLUS)
-    return VOXE_ERR_UNSUPPORTED;
+  if (const int st = grid_acts_status(g)) return st;
   if (!mesh_iso_value(g->density_post_act, level, L)) return VOXE_ERR_BAD_SHAPE;
   if (!scratch || scratch_bytes < mesh_scratch_bytes(g->X, g->Y, g->Z)) return VOXE_ERR_WORKSPACE;
   return VOXE_OK;
@@ -1398,14 +1400,8 @@ int voxe_mesh_emit(const VoxeGridDesc* grid, float level, const uint8_t* mask, f
 // the grid checks of validate_grid_only() for a call that reads `densities` only (features / F / feature_kind are ignored)
 static int validate_normals_grid(const VoxeGridDesc* g) {
   if (!g || !g->densities) return VOXE_ERR_NULL_POINTER;
-  if (g->X <= 0 || g->Y <= 0 || g->Z <= 0) return VOXE_ERR_BAD_SHAPE;
-  if ((long long)g->X * g->Y * g->Z >= (1LL << 31)) return VOXE_ERR_BAD_SHAPE;
-  if ((long long)g->X * g->Y >= (1LL << 24) || (long long)g->Y * g->Z >= (1LL << 24) || g->Z >= (1 << 24)) return VOXE_ERR_BAD_SHAPE;
-  if (g->density_pre_act != VOXE_ACT_IDENTITY && g->density_pre_act != VOXE_ACT_ABS) return VOXE_ERR_UNSUPPORTED;
-  if (g->density_post_act != VOXE_ACT_IDENTITY && g->density_post_act != VOXE_ACT_RELU &&
-      g->density_post_act != VOXE_ACT_SOFTPLUS)
-    return VOXE_ERR_UNSUPPORTED;
-  return VOXE_OK;
+  if (const int st = grid_extent_status(g, 1)) return st;
+  return grid_acts_status(g);
 }
 
 // DevCfg of a call that marches the forward's samples without rendering (normals, visibility): the sampling fields make_dev()
