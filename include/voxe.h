@@ -743,6 +743,58 @@ int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
                             void* scratch, size_t scratch_bytes, void* stream);
 int voxe_distortion_debug_lanes(int32_t lanes);
 
+/* ---- rigid transform, re-gridding and composition of voxel grids (not in the reference) ----------------------
+ * An added symbol is backward compatible: VOXE_ABI_VERSION stays 13.  No voxe_cpu_ twin; the float64 restatement is
+ * tests/transform_ref.py.
+ *
+ * voxe_grid_resample: every voxel of a DESTINATION grid [X2,Y2,Z2] samples a SOURCE grid [X,Y,Z] trilinearly at
+ *       u = A i + b        i = the destination voxel's integer index, u = continuous source index (voxel centres at integers),
+ *   evaluated in float32 without FMA as u_a = ((A_a0 i_x + A_a1 i_y) + A_a2 i_z) + b_a.  For the scene-frame map
+ *   p' = s R p + t (R orthogonal, det +-1, s > 0), source low corner lo_s and voxel edges v_s, destination lo_d and v_d:
+ *       A = diag(1/v_s) (R^T / s) diag(v_d),     b = diag(1/v_s) ((R^T / s)(lo_d + v_d/2 - t) - lo_s) - 1/2
+ *   (computed by the caller in float64, cast to float32).  i0 = floor(u), f = u - i0, per-axis weights (1 - f, f), corner
+ *   weights t_c = (wx wy) wz summed corners ascending (x in bit 0) as in the renderer's gather.
+ *   Density: each corner is read through density_pre_act (IDENTITY | ABS, no density scale); the interpolated pre-activated
+ *   value is stored as the new RAW density (ABS is idempotent on it).  A corner outside the source lattice contributes
+ *   density_fill to the density and 0 to every feature channel; a voxel whose 8 corners are all outside gets exactly
+ *   (density_fill, 0...) and loads nothing.
+ *   Features: sh_degree 0..3 -- C must be 3 (deg+1)^2, laid out [colour channel][coefficient]; per channel and band l the
+ *   interpolated coefficients are rotated, c'_l = M_l c_l, M_l the row-major (2l+1)^2 block of sh_rot at offset 0 / 1 / 10 / 35,
+ *   defined by b_l(R^T v)^T = b_l(v)^T M_l for every unit v in the renderer's own basis (band 0 is the identity and is not
+ *   multiplied).  sh_degree -1 -- C plain channels (1..64), no rotation (the attention grid).
+ *   Modes: VOXE_RESAMPLE_REPLACE writes every destination voxel.  VOXE_RESAMPLE_UNION (CSG union of the two pre-activation
+ *   fields, in place on the destination): a sample is VALID iff every corner with non-zero weight lies in the source lattice; a
+ *   valid sample whose density is strictly greater than pre_act(destination raw density) replaces the destination's density and
+ *   all its features; every other destination voxel is not written.  Source and destination must not alias.
+ *   taken (uint8 [X2,Y2,Z2] or NULL): UNION -- 1 where the source replaced the destination; REPLACE -- 1 where at least one
+ *   corner with non-zero weight lies in the lattice.
+ *   Either the density pair or the feature pair may be NULL in REPLACE (both NULL: VOXE_ERR_NULL_POINTER, as is one half of a
+ *   pair); UNION needs the density pair.  Shapes: all dims > 0, both voxel counts times (C + 1) < 2^31, X*Y, Y*Z, Z < 2^24 on
+ *   either grid, else VOXE_ERR_BAD_SHAPE; an unknown mode / pre-activation / sh_degree: VOXE_ERR_UNSUPPORTED.
+ *   Uniform scale is geometric only: raw values are not compensated, so the optical depth through the object scales by s.
+ *   No gradient is defined.  No workspace, forward record or voxe_recon_prefetch hint is touched; caller's stream, no host
+ *   synchronisation, no allocation.                                                                                         */
+typedef enum VoxeResampleMode {
+  VOXE_RESAMPLE_REPLACE = 0,
+  VOXE_RESAMPLE_UNION = 1
+} VoxeResampleMode;
+
+typedef struct VoxeResample {
+  float A[9];               /* row-major 3x3                                                       */
+  float b[3];
+  float sh_rot[84];         /* M_0 (1) | M_1 (9) | M_2 (25) | M_3 (49), each row-major             */
+  int32_t sh_degree;        /* -1: plain channels; 0..3: SH, C = 3 (deg+1)^2                       */
+  int32_t density_pre_act;  /* VoxeAct: IDENTITY | ABS                                             */
+  int32_t mode;             /* VoxeResampleMode                                                    */
+  float density_fill;       /* what a corner outside the source lattice adds to the density        */
+} VoxeResample;
+
+int voxe_grid_resample(const float* src_densities /* [X,Y,Z,1] or NULL */, const float* src_features /* [X,Y,Z,C] or NULL */,
+                       int32_t X, int32_t Y, int32_t Z, int32_t C,
+                       float* dst_densities /* [X2,Y2,Z2,1] or NULL */, float* dst_features /* [X2,Y2,Z2,C] or NULL */,
+                       int32_t X2, int32_t Y2, int32_t Z2,
+                       const VoxeResample* xf, uint8_t* taken /* [X2,Y2,Z2] or NULL */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.

@@ -12,7 +12,7 @@ out = subprocess.run([b.hipcc(), *b.FLAGS, "-I", b.INCLUDE, "-c", src, "--cuda-d
 names = subprocess.run(["c++filt"], input="\n".join(re.findall(r"Function Name: (\S+)", out)),
                        capture_output=True, text=True).stdout.splitlines()
 for blk, name in zip(re.split(r"remark: .*?Function Name: ", out)[1:], names):
-    name = name.split("(")[0].replace("voxe::", "")
+    name = name.replace("(anonymous namespace)::", "").split("(")[0].replace("voxe::", "")
     if filt and not all(f in name for f in filt):
         continue
     g = lambda k: re.search(re.escape(k) + r": (\d+)", blk).group(1)

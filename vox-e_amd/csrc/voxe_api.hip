@@ -1508,4 +1508,32 @@ int voxe_distortion_debug_lanes(int32_t lanes) {
   return VOXE_OK;
 }
 
+// ---- rigid transform / re-gridding / composition ------------------------------------------------------------
+static bool resample_dims_ok(int32_t X, int32_t Y, int32_t Z, int32_t C) {
+  if (X <= 0 || Y <= 0 || Z <= 0) return false;
+  if ((long long)X * Y * Z * (C + 1) >= (1LL << 31)) return false;
+  return (long long)X * Y < (1LL << 24) && (long long)Y * Z < (1LL << 24) && Z < (1 << 24);   // 24-bit index multiplies
+}
+
+int voxe_grid_resample(const float* src_densities, const float* src_features, int32_t X, int32_t Y, int32_t Z, int32_t C,
+                       float* dst_densities, float* dst_features, int32_t X2, int32_t Y2, int32_t Z2, const VoxeResample* xf,
+                       uint8_t* taken, void* stream) {
+  if (!xf) return VOXE_ERR_NULL_POINTER;
+  if ((src_densities == nullptr) != (dst_densities == nullptr) || (src_features == nullptr) != (dst_features == nullptr))
+    return VOXE_ERR_NULL_POINTER;
+  if (!src_densities && !src_features) return VOXE_ERR_NULL_POINTER;
+  if (xf->mode != VOXE_RESAMPLE_REPLACE && xf->mode != VOXE_RESAMPLE_UNION) return VOXE_ERR_UNSUPPORTED;
+  if (xf->mode == VOXE_RESAMPLE_UNION && !src_densities) return VOXE_ERR_NULL_POINTER;
+  if (xf->density_pre_act != VOXE_ACT_IDENTITY && xf->density_pre_act != VOXE_ACT_ABS) return VOXE_ERR_UNSUPPORTED;
+  if (xf->sh_degree < -1 || xf->sh_degree > 3) return VOXE_ERR_UNSUPPORTED;
+  const int32_t Cf = src_features ? C : 1;   // (C is not read without features)
+  if (src_features) {
+    if (xf->sh_degree < 0 ? (C < 1 || C > 64) : C != 3 * (xf->sh_degree + 1) * (xf->sh_degree + 1)) return VOXE_ERR_BAD_SHAPE;
+  }
+  if (!resample_dims_ok(X, Y, Z, Cf) || !resample_dims_ok(X2, Y2, Z2, Cf)) return VOXE_ERR_BAD_SHAPE;
+  launch_grid_resample(src_densities, src_features, X, Y, Z, Cf, dst_densities, dst_features, X2, Y2, Z2, *xf, taken,
+                       (hipStream_t)stream);
+  return finish();
+}
+
 }  // extern "C"

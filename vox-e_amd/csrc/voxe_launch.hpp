@@ -223,4 +223,8 @@ void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, con
                        const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
                        hipStream_t st);
 
+// voxe_transform.hip: rigid transform / re-gridding / composition of grids; arguments validated by the API
+void launch_grid_resample(const float* src_dens, const float* src_feat, int X, int Y, int Z, int C, float* dst_dens, float* dst_feat,
+                          int X2, int Y2, int Z2, const VoxeResample& xf, uint8_t* taken, hipStream_t st);
+
 }  // namespace voxe

@@ -142,6 +142,17 @@ class VoxeAttnRefineStep(C.Structure):
     ]
 
 
+class VoxeResample(C.Structure):
+    """index map, SH rotation blocks and mode of voxe_grid_resample (include/voxe.h)"""
+    _fields_ = [
+        ("A", C.c_float * 9), ("b", C.c_float * 3), ("sh_rot", C.c_float * 84),
+        ("sh_degree", C.c_int32), ("density_pre_act", C.c_int32), ("mode", C.c_int32), ("density_fill", C.c_float),
+    ]
+
+
+RESAMPLE_REPLACE, RESAMPLE_UNION = 0, 1
+SH_ROT_OFFSETS = (0, 1, 10, 35, 84)   # M_l starts at SH_ROT_OFFSETS[l]
+
 _P = C.c_void_p
 _GD = C.POINTER(VoxeGridDesc)
 _RC = C.POINTER(VoxeRenderCfg)
@@ -227,6 +238,9 @@ HIP_ONLY = {
     "distortion_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "distortion_fwd_bwd": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, C.c_float, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
     "distortion_debug_lanes": (C.c_int, [C.c_int32]),
+    # rigid transform / re-gridding / composition of grids (additive, still ABI v13)
+    "grid_resample": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                C.POINTER(VoxeResample), _P, _P]),
 }
 
 CPU_ONLY = {

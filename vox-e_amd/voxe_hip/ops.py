@@ -1300,6 +1300,93 @@ def visibility_mask(vis: torch.Tensor, threshold: float, dilate: int = 0) -> tor
 
 
 # ------------------------------------------------------------------------------------------------
+# rigid transform / re-gridding / composition of grids: no workspace, not differentiable
+# ------------------------------------------------------------------------------------------------
+def make_resample(A, b, sh_rot=None, sh_degree: int = -1, density_pre_act: int = abi.ACT_IDENTITY, density_fill: float = 0.0,
+                  mode: int = abi.RESAMPLE_REPLACE) -> abi.VoxeResample:
+    """VoxeResample from host values: A (3x3) and b (3) in any float type (cast to float32 here), sh_rot the list of band
+    blocks M_0..M_deg ((2l+1) x (2l+1) each, as thre3d_reprs.transform.sh_rotation_matrices returns them) or None."""
+    xf = abi.VoxeResample()
+    flat = [float(v) for row in A for v in row]
+    if len(flat) != 9 or len(b) != 3:
+        raise VoxeError("grid_resample: A must be 3x3 and b of length 3")
+    xf.A[:] = flat
+    xf.b[:] = [float(v) for v in b]
+    xf.sh_rot[0] = 1.0
+    for l in range(1, 4):   # identity blocks where none is given
+        for j in range(2 * l + 1):
+            xf.sh_rot[abi.SH_ROT_OFFSETS[l] + j * (2 * l + 2)] = 1.0
+    if sh_degree >= 0:
+        if sh_rot is None or len(sh_rot) < sh_degree + 1:
+            raise VoxeError(f"grid_resample: sh_degree {sh_degree} needs the rotation blocks M_0..M_{sh_degree}")
+        for l in range(1, sh_degree + 1):   # (band 0 is the identity by definition)
+            n = 2 * l + 1
+            vals = [float(v) for row in sh_rot[l] for v in row]
+            if len(vals) != n * n:
+                raise VoxeError(f"grid_resample: M_{l} must be {n}x{n}")
+            xf.sh_rot[abi.SH_ROT_OFFSETS[l]:abi.SH_ROT_OFFSETS[l + 1]] = vals
+    xf.sh_degree, xf.density_pre_act, xf.mode, xf.density_fill = int(sh_degree), int(density_pre_act), int(mode), float(density_fill)
+    return xf
+
+
+@torch.no_grad()
+def grid_resample(src_densities: Optional[torch.Tensor], src_features: Optional[torch.Tensor], xf: abi.VoxeResample,
+                  dst_dims: Optional[Sequence[int]] = None, dst_densities: Optional[torch.Tensor] = None,
+                  dst_features: Optional[torch.Tensor] = None, want_taken: bool = False):
+    """voxe_grid_resample (include/voxe.h): sample the source grid ([X,Y,Z,1] densities and / or [X,Y,Z,C] features) at
+    u = A i + b for every voxel i of the destination.  REPLACE: new float32 tensors of `dst_dims` are returned.  UNION:
+    `dst_densities` (and `dst_features` when the source has features) are updated in place -- contiguous float32 tensors that do
+    not alias the source.  Returns (densities, features, taken): taken is a uint8 [X2,Y2,Z2] tensor when want_taken, else
+    None."""
+    union = xf.mode == abi.RESAMPLE_UNION
+    srcs = [t for t in (src_densities, src_features) if t is not None]
+    if not srcs:
+        raise VoxeError("grid_resample: neither densities nor features given")
+    for t in srcs:
+        require_device(t, "grid_resample")
+        if t.dim() != 4:
+            raise VoxeError(f"grid_resample: source tensors must be [X,Y,Z,C]; got {tuple(t.shape)}")
+    device = srcs[0].device
+    X, Y, Z = (int(v) for v in srcs[0].shape[:3])
+    if any(tuple(t.shape[:3]) != (X, Y, Z) or t.device != device for t in srcs):
+        raise VoxeError("grid_resample: source densities and features must share dims and device")
+    if src_densities is not None and src_densities.shape[-1] != 1:
+        raise VoxeError(f"grid_resample: densities must be [X,Y,Z,1]; got {tuple(src_densities.shape)}")
+    Cn = int(src_features.shape[-1]) if src_features is not None else 1
+    sd = None if src_densities is None else f32c(src_densities.detach())
+    sf = None if src_features is None else f32c(src_features.detach())
+    ensure_gfx950(device)
+    with torch.cuda.device(device):
+        if union:
+            if dst_densities is None or sd is None or (sf is not None and dst_features is None):
+                raise VoxeError("grid_resample: UNION runs in place on dst_densities (and dst_features) and needs the densities")
+            dd, df = dst_densities, (dst_features if sf is not None else None)
+            dims2 = tuple(int(v) for v in dd.shape[:3])
+            for name, t, ch, s_ in (("dst_densities", dd, 1, sd), ("dst_features", df, Cn, sf)):
+                if t is None:
+                    continue
+                require_device(t, f"grid_resample ({name})")
+                if (t.dtype != torch.float32 or not t.is_contiguous() or t.device != device or t.dim() != 4
+                        or tuple(t.shape) != (*dims2, ch)):
+                    raise VoxeError(f"grid_resample: {name} must be a contiguous float32 {(*dims2, ch)} tensor on the source's "
+                                    f"device; got {tuple(t.shape)} {t.dtype}")
+                if t.untyped_storage().data_ptr() == s_.untyped_storage().data_ptr():
+                    raise VoxeError("grid_resample: source and destination must not alias")
+        else:
+            if dst_dims is None or dst_densities is not None or dst_features is not None:
+                raise VoxeError("grid_resample: REPLACE allocates its outputs: pass dst_dims and no destination tensors")
+            dims2 = tuple(int(v) for v in dst_dims)
+            if len(dims2) != 3 or min(dims2) <= 0:
+                raise VoxeError(f"grid_resample: dst_dims must be three positive ints; got {dims2}")
+            dd = None if sd is None else torch.empty((*dims2, 1), dtype=torch.float32, device=device)
+            df = None if sf is None else torch.empty((*dims2, Cn), dtype=torch.float32, device=device)
+        taken = torch.empty(dims2, dtype=torch.uint8, device=device) if want_taken else None
+        check(lib().voxe_grid_resample(ptr(sd), ptr(sf), X, Y, Z, Cn, ptr(dd), ptr(df), *dims2, C.byref(xf), ptr(taken),
+                                       stream_ptr(device)), "voxe_grid_resample")
+    return dd, df, taken
+
+
+# ------------------------------------------------------------------------------------------------
 # distortion loss on rays (DESIGN.md section 4 "Distortion"): reads the raw densities only, no workspace; differentiable w.r.t.
 # the densities
 # ------------------------------------------------------------------------------------------------
