@@ -136,7 +136,10 @@ typedef struct VoxeRenderCfg {
                                  samples exactly like the reference; with term_eps > 0 the BACKWARD stops marching a ray once
                                  its transmittance is below term_eps: samples behind that point get no gradient (their
                                  contributions scale with T < term_eps), the samples in front keep their EXACT gradient
-                                 (the suffix sums come from the full forward).  -20 % backward time on surface-like scenes. */
+                                 (the suffix sums come from the full forward).  -20 % backward time on surface-like scenes.
+                                 The rule: sample k receives its exact gradient iff the transmittance IN FRONT of it, T_k (the
+                                 exclusive product, T_0 = 1), is >= term_eps.  Meaningful for 0 < term_eps < 1; at >= 1 the
+                                 kernels still differentiate sample 0 of the first segment: neither tested nor promised.     */
   uint64_t seed, rng_offset;  /* in-kernel jitter stream                                          */
   int32_t reuse_packed_grid;  /* 1: workspace already holds this grid packed by a previous call
                                  on the same workspace (grid values unchanged)                    */

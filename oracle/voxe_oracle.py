@@ -163,8 +163,20 @@ def render_fwd(grid: Grid, cfg: abi.VoxeRenderCfg, rays_o, rays_d, jitter=None):
     return {"colour": colour, "depth": depth, "acc": acc, "disparity": disp}
 
 
+def _render_bwd_cut():
+    """voxe_cpu_render_bwd_cut: the oracle's own test hook (declared in voxe_cpu.c, not in include/voxe.h, so abi.py does not
+    know it): voxe_cpu_render_bwd's arguments with `const int32_t* cut` in front of the upstream gradients."""
+    fn = lib().voxe_cpu_render_bwd_cut
+    if fn.argtypes is None:
+        bwd = lib().voxe_cpu_render_bwd
+        fn.restype, fn.argtypes = bwd.restype, list(bwd.argtypes[:6]) + [C.c_void_p] + list(bwd.argtypes[6:])
+    return fn
+
+
 def render_bwd(grid: Grid, cfg: abi.VoxeRenderCfg, rays_o, rays_d, d_colour, d_depth=None, d_acc=None,
-               jitter=None, want_densities=True, want_features=True):
+               jitter=None, want_densities=True, want_features=True, cut=None):
+    """cut: int32 [R] or None -- sample k of ray r deposits no gradient when k >= cut[r] (the truncated gradient of
+    VoxeRenderCfg::term_eps with the threshold decision left to the caller; cfg.term_eps itself is not read)"""
     rays_o, rays_d, d_colour = _f32(rays_o), _f32(rays_d), _f32(d_colour)
     R = rays_o.shape[0]
     jitter = None if jitter is None else _f32(jitter)
@@ -173,12 +185,17 @@ def render_bwd(grid: Grid, cfg: abi.VoxeRenderCfg, rays_o, rays_d, d_colour, d_d
     gd = np.zeros_like(grid.densities) if want_densities else None
     gf = np.zeros_like(grid.features) if want_features else None
     g = grid.desc()
-    _check(
-        lib().voxe_cpu_render_bwd(C.byref(g), C.byref(cfg), rays_o.ctypes.data, rays_d.ctypes.data, R,
-                                  _ptr(jitter), d_colour.ctypes.data, _ptr(d_depth), _ptr(d_acc),
-                                  _ptr(gd), _ptr(gf), 0),
-        "render_bwd",
-    )
+    if cut is None:
+        st = lib().voxe_cpu_render_bwd(C.byref(g), C.byref(cfg), rays_o.ctypes.data, rays_d.ctypes.data, R,
+                                       _ptr(jitter), d_colour.ctypes.data, _ptr(d_depth), _ptr(d_acc),
+                                       _ptr(gd), _ptr(gf), 0)
+    else:
+        cut = np.ascontiguousarray(cut, dtype=np.int32)
+        assert cut.shape == (R,)
+        st = _render_bwd_cut()(C.byref(g), C.byref(cfg), rays_o.ctypes.data, rays_d.ctypes.data, R,
+                                           _ptr(jitter), cut.ctypes.data, d_colour.ctypes.data, _ptr(d_depth),
+                                           _ptr(d_acc), _ptr(gd), _ptr(gf), 0)
+    _check(st, "render_bwd")
     return gd, gf
 
 
