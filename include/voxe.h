@@ -746,6 +746,62 @@ int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
                             void* scratch, size_t scratch_bytes, void* stream);
 int voxe_distortion_debug_lanes(int32_t lanes);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ray and camera-pose gradients (additive; still ABI v13), DESIGN.md section 4.13 "Ray gradients".  No voxe_cpu_ twin; the
+ * float64 restatement is tests/ray_grad_ref.py.
+ *
+ * voxe_render_bwd_rays: the gradient of a render with respect to rays_o / rays_d, what the reference chain (sample ->
+ *   grid_sample -> SH -> accumulate) delivers to the rays under autograd.  The samples z_k, the inside test, sigma_k, delta_k =
+ *   dl_k |d| (last dl = 1e10) and w_k = T_k alpha_k are those of voxe_render_fwd for the same rays, cfg and jitter / (seed,
+ *   rng_offset).  Upstream gradients d_colour [R,3], d_depth [R], d_acc [R]; each may be NULL (= 0).  Per ray:
+ *       q_k   = d_colour . rad_k + d_depth z_k + d_acc - (white_bkgd ? sum_c d_colour_c : 0)
+ *       E_k   = q_k (T_k - w_k) - sum_{i>k} w_i q_i
+ *       dL/dsigma_k = delta_k E_k,    dL/ddelta_k = sigma_k E_k
+ *       dL/dp_k = dL/dsigma_k post'(v_k) grad v(p_k) + w_k sum_c d_colour_c rad_kc (1 - rad_kc) sum_j B_j(v^) grad f_cj(p_k)
+ *       d_rays_o = sum_k dL/dp_k
+ *       d_rays_d = sum_k z_k dL/dp_k + (sum_k dL/ddelta_k dl_k) d/|d| + Jn^T (dB/dv^)^T m
+ *       m_j = sum_k w_k sum_c d_colour_c rad_kc (1 - rad_kc) f_cj(p_k),   Jn = (I - v^ v^T) / |d|,   v^ = d / |d|
+ *   rad_kc = sigmoid(sum_j B_j f_cj); grad of a trilinear interpolant is its slope inside the cell floor(u) the forward used,
+ *   corners outside the grid counting as 0 for the slope too, in world units (N_a norm_scale_a / 2 per axis): the conventions
+ *   of voxe_render_normals, applied to the pre-activated, scaled density corners and to every feature channel.  With
+ *   render_diffuse or sh_degree 0 only B_0 exists and the last term of d_rays_d vanishes.  Samples that fail the strict AABB
+ *   test contribute nothing; post' follows voxe_render_bwd.
+ *   THE SAMPLE DEPTHS z_k ARE CONSTANTS.  Without aabb_clip that is exactly the reference's autograd (z depends on near / far /
+ *   jitter only).  With aabb_clip the per-ray bounds get a stop-gradient: the reference would differentiate the slab test,
+ *   this call does not (as voxe_distortion_fwd_bwd: no gradient flows to z).
+ *   cfg: term_eps, deterministic, reuse_packed_grid, ray_state_valid and dispatch are ignored; image_width / image_height only
+ *   choose the ray -> thread mapping (a ray's gradient depends on that ray and cfg only).  VOXE_FEAT_ATTN grids:
+ *   VOXE_ERR_UNSUPPORTED.  Validation, the limits on R and the voxel count and the error codes are those of voxe_render_normals,
+ *   plus F == 3 (sh_degree + 1)^2 (VOXE_ERR_BAD_SHAPE) and a non-NULL grid->features.  R == 0 or both outputs NULL: VOXE_OK with
+ *   no launch.  accumulate != 0: += into the outputs, else overwrite.
+ *   The RAW API tensors (grid->densities, grid->features) are read: no workspace; no forward record or voxe_recon_prefetch hint
+ *   is read or dropped.  Caller's stream, no host synchronisation, no allocation.  No atomics: a ray's 6 outputs are written by
+ *   one lane, so the result is bit-reproducible for a fixed lanes split.
+ *   voxe_render_bwd_rays_debug_lanes: test aid, as voxe_distortion_debug_lanes (0 | 1 | 2 | 4 | 8 lanes per ray for the calling
+ *   thread's later calls; anything else: VOXE_ERR_BAD_SHAPE).
+ *
+ * voxe_cast_rays_bwd: the chain rule of voxe_cast_rays / voxe_cast_rays_indexed into the poses [K,3,4] and the focal length:
+ *       d_trans = sum d_rays_o,   d_rot[a][b] = sum d_rays_d[a] dir_cam[b],   d_focal = sum d_rays_d . (R d dir_cam / d focal)
+ *   over the rays of each camera (dir_cam = ((x - W/2) / focal, -(y - H/2) / focal, -1)).  flat_index NULL: ray i is pixel i of
+ *   K whole images (B must be K * H * W).  Either d_rays_* may be NULL (= 0).  The sums are carried in double, 13 per camera in
+ *   `scratch` (voxe_cast_rays_bwd_scratch_bytes(K); too small: VOXE_ERR_WORKSPACE), then cast once into d_poses / d_focal
+ *   (device float[1] or NULL), added to them when accumulate != 0.  Cameras with no ray get an exact 0.  The rays of a wave that
+ *   share a camera are reduced in the wave before one lane adds; where lanes of different waves meet on a camera the adds are
+ *   double atomics, so the result is NOT promised bit-reproducible from run to run.                                          */
+int voxe_render_bwd_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                         const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                         const float* d_colour, const float* d_depth, const float* d_acc,
+                         float* d_rays_o /* [R,3] or NULL */, float* d_rays_d /* [R,3] or NULL */,
+                         int32_t accumulate, void* stream);
+int voxe_render_bwd_rays_debug_lanes(int32_t lanes);
+
+size_t voxe_cast_rays_bwd_scratch_bytes(int32_t K);
+int voxe_cast_rays_bwd(int32_t H, int32_t W, float focal, const float* poses /* [K,3,4] device */, int32_t K,
+                       const int64_t* flat_index /* [B] device or NULL: ray i is pixel i of K whole images */, int64_t B,
+                       const float* d_rays_o, const float* d_rays_d /* [B,3], either may be NULL */,
+                       float* d_poses /* [K,3,4] */, float* d_focal /* device float[1] or NULL */,
+                       int32_t accumulate, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- rigid transform, re-gridding and composition of voxel grids (not in the reference) ----------------------
  * An added symbol is backward compatible: VOXE_ABI_VERSION stays 13.  No voxe_cpu_ twin; the float64 restatement is
  * tests/transform_ref.py.

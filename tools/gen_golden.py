@@ -724,6 +724,63 @@ def g18_degenerate_rays():
     assert os.path.getsize(os.path.join(OUT, "degenerate_rays.npz")) < 512 * 1024
 
 
+def _ray_grad_case(vg, rays, S, white, jitter_seed=None, **cfg_kw):
+    """render_case's colour + depth + acc loss (generator seed 43), differentiated w.r.t. the rays by the reference's autograd"""
+    cfg = SHVoxGridRenderConfig(num_samples_per_ray=S, camera_bounds=BOUNDS, perturb_sampled_points=jitter_seed is not None,
+                                white_bkgd=white, **cfg_kw)
+    res = {}
+    if jitter_seed is not None:
+        torch.manual_seed(jitter_seed)
+        res["jitter"] = np_(torch.rand(len(rays.origins), S))
+        torch.manual_seed(jitter_seed)
+    o = rays.origins.detach().clone().requires_grad_(True)
+    d = rays.directions.detach().clone().requires_grad_(True)
+    out = render_sh_voxel_grid(vg, Rays(o, d), cfg)
+    acc = out.extra["accumulated_weight"]
+    g = torch.Generator().manual_seed(43)
+    g_col = torch.randn(out.colour.shape, generator=g)
+    g_dep = torch.randn(out.depth.shape, generator=g) * 0.25
+    g_acc = torch.randn(out.depth.shape, generator=g) * 0.25
+    loss = (out.colour * g_col).sum() + (out.depth * g_dep).sum() + (acc * g_acc).sum()
+    d_o, d_d = torch.autograd.grad(loss, (o, d))
+    res.update(colour=np_(out.colour), g_colour=np_(g_col), g_depth=np_(g_dep)[:, 0], g_acc=np_(g_acc)[:, 0],
+               d_rays_o=np_(d_o), d_rays_d=np_(d_d))
+    return res
+
+
+def _assert_stored_grid(vg, name, prefix):
+    with np.load(os.path.join(OUT, name)) as z:
+        assert np.array_equal(z[prefix + "densities"], np_(vg.densities)) and np.array_equal(z[prefix + "features"], np_(vg.features))
+
+
+def g19_ray_grads():
+    """The reference's own autograd gradients w.r.t. rays.origins / rays.directions (tests/test_ray_grad_*.py): SH-0 grids of the
+    three fields on the 16 x 16 camera 3 of 8 plus g5_g6_render's three extra rays (one misses, one starts inside), S = 64,
+    plain and jittered (seed 77); SH degree 1 - 3 on the 10 x 10 camera 1 of 8, S = 32, full and render_diffuse.  No
+    optimized_sampling case: there the reference differentiates the per-ray bounds, voxe_render_bwd_rays does not.
+    The grids are those of render_sh0.npz / render_shdeg.npz (same make_grid calls) and are read from there, not stored again."""
+    out = {"bounds": np.array(BOUNDS, dtype=np.float64)}
+    rays, _, _ = rays_for(16, 16, 3, 8)
+    extra_o = torch.tensor([[0.0, 0.0, 6.0], [0.1, -0.2, 0.3], [4.0, 4.0, 4.0]])
+    extra_d = torch.tensor([[1.0, 0.0, 0.0], [0.3, 0.5, -0.8], [-1.0, -1.0, -1.02]])
+    rays = Rays(torch.cat([rays.origins, extra_o]), torch.cat([rays.directions, extra_d]))
+    out["sh0_rays_o"], out["sh0_rays_d"] = np_(rays.origins), np_(rays.directions)
+    for kind in ("softplus", "relu", "abs"):
+        vg = make_grid((16, 16, 16), 3, 42, kind)
+        _assert_stored_grid(vg, "render_sh0.npz", kind + "_")
+        out.update({f"{kind}_plain_" + k: v for k, v in _ray_grad_case(vg, rays, 64, True).items()})
+        out.update({f"{kind}_jit_" + k: v for k, v in _ray_grad_case(vg, rays, 64, True, jitter_seed=77).items()})
+    rays, _, _ = rays_for(10, 10, 1, 8)
+    out["deg_rays_o"], out["deg_rays_d"] = np_(rays.origins), np_(rays.directions)
+    for deg in (1, 2, 3):
+        vg = make_grid((8, 8, 8), 3 * (deg + 1) ** 2, 50 + deg, "softplus_soft")
+        _assert_stored_grid(vg, "render_shdeg.npz", f"deg{deg}_")
+        out.update({f"deg{deg}_full_" + k: v for k, v in _ray_grad_case(vg, rays, 32, True).items()})
+        out.update({f"deg{deg}_diffuse_" + k: v for k, v in _ray_grad_case(vg, rays, 32, True, render_diffuse=True).items()})
+    save("ray_grads.npz", **out)
+    assert os.path.getsize(os.path.join(OUT, "ray_grads.npz")) < 512 * 1024
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if len(sys.argv) > 1:      # python tools/gen_golden.py g17_regulariser_modes  -> only that fixture
@@ -747,3 +804,4 @@ if __name__ == "__main__":
     g16_sds_boundary()
     g17_regulariser_modes()
     g18_degenerate_rays()
+    g19_ray_grads()

@@ -1508,6 +1508,52 @@ int voxe_distortion_debug_lanes(int32_t lanes) {
   return VOXE_OK;
 }
 
+// ---- ray and camera-pose gradients -------------------------------------------------------------------------
+int voxe_render_bwd_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
+                         const float* jitter, const float* d_colour, const float* d_depth, const float* d_acc, float* d_rays_o,
+                         float* d_rays_d, int32_t accumulate, void* stream) {
+  const int st = validate_normals_grid(grid);
+  if (st) return st;
+  if (!cfg) return VOXE_ERR_NULL_POINTER;
+  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  if (grid->feature_kind != VOXE_FEAT_SH || cfg->sh_degree < 0 || cfg->sh_degree > 3) return VOXE_ERR_UNSUPPORTED;
+  if (grid->F != 3 * (cfg->sh_degree + 1) * (cfg->sh_degree + 1)) return VOXE_ERR_BAD_SHAPE;
+  if (const int se = grid_extent_status(grid, grid->F + 1)) return se;
+  if (!grid->features) return VOXE_ERR_NULL_POINTER;
+  if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
+  if (R == 0 || (!d_rays_o && !d_rays_d)) return VOXE_OK;
+  DevGrid dg;
+  grid_to_dev(grid, &dg);
+  DevCfg dc;
+  sampling_cfg_to_dev(cfg, R, &dc);
+  dc.white = cfg->white_bkgd;
+  launch_render_rays_bwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, grid->densities, grid->features, rays_o, rays_d, jitter,
+                         d_colour, d_depth, d_acc, d_rays_o, d_rays_d, accumulate, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_render_bwd_rays_debug_lanes(int32_t lanes) {
+  if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8) return VOXE_ERR_BAD_SHAPE;
+  tl_rays_bwd_lanes = lanes;
+  return VOXE_OK;
+}
+
+size_t voxe_cast_rays_bwd_scratch_bytes(int32_t K) { return cast_rays_bwd_scratch_bytes(K); }
+
+int voxe_cast_rays_bwd(int32_t H, int32_t W, float focal, const float* poses, int32_t K, const int64_t* flat_index, int64_t B,
+                       const float* d_rays_o, const float* d_rays_d, float* d_poses, float* d_focal, int32_t accumulate,
+                       void* scratch, size_t scratch_bytes, void* stream) {
+  if (H <= 0 || W <= 0 || K <= 0 || B < 0 || !(focal > 0.0f)) return VOXE_ERR_BAD_SHAPE;
+  if (K > (1 << 24) || (int64_t)K * H * W >= (1LL << 40)) return VOXE_ERR_BAD_SHAPE;
+  if (!flat_index && B != (int64_t)K * H * W) return VOXE_ERR_BAD_SHAPE;
+  if (!poses || !d_poses) return VOXE_ERR_NULL_POINTER;
+  if (!scratch || scratch_bytes < cast_rays_bwd_scratch_bytes(K)) return VOXE_ERR_WORKSPACE;
+  if (launch_cast_rays_bwd(H, W, focal, poses, K, (const long long*)flat_index, B, d_rays_o, d_rays_d, d_poses, d_focal,
+                           accumulate, scratch, (hipStream_t)stream) != hipSuccess)
+    return VOXE_ERR_LAUNCH;
+  return finish();
+}
+
 // ---- rigid transform / re-gridding / composition ------------------------------------------------------------
 static bool resample_dims_ok(int32_t X, int32_t Y, int32_t Z, int32_t C) {
   if (X <= 0 || Y <= 0 || Z <= 0) return false;

@@ -73,6 +73,93 @@ void launch_cast_rays_indexed(int H, int W, float focal, const float* poses, int
                                                                     rays_d);
 }
 
+// ------------------------------------------------------------------------------------------------
+// cast_rays backward: the chain rule of cast_indexed_ray / cast_rays_kernel into the poses and the focal length
+//   d_trans = sum d_o,   d_rot[a][b] = sum d_d[a] dir_cam[b],   d_focal = sum d_d . (R d dir_cam / d focal)
+// kPoseSums doubles per camera (rot 9 | trans 3 | focal 1) in `sums`, zeroed by the launcher.  The lanes of a wave that
+// share a camera (whole images; mostly, a sorted batch) reduce in the wave and one lane adds; otherwise every lane adds.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPoseSums = 13;
+
+__global__ __launch_bounds__(256) void cast_rays_bwd_kernel(int H, int W, float focal, int K, const float* __restrict__ poses,
+                                                            const long long* __restrict__ flat_index, long long B,
+                                                            const float* __restrict__ d_o, const float* __restrict__ d_d,
+                                                            double* __restrict__ sums) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool on = i < B;   // (no early return: every lane joins the ballot and the shuffles)
+  double v[kPoseSums];
+#pragma unroll
+  for (int k = 0; k < kPoseSums; ++k) v[k] = 0.0;
+  int cam = 0;
+  if (on) {
+    const long long per = (long long)H * W;
+    const long long f = flat_index ? flat_index[i] : i;
+    long long cm = f / per;
+    const long long rem = f - cm * per;
+    cm = cm < 0 ? 0 : (cm >= K ? K - 1 : cm);   // as cast_indexed_ray: never out of bounds
+    cam = (int)cm;
+    const int py = (int)(rem / W), px = (int)(rem - (long long)py * W);
+    const float x = (float)px + 0.5f, y = (float)py + 0.5f;
+    const float dc[3] = {(x - (float)W * 0.5f) / focal, -(y - (float)H * 0.5f) / focal, -1.0f};
+    const float* pose = poses + (long long)cam * 12;
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double gd = d_d ? (double)d_d[3 * i + a] : 0.0;
+#pragma unroll
+      for (int b = 0; b < 3; ++b) v[3 * a + b] = gd * (double)dc[b];
+      v[9 + a] = d_o ? (double)d_o[3 * i + a] : 0.0;
+      s += gd * ((double)pose[4 * a] * (double)dc[0] + (double)pose[4 * a + 1] * (double)dc[1]);
+    }
+    v[12] = -s / (double)focal;   // d dir_cam / d focal = -(dx, dy, 0) / focal
+  }
+  if (__builtin_amdgcn_ballot_w64(on) == 0ull) return;   // (lane 0 of every remaining wave is on: i grows with the lane)
+  const int cam0 = __builtin_amdgcn_readfirstlane(cam);
+  if (__builtin_amdgcn_ballot_w64(on && cam != cam0) == 0ull) {
+#pragma unroll
+    for (int k = 0; k < kPoseSums; ++k) {
+      double t = v[k];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+      if ((threadIdx.x & 63) == 0) atomicAdd(sums + (long long)cam0 * kPoseSums + k, t);
+    }
+  } else if (on) {
+#pragma unroll
+    for (int k = 0; k < kPoseSums; ++k)
+      if (v[k] != 0.0) atomicAdd(sums + (long long)cam * kPoseSums + k, v[k]);
+  }
+}
+
+__global__ __launch_bounds__(256) void cast_rays_bwd_finalize_kernel(int K, const double* __restrict__ sums,
+                                                                     float* __restrict__ d_poses, float* __restrict__ d_focal,
+                                                                     int accumulate) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < K * 12) {
+    const int k = t / 12, e = t - k * 12, a = e >> 2, b = e & 3;
+    const float val = (float)(b < 3 ? sums[k * kPoseSums + 3 * a + b] : sums[k * kPoseSums + 9 + a]);
+    d_poses[t] = accumulate ? d_poses[t] + val : val;
+  }
+  if (t == 0 && d_focal) {
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += sums[k * kPoseSums + 12];
+    *d_focal = accumulate ? *d_focal + (float)s : (float)s;
+  }
+}
+
+size_t cast_rays_bwd_scratch_bytes(int K) { return sizeof(double) * kPoseSums * (size_t)(K > 0 ? K : 0) + 256; }
+
+hipError_t launch_cast_rays_bwd(int H, int W, float focal, const float* poses, int K, const long long* flat_index, long long B,
+                                const float* d_o, const float* d_d, float* d_poses, float* d_focal, int accumulate, void* scratch,
+                                hipStream_t st) {
+  double* sums = (double*)scratch;
+  const hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * kPoseSums * (size_t)K, st);
+  if (e != hipSuccess) return e;
+  if (B > 0 && (d_o || d_d))
+    cast_rays_bwd_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(H, W, focal, K, poses, flat_index, B, d_o, d_d, sums);
+  cast_rays_bwd_finalize_kernel<<<(K * 12 + 255) / 256, 256, 0, st>>>(K, sums, d_poses, d_focal, accumulate);
+  return hipSuccess;
+}
+
 __global__ __launch_bounds__(256) void random_subset_kernel(uint32_t n, long long count, int half, uint32_t key0,
                                                            uint32_t key1, long long* __restrict__ out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -223,6 +223,19 @@ void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, con
                        const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
                        hipStream_t st);
 
+// voxe_render_rays_bwd.hip: gradient of a render w.r.t. its rays; reads the raw densities and features, no
+// workspace, no atomics
+int rays_bwd_lanes_for(long long R);   // lanes per ray (1, 2, 4 or 8)
+extern thread_local int tl_rays_bwd_lanes;   // test aid (voxe_render_bwd_rays_debug_lanes): != 0 overrides rays_bwd_lanes_for
+void launch_render_rays_bwd(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const float* dens, const float* feat,
+                            const float* rays_o, const float* rays_d, const float* jitter, const float* g_col,
+                            const float* g_depth, const float* g_acc, float* d_o, float* d_d, int accumulate, hipStream_t st);
+// voxe_grid_ops.hip: chain rule of the ray casting into the poses and the focal length (13 doubles per camera in `scratch`)
+size_t cast_rays_bwd_scratch_bytes(int K);
+hipError_t launch_cast_rays_bwd(int H, int W, float focal, const float* poses, int K, const long long* flat_index, long long B,
+                                const float* d_o, const float* d_d, float* d_poses, float* d_focal, int accumulate, void* scratch,
+                                hipStream_t st);
+
 // voxe_transform.hip: rigid transform / re-gridding / composition of grids; arguments validated by the API
 void launch_grid_resample(const float* src_dens, const float* src_feat, int X, int Y, int Z, int C, float* dst_dens, float* dst_feat,
                           int X2, int Y2, int Z2, const VoxeResample& xf, uint8_t* taken, hipStream_t st);

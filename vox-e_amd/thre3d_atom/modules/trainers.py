@@ -18,6 +18,7 @@ from thre3d_atom.modules.optim import FusedGridAdam, VoxeAdam
 from thre3d_atom.modules.testers import test_sh_vox_grid_vol_mod_with_posed_images
 from thre3d_atom.modules.volumetric_model import VolumetricModel
 from thre3d_atom.rendering.volumetric.utils.misc import sample_random_rays_and_pixels_from_cameras
+from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, write_camera_params
 from thre3d_atom.thre3d_reprs.renderers import _render_params, render_sh_voxel_grid
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid, scale_voxel_grid_with_required_output_size
 from thre3d_atom.utils.constants import CAMERA_BOUNDS, CAMERA_INTRINSICS, HEMISPHERICAL_RADIUS
@@ -88,6 +89,10 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     distortion_weight: float = 0.0,    # addition of this build: weight of the distortion loss on the ray batch (mip-NeRF 360's
                                        # regulariser against floaters, thre3d_reprs/distortion.py); 0 = off, nothing changes.
                                        # Above 0 the iteration is not the one-call one (voxe_recon_step has no such term)
+    pose_learning_rate: float = 0.0,   # addition of this build: > 0 refines the training cameras while training (BARF / NeRF--):
+                                       # one CameraPoseDeltas over all training cameras, shared across the stages, stepped by a
+                                       # second Adam at this rate; the refined poses are saved next to the checkpoints.  0 = off,
+                                       # nothing changes.  Above 0 the iteration is not the one-call one either
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
@@ -125,6 +130,15 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                 render_diffuse=diffuse).colour for diffuse in (False, True)]
         Image.fromarray(to8b(torch.cat(views, dim=1).cpu().numpy())).save(render_dir / f"default_{step}.png")
 
+    pose_deltas = pose_optimizer = None
+    if pose_learning_rate > 0.0:
+        pose_deltas = CameraPoseDeltas(len(train_dataset)).to(device)
+        pose_optimizer = torch.optim.Adam(pose_deltas.parameters(), lr=pose_learning_rate)
+
+    def save_refined_poses() -> None:
+        refined = pose_deltas.apply(train_dataset.poses.to(device)).detach()
+        write_camera_params(model_dir / "refined_train_camera_params.json", train_dataset, refined)
+
     global_step, trained = 0, 0.0
     gen = torch.Generator().manual_seed(torch.initial_seed() % (2 ** 31))
     for stage in range(1, num_stages + 1):
@@ -141,6 +155,10 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
         if distortion_weight > 0.0:
             if one_call and stage == 1:
                 log.info("distortion_weight > 0: the iterations render, add the term and step separately (no one-call iteration)")
+            one_call = False
+        if pose_deltas is not None:
+            if one_call and stage == 1:
+                log.info("pose_learning_rate > 0: the iterations cast, render and step separately (no one-call iteration)")
             one_call = False
         fused_losses = torch.zeros(4, dtype=torch.float32, device=device)
         log.info(f"stage {stage}: grid {vol_mod.thre3d_repr.grid_dims}, images [{intr.height} x {intr.width}], lr {lr:.4f}")
@@ -176,8 +194,13 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                                           data.images, batch_it, apply_diffuse_render_regularization, fused_losses,
                                                           upcoming[2])
                 else:
+                    poses_batch = data.poses[picks]
+                    refine = {}
+                    if pose_deltas is not None:
+                        # (the rays carry the render's gradient back to the deltas of the picked cameras)
+                        poses_batch, refine = pose_deltas.apply(poses_batch, picks), {"differentiable": True}
                     rays_batch, pixels_batch = sample_random_rays_and_pixels_from_cameras(
-                        intr, data.poses[picks], data.images, ray_batch_size, image_ids=picks,
+                        intr, poses_batch, data.images, ray_batch_size, image_ids=picks, **refine,
                         # (sorting the batch by (camera, row, column) helps the ray-ordered gather of small batches; batches of
                         #  16384+ rays take the space-binned render, which does not care about the order: skip the sort)
                         memory_order=ray_batch_size < 16384, fast_subset=True)
@@ -193,8 +216,12 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         distortion = vol_mod.distortion_loss(rays_batch)
                         loss = loss + distortion_weight * distortion
                     optimizer.zero_grad()
+                    if pose_optimizer is not None:
+                        pose_optimizer.zero_grad()
                     loss.backward()
                     optimizer.step()
+                    if pose_optimizer is not None:
+                        pose_optimizer.step()
                 global_step += 1
                 trained += time.perf_counter() - t0
                 if global_step % summary_freq == 0 or it in (1, num_iterations_per_stage):
@@ -216,6 +243,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                                                global_step=global_step)
                 if it % save_freq == 0 and not fast_debug_mode:
                     torch.save(vol_mod.get_save_info(extra_info), model_dir / f"model_stage_{stage}_iter_{it}.pth")
+                    if pose_deltas is not None:
+                        save_refined_poses()
         finally:
             if fused_grid_step:   # leave the deferred-gradient mode even when the loop raised (renders would return no .grad)
                 optimizer.detach()
@@ -223,5 +252,7 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
             with torch.no_grad():
                 vol_mod.thre3d_repr = scale_voxel_grid_with_required_output_size(vol_mod.thre3d_repr, grid_sizes[stage])
     torch.save(vol_mod.get_save_info(extra_info), model_dir / "model_final.pth")
+    if pose_deltas is not None:
+        save_refined_poses()
     log.info(f"Training complete; time spent actually training: {trained:.1f} s")
     return vol_mod

@@ -238,6 +238,12 @@ HIP_ONLY = {
     "distortion_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "distortion_fwd_bwd": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, C.c_float, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
     "distortion_debug_lanes": (C.c_int, [C.c_int32]),
+    # ray and camera-pose gradients (additive, still ABI v13)
+    "render_bwd_rays": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
+    "render_bwd_rays_debug_lanes": (C.c_int, [C.c_int32]),
+    "cast_rays_bwd_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "cast_rays_bwd": (C.c_int, [C.c_int32, C.c_int32, C.c_float, _P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, _P,
+                                C.c_size_t, _P]),
     # rigid transform / re-gridding / composition of grids (additive, still ABI v13)
     "grid_resample": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                                 C.POINTER(VoxeResample), _P, _P]),

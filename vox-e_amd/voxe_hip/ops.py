@@ -250,8 +250,28 @@ class _RenderFn(torch.autograd.Function):
     def backward(ctx, g_colour, g_depth, g_acc, g_disp):
         densities, features, ro, rd, jit, colour, depth, acc = ctx.saved_tensors
         need_d, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_d or need_f):
+        need_ro, need_rd = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if not (need_d or need_f or need_ro or need_rd):
             return (None,) * 9
+        if need_ro or need_rd:
+            # the gradient to the rays is a call of its own on the raw tensors (no workspace, no forward record); the grid's
+            # gradient below is computed exactly as without it
+            grid_grads = _RenderFn._backward_grid(ctx, g_colour, g_depth, g_acc, g_disp) if (need_d or need_f) else (None, None)
+            gd = None if g_depth is None else f32c(g_depth)
+            ga = None if g_acc is None else f32c(g_acc)
+            if g_disp is not None:
+                gd, ga = disparity_bwd(depth, acc, f32c(g_disp), gd, ga)
+            d_ro, d_rd = render_bwd_rays(ctx.spec, ctx.params, densities.detach(), features.detach(), ro, rd, jit, ctx.rng,
+                                         None if g_colour is None else f32c(g_colour), gd, ga,
+                                         want_o=bool(need_ro), want_d=bool(need_rd))
+            return grid_grads + (d_ro, d_rd) + (None,) * 5
+        return _RenderFn._backward_grid(ctx, g_colour, g_depth, g_acc, g_disp) + (None,) * 7
+
+    @staticmethod
+    def _backward_grid(ctx, g_colour, g_depth, g_acc, g_disp):
+        """(d_densities, d_features) of a backward whose grid needs a gradient (None, None in the deferred-gradient mode)"""
+        densities, features, ro, rd, jit, colour, depth, acc = ctx.saved_tensors
+        need_d, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         device = densities.device
         spec, params, workspace = ctx.spec, ctx.params, ctx.workspace
         g_depth = None if g_depth is None else f32c(g_depth)
@@ -285,7 +305,7 @@ class _RenderFn(torch.autograd.Function):
                     deferred.layout = layout
                     deferred.dirty = True
                 workspace.pending = False
-                return (None,) * 9
+                return None, None
             # (the kernel that fits this render writes another gradient layout than what the region holds -- cannot happen
             #  with linear_grad -- : ordinary path; its un-pack leaves a gradient in ITS workspace's region)
             if workspace is main:
@@ -298,7 +318,7 @@ class _RenderFn(torch.autograd.Function):
         render_bwd_into(spec, params, dens, feat, ro, rd, jit, colour, depth, acc, g_colour, g_depth, g_acc,
                         d_dens, d_feat, workspace, ctx.rng)
         workspace.pending = False
-        return d_dens, d_feat, None, None, None, None, None, None, None
+        return d_dens, d_feat
 
 
 def render(spec: GridSpec, params: RenderParams, densities: torch.Tensor, features: torch.Tensor,
@@ -1466,3 +1486,140 @@ def distortion_loss(spec: GridSpec, params: RenderParams, densities: torch.Tenso
     if rng is None:
         rng = _next_rng() if (params.perturb and jitter is None) else (0, 0)
     return _DistortionFn.apply(densities, spec, params, rays_o, rays_d, jitter, rng, bool(return_ray_loss), int(_lanes))
+
+
+# ------------------------------------------------------------------------------------------------
+# ray and camera-pose gradients (DESIGN.md section 4 "Ray gradients"): the render's gradient w.r.t. its rays reads the raw grid
+# tensors only (no workspace); the ray casting's backward carries it on to the poses and the focal length
+# ------------------------------------------------------------------------------------------------
+def render_bwd_rays(spec: GridSpec, params: RenderParams, densities: torch.Tensor, features: torch.Tensor, rays_o: torch.Tensor,
+                    rays_d: torch.Tensor, jitter: Optional[torch.Tensor], rng: Tuple[int, int], g_colour: Optional[torch.Tensor],
+                    g_depth: Optional[torch.Tensor], g_acc: Optional[torch.Tensor], lanes: int = 0, want_o: bool = True,
+                    want_d: bool = True, d_rays_o: Optional[torch.Tensor] = None, d_rays_d: Optional[torch.Tensor] = None,
+                    accumulate: bool = False):
+    """voxe_render_bwd_rays: (d_rays_o [R,3], d_rays_d [R,3]) of the render of these rays for the upstream gradients g_colour
+    [R,3], g_depth [R] / [R,1], g_acc [R] / [R,1] (each may be None = 0).  want_o / want_d = False skips that output (None);
+    d_rays_o / d_rays_d: caller's buffers (contiguous float32 [R,3]), added to when `accumulate`.  `lanes` (test aid): 1 / 2 /
+    4 / 8 pins the kernel's lanes per ray for this call, 0 = chosen by R."""
+    _validate_inputs(densities, features, rays_o, rays_d, jitter, params)
+    device = densities.device
+    ensure_gfx950(device)
+    dens, feat = f32c(densities.detach()), f32c(features.detach())
+    ro, rd = f32c(rays_o.detach()), f32c(rays_d.detach())
+    jit = None if jitter is None else f32c(jitter.detach())
+    R = ro.shape[0]
+    ups = []
+    for name, t, n in (("g_colour", g_colour, 3 * R), ("g_depth", g_depth, R), ("g_acc", g_acc, R)):
+        if t is not None:
+            require_device(t, f"render_bwd_rays ({name})")
+            if t.numel() != n:
+                raise VoxeError(f"render_bwd_rays: {name} must hold {n} values; got {tuple(t.shape)}")
+            t = f32c(t.detach())
+        ups.append(t)
+    for name, t in (("d_rays_o", d_rays_o), ("d_rays_d", d_rays_d)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != device or tuple(t.shape) != (R, 3)):
+            raise VoxeError(f"render_bwd_rays: {name} must be a contiguous float32 [R,3] buffer on the grid's device")
+    g, c = _descs(spec, params, dens, feat, rng[0], rng[1], False)
+    L = lib()
+    with torch.cuda.device(device):
+        d_o = d_rays_o if d_rays_o is not None else (torch.empty((R, 3), dtype=torch.float32, device=device) if want_o else None)
+        d_d = d_rays_d if d_rays_d is not None else (torch.empty((R, 3), dtype=torch.float32, device=device) if want_d else None)
+        if lanes:
+            check(L.voxe_render_bwd_rays_debug_lanes(int(lanes)), "voxe_render_bwd_rays_debug_lanes")
+        try:
+            check(L.voxe_render_bwd_rays(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), ptr(ups[0]), ptr(ups[1]),
+                                         ptr(ups[2]), ptr(d_o), ptr(d_d), 1 if accumulate else 0, stream_ptr(device)),
+                  "voxe_render_bwd_rays")
+        finally:
+            if lanes:
+                L.voxe_render_bwd_rays_debug_lanes(0)
+    for t in (d_rays_o, d_rays_d):
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
+    return d_o, d_d
+
+
+def cast_rays_bwd(height: int, width: int, focal: float, poses: torch.Tensor, flat_index: Optional[torch.Tensor],
+                  g_rays_o: Optional[torch.Tensor], g_rays_d: Optional[torch.Tensor], want_focal: bool = False,
+                  d_poses: Optional[torch.Tensor] = None, d_focal: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """voxe_cast_rays_bwd: (d_poses [K,3,4], d_focal [] or None) of the rays cast_rays_indexed(height, width, focal, poses,
+    flat_index) returns -- flat_index None: the K whole images, ray i = pixel i -- for the upstream gradients g_rays_o / g_rays_d
+    [B,3] (either may be None = 0).  d_poses / d_focal: caller's buffers, added to when `accumulate`."""
+    require_device(poses, "cast_rays_bwd")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4):
+        raise VoxeError("cast_rays_bwd: poses must be [K,3,4]")
+    device = poses.device
+    ensure_gfx950(device)
+    p = f32c(poses.detach())
+    K = int(p.shape[0])
+    if flat_index is not None:
+        require_device(flat_index, "cast_rays_bwd")
+        if flat_index.dtype != torch.int64 or flat_index.dim() != 1:
+            raise VoxeError("cast_rays_bwd: flat_index must be int64 [B]")
+        idx = flat_index.contiguous()
+        B = int(idx.shape[0])
+    else:
+        idx, B = None, K * int(height) * int(width)
+    ups = []
+    for name, t in (("g_rays_o", g_rays_o), ("g_rays_d", g_rays_d)):
+        if t is not None:
+            require_device(t, f"cast_rays_bwd ({name})")
+            if tuple(t.shape) != (B, 3):
+                raise VoxeError(f"cast_rays_bwd: {name} must be [B,3]={B, 3}; got {tuple(t.shape)}")
+            t = f32c(t.detach())
+        ups.append(t)
+    L = lib()
+    with torch.cuda.device(device):
+        if d_poses is None:
+            d_poses = torch.empty((K, 3, 4), dtype=torch.float32, device=device)
+        if d_focal is None and want_focal:
+            d_focal = torch.empty((), dtype=torch.float32, device=device)
+        sc = _scratch_for(device, L.voxe_cast_rays_bwd_scratch_bytes(K))
+        check(L.voxe_cast_rays_bwd(int(height), int(width), float(focal), ptr(p), K, ptr(idx), B, ptr(ups[0]), ptr(ups[1]),
+                                   ptr(d_poses), ptr(d_focal), 1 if accumulate else 0, ptr(sc), sc.numel(), stream_ptr(device)),
+              "voxe_cast_rays_bwd")
+    return d_poses, d_focal
+
+
+class _CastRaysFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, poses, focal_tensor, flat_index, height, width, focal):
+        ctx.set_materialize_grads(False)
+        if flat_index is None:
+            # whole images through the indexed kernel: per pixel the arithmetic of voxe_cast_rays, bit for bit
+            index = torch.arange(poses.shape[0] * height * width, dtype=torch.int64, device=poses.device)
+        else:
+            index = flat_index
+        ro, rd = cast_rays_indexed(height, width, focal, poses.detach(), index)
+        ctx.save_for_backward(poses, flat_index)
+        ctx.geometry = (height, width, focal)
+        ctx.focal_like = focal_tensor
+        return ro, rd
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        poses, flat_index = ctx.saved_tensors
+        height, width, focal = ctx.geometry
+        want_focal = ctx.focal_like is not None and ctx.needs_input_grad[1]
+        if not (ctx.needs_input_grad[0] or want_focal) or (g_o is None and g_d is None):
+            return (None,) * 6
+        d_poses, d_focal = cast_rays_bwd(height, width, focal, poses, flat_index, g_o, g_d, want_focal=want_focal)
+        if want_focal:
+            d_focal = d_focal.to(device=ctx.focal_like.device, dtype=ctx.focal_like.dtype).reshape(ctx.focal_like.shape)
+        return (d_poses.to(poses.dtype) if ctx.needs_input_grad[0] else None), (d_focal if want_focal else None), None, None, None, None
+
+
+def cast_rays_from_poses(height: int, width: int, focal, poses: torch.Tensor,
+                         flat_index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rays_o, rays_d [B,3] of poses [K,3,4] (rotation | translation, on the GPU), differentiable w.r.t. `poses` and, when
+    `focal` is a 0-dim tensor, w.r.t. the focal length.  flat_index (int64 [B], (camera * H + y) * W + x) picks pixels as
+    cast_rays_indexed does; None: the K whole images one after the other.  The forward's bits are those of cast_rays /
+    cast_rays_indexed."""
+    require_device(poses, "cast_rays_from_poses")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4):
+        raise VoxeError("cast_rays_from_poses: poses must be [K,3,4]")
+    focal_tensor = focal if isinstance(focal, torch.Tensor) else None
+    if focal_tensor is not None and focal_tensor.dim() != 0:
+        raise VoxeError("cast_rays_from_poses: focal must be a number or a 0-dim tensor")
+    value = float(focal) if focal_tensor is None else float(focal_tensor.detach())
+    return _CastRaysFn.apply(poses, focal_tensor, flat_index, int(height), int(width), value)
