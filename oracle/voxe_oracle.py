@@ -199,6 +199,49 @@ def render_bwd(grid: Grid, cfg: abi.VoxeRenderCfg, rays_o, rays_d, d_colour, d_d
     return gd, gf
 
 
+EPS32 = 2.0 ** -24
+
+
+def budget_constants():
+    """(A, B, C, Q, V) of voxe_cpu_render_bwd_budget, in units of EPS32 (derivation: the comment above the function in voxe_cpu.c)"""
+    fn = lib().voxe_cpu_render_bwd_budget_constants
+    fn.restype, fn.argtypes = None, [C.c_void_p]
+    abc = np.zeros(5, np.float64)
+    fn(abc.ctypes.data)
+    return tuple(float(v) for v in abc)
+
+
+def render_bwd_budget(grid: Grid, cfg: abi.VoxeRenderCfg, rays_o, rays_d, d_colour, d_depth=None, d_acc=None, jitter=None, cut=None,
+                      segment=0):
+    """voxe_cpu_render_bwd_budget (the oracle's own test hook, like the cut: declared in voxe_cpu.c alone): render_bwd's inputs ->
+    {"densities": (mag, budget, count), "features": (mag, budget, count)}, float64 / float64 / int32 arrays of the gradients'
+    shapes: the sum of the magnitudes of all deposits into a voxel, the same sum weighted by each sample's float32 uncertainty in
+    units of EPS32, and the number of deposits (per voxel; the feature values of a voxel share it).  segment: the length of the
+    aligned block whose start the suffix is taken from (0: VOXE_SEGMENT_SAMPLES, the default kernels' contract; num_samples: the
+    whole ray, the contract of the plain scatter kernel's prefix/total form)"""
+    fn = lib().voxe_cpu_render_bwd_budget
+    if fn.argtypes is None:
+        bwd = lib().voxe_cpu_render_bwd
+        fn.restype, fn.argtypes = bwd.restype, list(bwd.argtypes[:6]) + [C.c_void_p, C.c_int32] + list(bwd.argtypes[6:9]) + [C.c_void_p] * 5
+    rays_o, rays_d, d_colour = _f32(rays_o), _f32(rays_d), _f32(d_colour)
+    R = rays_o.shape[0]
+    jitter = None if jitter is None else _f32(jitter)
+    d_depth = None if d_depth is None else _f32(d_depth)
+    d_acc = None if d_acc is None else _f32(d_acc)
+    if cut is not None:
+        cut = np.ascontiguousarray(cut, dtype=np.int32)
+        assert cut.shape == (R,)
+    dshape, fshape = grid.densities.shape, grid.features.shape
+    mag_d, bud_d = np.zeros(dshape, np.float64), np.zeros(dshape, np.float64)
+    mag_f, bud_f = np.zeros(fshape, np.float64), np.zeros(fshape, np.float64)
+    count = np.zeros(dshape, np.int32)
+    g = grid.desc()
+    _check(fn(C.byref(g), C.byref(cfg), rays_o.ctypes.data, rays_d.ctypes.data, R, _ptr(jitter), _ptr(cut), int(segment),
+              d_colour.ctypes.data, _ptr(d_depth), _ptr(d_acc), mag_d.ctypes.data, bud_d.ctypes.data, mag_f.ctypes.data, bud_f.ctypes.data,
+              count.ctypes.data), "render_bwd_budget")
+    return {"densities": (mag_d, bud_d, count), "features": (mag_f, bud_f, np.broadcast_to(count, fshape))}
+
+
 def sample_probe(grid: Grid, cfg: abi.VoxeRenderCfg, rays_o, rays_d, jitter=None):
     rays_o, rays_d = _f32(rays_o), _f32(rays_d)
     R, S = rays_o.shape[0], cfg.num_samples

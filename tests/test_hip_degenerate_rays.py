@@ -14,12 +14,14 @@ import pytest
 import torch
 
 import degenerate_cases as dc
+from helpers import per_voxel_check
 from test_hip_fuzz import _close
 from voxe_hip import abi
 
 from oracle import voxe_oracle as vo
 
 pytestmark = pytest.mark.gpu
+DET_BITS = 37       # the deterministic backward truncates every deposit to 2^-37 of the launch's largest contribution (64-bit fixed point)
 
 if torch.cuda.is_available():
     import gpu_helpers as gh
@@ -69,12 +71,20 @@ def _ref(name, order="image", deg=0, diffuse=False):
         perm = rng.permutation(R)
         o, d, gc, gdep, gacc = (np.ascontiguousarray(a[perm]) for a in (o, d, gc, gdep, gacc))
         jit = None if jit is None else np.ascontiguousarray(jit[perm])
-    out = dict(case=c, cfg=cfg, o=o, d=d, jit=jit, gc=gc, gdep=gdep, gacc=gacc, width=c.W if order == "image" else 0,
+    out = dict(case=c, order=order, cfg=cfg, o=o, d=d, jit=jit, gc=gc, gdep=gdep, gacc=gacc, width=c.W if order == "image" else 0,
                over=dict(image_width=c.W, image_height=c.H if c.views > 1 else 0) if order == "image" else dict(image_width=0))
     out["probe"] = vo.sample_probe(c.grid, cfg, o, d, jit)
     out["fwd"] = vo.render_fwd(c.grid, cfg, o, d, jit)
     out["bwd"] = vo.render_bwd(c.grid, cfg, o, d, gc, d_depth=gdep, d_acc=gacc, jitter=jit)
+    out["budget"] = vo.render_bwd_budget(c.grid, cfg, o, d, gc, d_depth=gdep, d_acc=gacc, jitter=jit)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def _whole_ray_budget(name, order):
+    r = _ref(name, order)
+    return vo.render_bwd_budget(r["case"].grid, r["cfg"], r["o"], r["d"], r["gc"], d_depth=r["gdep"], d_acc=r["gacc"], jitter=r["jit"],
+                                segment=r["cfg"].num_samples)
 
 
 def _check_forward(r, got):
@@ -91,8 +101,9 @@ def _check_forward(r, got):
         assert np.array_equal(got["acc"], ref["acc"]) and np.array_equal(got["colour"], ref["colour"]) and not got["acc"].any()
 
 
-def _check_backward(r, got):
-    """tests/test_hip_fuzz.py's _close (1e-4 rel-L2 + its absolute floor); an exactly-zero oracle gradient: exactly zero"""
+def _check_backward(r, got, route=""):
+    """tests/test_hip_fuzz.py's _close (1e-4 rel-L2 + its absolute floor) and tests/helpers.py's per_voxel_check (the budget twin of
+    the oracle); an exactly-zero oracle gradient: exactly zero"""
     for name, got_g, ref_g in (("densities", got[0], r["bwd"][0]), ("features", got[1], r["bwd"][1])):
         err = float(np.linalg.norm(got_g.astype(np.float64) - ref_g.astype(np.float64)))
         print(f"{r['case'].name} backward {name}: |err| {err:.3e}  |ref| {float(np.linalg.norm(ref_g)):.3e}")
@@ -100,6 +111,13 @@ def _check_backward(r, got):
             assert np.array_equal(got_g, np.zeros_like(got_g)), name
         depth_grad = r["gdep"] is not None and np.any(r["gdep"] != 0.0)
         _close(name, got_g, ref_g, far=r["cfg"].far if (name == "densities" and depth_grad) else 1.0)
+        # every voxel against its own float32 error budget: the 5e-5 floor above swallows these small gradients whole
+        # (the plain scatter's suffix is `total - prefix` over the whole ray: the twin with one block per ray)
+        budget = _whole_ray_budget(r["case"].name, r["order"]) if route == "plain_scatter" else r["budget"]
+        exempt = per_voxel_check(got_g, ref_g, *budget[name], f"{r['case'].name} backward {name}",
+                                 fixed_point_bits=DET_BITS if route == "deterministic" else None)
+        # (voxels behind a transmittance below 1e-20: only the opaque ReLU x 100/3 lattice has more than 1 % of them)
+        assert exempt <= 0.01 or r["case"].grid.density_scale >= 20.0, (name, exempt)
 
 
 def _hip_route(r, **over):
@@ -137,7 +155,7 @@ def test_case_through_route(name, route, disp):
     _check_forward(r, gh.hip_forward(*args, r["jit"], rng=c.rng, **r["over"]))
     bwd = lambda: gh.hip_backward(*args, r["gc"], g_depth=r["gdep"], g_acc=r["gacc"], jitter=r["jit"], rng=c.rng, **r["over"], **det)  # noqa: E731
     got = bwd()
-    _check_backward(r, got)
+    _check_backward(r, got, route)
     if route == "deterministic":
         again = bwd()
         assert np.array_equal(got[0], again[0]) and np.array_equal(got[1], again[1])

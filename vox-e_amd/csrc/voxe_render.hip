@@ -1054,6 +1054,8 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(
   if (white) total -= gsum * asum;
 
   float prefix = 0.0f, T = 1.0f;
+  int k_sat = -1;      // first saturated interior sample of the ray (om == 0, e != 0), and T in front of it
+  float T_sat = 0.0f;
   float z_next = rc.dg.z(rc.k_lo);
   for (int k = rc.k_lo; k <= rc.k_hi; ++k) {
     const float z = z_next;
@@ -1084,6 +1086,7 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(
     prefix += dldw * w;
     const float suffix = last ? 0.0f : (total - prefix);
     const float tail = (om > 0.0f) ? suffix / om : 0.0f;
+    if (WANT_D && om == 0.0f && e != 0.0f && !last && k_sat < 0) { k_sat = k; T_sat = T; }   // (see saturated_correction())
     const float dsig = (delta * e) * (T * dldw - tail);
     const float dv = dsig * dpost;
     float drad[COUT];
@@ -1115,6 +1118,24 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(
       }
     }
     if (c.term_eps > 0.0f && T < c.term_eps) break;
+  }
+  if constexpr (WANT_D) {
+    if (k_sat >= 0) {   // rare: the tail the `suffix / om` form lost at a saturated interior sample, after the march
+      UpstreamColour u = {{0.0f, 0.0f, 0.0f}};
+#pragma unroll
+      for (int ch = 0; ch < COUT; ++ch) u.v[ch] = gc[ch];
+      Cell cell;
+      const float dv = saturated_correction<COUT, NCM, NCU>(g, c, packed, rc, k_sat, T_sat, u, gsum, gdep, gacc, white, cell);
+      if (dv != 0.0f) {
+        const CellAddr ad = cell_addr(g, cell);
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+          const float wg = (cell.w[0][kk & 1] * cell.w[1][(kk >> 1) & 1]) * cell.w[2][kk >> 2];
+          if (wg != 0.0f)
+            atomicAdd(gpacked + (long long)(ad.base + (kk & 1) * ad.sx + ((kk >> 1) & 1) * ad.sy + (kk >> 2) * ad.sz) * C + (C - 1), dv * wg);
+        }
+      }
+    }
   }
 }
 

@@ -249,4 +249,52 @@ __device__ __forceinline__ void gather(const DevGrid& g, const float* __restrict
   }
 }
 
+// The suffix term of a SATURATED interior sample k: om_k = 1 - alpha_k is exactly 0 in float32 while e_k is not (x_k between 17.4 and
+// 87), so every weight behind k is exactly 0 and `suffix / om_k` is 0 / 0: the backward kernels take tail_k = 0 there.  The
+// reference's cumprod backward takes the product that leaves k out: tail_k = sum_{j>k} dL/dw_j alpha_j T_k prod_{k<i<j} om_i, and
+// the deposit delta_k e_k tail_k (<= 3e-8 delta_k tail_k) is missing.  Only the FIRST such sample of a ray matters (T = 0 behind it).
+// The kernels that march one ray per lane note it (sample index and T_k: two registers) and, AFTER their march, when the march's
+// registers are dead, re-march the rest of the ray for it: saturated_correction() returns what has to be added to d L / d v of
+// sample k -- the caller scatters it with the cell's weights into the density channel -- and the sample's cell.
+struct UpstreamColour { float v[3]; };
+template <int COUT, int NCM, int NCU>
+__device__ __forceinline__ float saturated_correction(const DevGrid& g, const DevCfg& c, const float* __restrict__ packed,
+                                                      RayCtx<COUT, NCM, NCU>& rc, int k, float T, const UpstreamColour& gc,
+                                                      float gsum, float gdep, float gacc, bool white, Cell& cell_k) {
+  float lead = 0.0f, tail = 0.0f, P = T;   // lead = delta_k e_k post'(v_k)
+  float z = rc.dg.z(k);
+  for (int j = k; j <= rc.k_hi && P > 0.0f; ++j) {
+    const bool last = (j == c.S - 1);
+    const float z_next = last ? z : rc.dg.z(j + 1);
+    float p[3];
+    rc.point(z, p);
+    Footprint fp;
+    footprint(g, p, fp);
+    if (fp.inside) {
+      Cell cell;
+      make_cell(g, fp, cell);
+      float v, rad[COUT];
+      gather<COUT, NCM, NCU>(g, packed, cell, rc.basis, v, rad);
+      float sigma, dpost;
+      post_activate_vg(g.post_act, v, sigma, dpost);
+      const float delta = (last ? kInfinity : (z_next - z)) * rc.dnorm;
+      const float e = fast_exp(-(sigma * delta));
+      if (j == k) {          // the saturated sample itself: its own factors, and it is left out of the product
+        lead = (delta * e) * dpost;
+        cell_k = cell;
+      } else {
+        const float alpha = 1.0f - e;
+        float dldw = fmaf(gdep, z, gacc);
+#pragma unroll
+        for (int ch = 0; ch < COUT; ++ch) dldw = fmaf(gc.v[ch], sigmoidf(rad[ch]), dldw);
+        if (white) dldw -= gsum;
+        tail = fmaf(dldw * alpha, P, tail);
+        P = P * (1.0f - alpha);
+      }
+    }
+    z = z_next;
+  }
+  return -(lead * tail);
+}
+
 }  // namespace voxe

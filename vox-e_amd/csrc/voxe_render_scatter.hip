@@ -127,6 +127,8 @@ __global__ __launch_bounds__(64) void render_bwd_packed_scatter_kernel(
     if (white) suffix0 -= gsum * suf_a;
   }
   float run = 0.0f;   // sum of dL/dw_j w_j over the samples of this segment up to and including the current one
+  int k_sat = -1;     // first saturated interior sample of this lane's ray in this segment (om == 0, e != 0), and T in front of it
+  float T_sat = 0.0f;
   float z_next = has ? rc.dg.z(k_lo) : 0.0f;
   // pending footprint of this lane's ray: cell (pc0 == INT_MIN: none) and its 8 x C accumulated values
   int pc0 = INT_MIN, pc1 = 0, pc2 = 0;
@@ -172,6 +174,7 @@ __global__ __launch_bounds__(64) void render_bwd_packed_scatter_kernel(
         run = fmaf(dldw, wk, run);
         const float suffix = last ? 0.0f : (suffix0 - run);
         const float tail = (om > 0.0f) ? suffix * fast_rcp(om) : 0.0f;
+        if (WANT_D && om == 0.0f && e != 0.0f && !last && k_sat < 0) { k_sat = k; T_sat = T; }   // (see saturated_correction())
         const float dsig = (delta * e) * fmaf(T, dldw, -tail);
         bool any = false;
 #pragma unroll
@@ -316,6 +319,26 @@ __global__ __launch_bounds__(64) void render_bwd_packed_scatter_kernel(
             const float src = kPend ? s_val[j * C + (dens ? COUT : ch)][s] : s_g[dens ? COUT : ch][s];
             const float gv = dens ? src : src * s_basis[jj][s];
             if (gv != 0.0f && w != 0.0f) atomicAdd(texel + (dens ? CM - 1 : ch * NCM + jj), gv * w);
+          }
+        }
+      }
+    }
+  }
+  if constexpr (WANT_D) {
+    if (k_sat >= 0) {   // rare: the tail the `suffix / om` form lost at a saturated interior sample, after the march
+      UpstreamColour u = {{0.0f, 0.0f, 0.0f}};
+#pragma unroll
+      for (int ch = 0; ch < COUT; ++ch) u.v[ch] = gc[ch];
+      Cell cell;
+      const float dv = saturated_correction<COUT, NCM, NCU>(g, c, packed, rc, k_sat, T_sat, u, gsum, gdep, gacc, white, cell);
+      if (dv != 0.0f) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float w = (cell.w[0][j & 1] * cell.w[1][(j >> 1) & 1]) * cell.w[2][j >> 2];
+          if (w != 0.0f) {
+            const int x = min(cell.i[0] + (j & 1), g.X - 1), y = min(cell.i[1] + ((j >> 1) & 1), g.Y - 1);
+            const int z = min(cell.i[2] + (j >> 2), g.Z - 1);
+            atomicAdd(gpacked + grad_slot(c, x, y, z, g.Y, g.Z) * CM + (CM - 1), dv * w);
           }
         }
       }
