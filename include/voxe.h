@@ -262,6 +262,12 @@ int voxe_random_subset(int64_t n, int64_t count, uint64_t seed, uint64_t rng_off
  *   - VoxeDispatch::precise_grad: 5 doubles per (ray, depth segment); cfg->deterministic: 8 B per gradient value.
  * cfg->ray_state_valid = -1 (inference) returns the size without any of these. */
 size_t voxe_workspace_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R);
+/* Optional: bytes a caller may ADD to voxe_workspace_bytes() for the per-tile plan of the lean tile kernels (large image-ordered
+ * SH-0 launches: 16 B per 8x8-pixel tile and depth segment, 320 KB at 400x400; 0 where no plan is built, and for
+ * ray_state_valid = -1).  With a workspace of at least the sum, forward and backward of a render take their per-tile decisions from
+ * the plan the forward's schedule pass writes there; with less they derive them per block -- same results, a few percent slower.
+ * Forward and backward of one render must be given the same workspace_bytes. */
+size_t voxe_tile_plan_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R);
 
 int voxe_render_fwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
                     const float* rays_o, const float* rays_d, int64_t R, const float* jitter,

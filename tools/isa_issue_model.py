@@ -213,7 +213,9 @@ def model(src_file, kernel_filter):
     return out, blocks, loops
 
 
-HEADLINE = [("voxe_render_tile4.hip", "render_bwd_tile4_kernel<8, false, 0>"), ("voxe_render_tile4.hip", "render_fwd_tile4w_kernel<false>")]
+# the kernels of the headline step: the planned instantiations and the unplanned kernels of launches without a plan
+HEADLINE = [("voxe_render_tile4.hip", "render_bwd_tile4_plan_kernel"), ("voxe_render_tile4.hip", "render_fwd_tile4w_plan_kernel"),
+            ("voxe_render_tile4.hip", "render_bwd_tile4_kernel<8, false, 0>"), ("voxe_render_tile4.hip", "render_fwd_tile4w_kernel<false>")]
 
 
 def occupancy_of(src_file):

@@ -75,14 +75,14 @@ def main():
     ap.add_argument("--cameras", type=int, nargs="*", default=list(range(3, 100, 5)))
     ap.add_argument("--image", type=int, default=400)
     ap.add_argument("--samples", type=int, default=256)
-    ap.add_argument("--prologue", type=float, nargs="*", default=None, help="iteration-equivalents (default: 5 backward, 3 forward)")
+    ap.add_argument("--prologue", type=float, nargs="*", default=None, help="iteration-equivalents (default: 4.4 backward, 2.2 forward: profiles/tile_plan.txt)")
     ap.add_argument("--empty", type=float, default=0.5)
     ap.add_argument("--widths", type=int, nargs="*", default=[4, 8, 16])
     args = ap.parse_args()
     its = {cam: iterations(cam, args.image, args.samples) for cam in args.cameras}
     for cam, (flat, mean_in) in its.items():
         print(f"camera {cam}: {mean_in:.1f} in-volume samples per ray, {int((flat > 0).sum())} of {flat.size} blocks with samples")
-    for name, slots, pro_default in (("backward", 384, 5.0), ("forward", 640, 3.0)):
+    for name, slots, pro_default in (("backward", 384, 4.4), ("forward", 640, 2.2)):
         for pro in (args.prologue or [pro_default]):
             out = {}
             for flat, _ in its.values():

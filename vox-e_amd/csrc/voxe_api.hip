@@ -152,6 +152,9 @@ struct WsLayout {
   size_t packed_off, grad_off, state_off, seg_off, prec_off, sched_off, src_off, fwdval_off, planar_off, det_off, det_scale_off, region_off;
   size_t det_bytes;                          // fixed-point gradient + its scales (contiguous from det_off)
   size_t fwd_total, total, total_with_src;   // what a forward alone / a backward / every optional buffer needs
+  // per-tile plan of the lean tile kernels, BEHIND everything voxe_workspace_bytes asks for: a caller that adds
+  // voxe_tile_plan_bytes() to its workspace gets the planned kernels, every other caller the list alone (plan_render fills these)
+  size_t plan_off, plan_bytes;
   bool has_precise, has_sched, has_src;      // the layout holds precise_grad sums / a schedule list / two-phase sources
   size_t grad_bytes() const { return state_off - grad_off; }
 };
@@ -230,10 +233,11 @@ struct RenderPlan {
     bool full, with_src;         // workspace_bytes >= total | >= total_with_src
     bool region, two_phase;      // the region route / the two-phase buffers are live
     int route;                   // effective VOXE_ROUTE_*
+    bool plan;                   // workspace_bytes >= total_with_src + the per-tile plan of this configuration
   };
   Tier tier(size_t workspace_bytes) const {
     const bool full = workspace_bytes >= l.total, with_src = workspace_bytes >= l.total_with_src;
-    Tier t{full, with_src, region && with_src, two_phase_ok && with_src, 0};
+    Tier t{full, with_src, region && with_src, two_phase_ok && with_src, 0, l.plan_bytes > 0 && workspace_bytes >= l.plan_off + l.plan_bytes};
     t.route = dc.R == 0 ? VOXE_ROUTE_NONE : det ? VOXE_ROUTE_DETERMINISTIC : t.region ? VOXE_ROUTE_REGION : tiled ? VOXE_ROUTE_TILE
               : packed_bwd ? VOXE_ROUTE_PACKED_SCATTER : VOXE_ROUTE_SCATTER;
     return t;
@@ -262,6 +266,8 @@ int plan_render(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const 
   }
   p->l = ws_layout(g, c, R, p->region);
   if (st != VOXE_OK) return st;
+  p->l.plan_off = p->l.total_with_src;
+  p->l.plan_bytes = p->l.has_sched ? tile_plan_bytes(p->dc) : 0;
   p->route = p->tier(p->l.total_with_src).route;
   p->two_phase_ok = p->tiled && p->l.has_src && !two_phase_disabled(p->dc.disp);
   if (p->l.has_precise && c->sh_degree == 0 && !p->dc.attn && p->nseg > 1 && p->dc.disp.fwd_segments_per_thread <= 1) {
@@ -289,6 +295,7 @@ FwdArgs fwd_args(const RenderPlan& p, const RenderPlan::Tier& t, void* workspace
   if (t.full) a.segbuf = at<float>(workspace, l.seg_off);
   if (t.full && keep && p.precise_sums_apply) a.segsum_d = at<double>(workspace, l.prec_off);
   if (t.full && l.has_sched) a.sched = at<int>(workspace, l.sched_off);
+  if (a.sched && t.plan) a.plan = at<int2>(workspace, l.plan_off);
   if (keep && t.two_phase) a.sample_fwd = at<float>(workspace, l.fwdval_off);   // (what the two-phase backward will read)
   return a;
 }
@@ -490,6 +497,29 @@ int voxe_tile_sched_debug_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* 
   return VOXE_OK;
 }
 
+// test aids (not part of voxe.h): byte offset in the workspace of this render's per-tile plan, one 8-byte record per block in list
+// order (voxe_render_tile4.hip: PlanCfg), -1 when launches of this configuration build none; and how many launches of the planned
+// forward / backward kernels this process has made so far
+int voxe_tile_plan_debug_offset(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, int64_t* out) {
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, nullptr, &p);
+  if (st) return st;
+  if (!out) return VOXE_ERR_NULL_POINTER;
+  *out = p.l.plan_bytes > 0 ? (int64_t)p.l.plan_off : -1;
+  return VOXE_OK;
+}
+int voxe_tile_plan_debug_launches(int64_t out[2]) {
+  if (!out) return VOXE_ERR_NULL_POINTER;
+  tile_plan_launch_counts(out);
+  return VOXE_OK;
+}
+
+size_t voxe_tile_plan_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
+  RenderPlan p;
+  if (plan_render(grid, cfg, R, nullptr, &p) != VOXE_OK || !cfg || cfg->ray_state_valid < 0) return 0;
+  return p.l.plan_bytes;
+}
+
 size_t voxe_workspace_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
   RenderPlan p;
   (void)plan_render(grid, cfg, R, nullptr, &p);   // (sizes are answered for descriptors a render call would refuse, too)
@@ -569,6 +599,7 @@ int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
   // per-sample values under the same plan: fwd_args())
   if (p.precise_sums_apply) a.segsum_d = at<const double>(workspace, l.prec_off);
   if (l.has_sched) a.sched = at<const int>(workspace, l.sched_off);
+  if (a.sched && tier.plan) a.plan = at<const int2>(workspace, l.plan_off);
   if (tier.two_phase) {
     a.sample_src = at<float>(workspace, l.src_off);
     if (p.nseg > 1) a.sample_fwd = at<const float>(workspace, l.fwdval_off);   // (only the depth-segmented forward writes them)

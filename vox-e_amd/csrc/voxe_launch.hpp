@@ -24,6 +24,8 @@ struct FwdArgs {
   // cost-ordered block list of the lean tile kernels (tile_sched_bytes(); nullable): the lean forward builds it for itself and
   // for the backward of the same rays
   int* sched = nullptr;
+  // per-tile plan of the launches that build a list (tile_plan_bytes(); nullable: without it the kernels read the list alone)
+  int2* plan = nullptr;
 };
 struct BwdArgs {
   const float *packed, *rays_o, *rays_d, *jitter, *colour, *depth, *acc, *d_colour, *d_depth, *d_acc;
@@ -39,6 +41,7 @@ struct BwdArgs {
   float* det_scale = nullptr;
   const double* segsum_d = nullptr;   // FwdArgs::segsum_d of the forward of the SAME rays (VoxeDispatch::precise_grad), or null
   const int* sched = nullptr;         // FwdArgs::sched of the forward of the SAME rays, or null
+  const int2* plan = nullptr;         // FwdArgs::plan of the forward of the SAME rays, or null
 };
 // Launch-constant device config + the dispatch decisions of THIS call (VoxeRenderCfg::dispatch, NULL = all defaults): kernels
 // take the DevCfg base by value, host-side predicates and launchers read `disp` through the accessors below (0 = default).
@@ -116,6 +119,17 @@ void launch_fwd_tile4(const DevGrid& g, const HostCfg& c, const FwdArgs& a, hipS
 // workspace for R image-ordered rays (0: never)
 bool tile_sched_applies(const HostCfg& c);
 size_t tile_sched_bytes(long long R, int W, int H, int S);
+// ... and the per-tile plan that goes with the list: bytes of FwdArgs::plan for launches of this configuration
+// (0: they build no list, or their rays do not fit a plan record) -- 8 bytes per block in list order, 8 more in launch order
+size_t tile_plan_bytes(const HostCfg& c);
+// launches of the planned forward / backward kernels made by this process so far (test aid)
+void tile_plan_launch_counts(int64_t out[2]);
+// bound on a pass's spread along the march axis (layers) of the tile backward's split decision: what launch_bwd_tile_t hands its
+// kernels, and what the schedule pass plans the lean backward's tiles with (qsplit 1, the 8-wide window)
+inline float tile_bwd_fit_m(const HostCfg& c, int qsplit, bool wide, long long tile_segs) {
+  const float env_fit_m = c.disp.tile_fit_m;
+  return env_fit_m > 0.0f ? env_fit_m : (qsplit == 4 ? (wide ? 4.5f : 4.0f) : (tile_segs <= 16000 ? 4.5f : 5.5f));
+}
 // LDS-staged forward for SH-0 image-ordered renders: writes the per-segment partials into a.segbuf (the caller then runs
 // the ordinary combine pass)
 bool fwd_tile_supported(const DevGrid& g, const HostCfg& c, int cout, int ncm);

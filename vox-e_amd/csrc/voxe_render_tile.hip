@@ -1198,13 +1198,12 @@ static void launch_bwd_tile_t(const DevGrid& g, const HostCfg& c, const BwdArgs&
   // run as sibling blocks on an under-filled chip, splitting oblique tiles beats their ring overflows by up to 1.7x (4.0
   // best at 266 px, 4.5 - 5.0 at 128 - 200 px in the 10-wide window); mid-size launches 4.5; a full chip (400x400: 20 000
   // tile-segments) prefers the overflow of ~1 % of the samples to 1.5x the blocks.
-  const float env_fit_m = c.disp.tile_fit_m;
   const long long tile_segs = ntx8 * nty8 * num_segments(c.S, c.seg_len);
   const int side_for_kl = g.X > g.Y ? (g.X > g.Z ? g.X : g.Z) : (g.Y > g.Z ? g.Y : g.Z);
   const bool wide = (float)side_for_kl >= kWideWindowRatio * (float)c.image_width;
   const float env_fit_lat = c.disp.tile_fit_lat;
   const float fit_lat = env_fit_lat;   // (0: the kernel's default, KL - 2.5 voxels)
-  const float fit_m = env_fit_m > 0.0f ? env_fit_m : (qsplit == 4 ? (wide ? 4.5f : 4.0f) : (tile_segs <= 16000 ? 4.5f : 5.5f));
+  const float fit_m = tile_bwd_fit_m(c, qsplit, wide, tile_segs);
 #define VOXE_TBWD(WD, WF, MODE, KL, NB, GB, NGR)                                                 \
   render_bwd_tile_kernel<COUT, NCM, NCU, WD, WF, MODE, KL><<<NB, 64, 0, st>>>(                    \
       g, c, a.packed, a.rays_o, a.rays_d, a.jitter, a.colour, a.depth, a.acc, a.d_colour,         \

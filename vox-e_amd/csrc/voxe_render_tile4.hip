@@ -27,6 +27,7 @@
 // accumulate.py:49-84 (alpha, transmittance, weights), process.py:45-84, voxels.py:287-332 (trilinear sample), sample.py:44-67.
 #include <limits.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "voxe_device.hpp"
@@ -78,7 +79,171 @@ struct Tile4Args {
   int ngrp, ng;
   long long nvox;
   const int* sched;       // cost-ordered block list of this launch (build_tile_sched), or null: blocks run in launch order
+  const int2* plan;       // planned kernel only: the launch's per-tile plan in list order (build_tile_sched)
 };
+
+// Orientation of a tile in its wave (wave-uniform): do the 8 consecutive lanes of a row run along the image rows (false) or down
+// the image columns (true)?  The texel gathers are bound by the texture-address / L1 path (~45 clk per divergent 16-byte wave
+// load; profiles/r05_lean_experiments.txt), and what that path sees is how many cache lines a quad / a row of lanes touches: z
+// runs fastest in memory, so consecutive lanes should step along the image axis whose world step has the larger z share (8 pixels
+// x ~0.4 voxel along z = one 128-byte line instead of eight).  Same forward, bit for bit (results are per ray); the backward's
+// parity-class deposit is conflict free for ANY lane -> pixel map.  d0 / dx / dy: directions of pixels (0, 0), (1, 0), (0, 1).
+__device__ __forceinline__ bool tile_lanes_down_columns(const DevGrid& g, const float (&d0)[3], const float (&dx)[3], const float (&dy)[3]) {
+  float ex[3], ey[3];
+  const int N[3] = {g.X, g.Y, g.Z};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float s = g.scale[a] * (float)N[a];
+    ex[a] = (dx[a] - d0[a]) * s;
+    ey[a] = (dy[a] - d0[a]) * s;
+  }
+  const float lat_x = ex[0] * ex[0] + ex[1] * ex[1], lat_y = ey[0] * ey[0] + ey[1] * ey[1];
+  // the z share of the column step beats the row step's:  ey.z^2 / lat_y > ex.z^2 / lat_x
+  return (ey[2] * ey[2]) * lat_x > (ex[2] * ex[2]) * lat_y;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The per-tile decisions of the lean kernels as functions of (tile, rays, configuration): the render kernels take them in their
+// prologue, the schedule pass takes them once per tile slot and segment for the planned instantiations.  One
+// body each -- a plan can only say what the kernel itself would have decided.
+// ------------------------------------------------------------------------------------------------------------------------
+#ifndef VOXE_T4_ORIENT
+#define VOXE_T4_ORIENT 1   // 0: lanes always along the pixel rows
+#endif
+// lanes of the wave down the image columns?  `rc`: the tile's rays with the lanes along the pixel rows (lane = 8 row + column),
+// am: ballot of the lanes whose pixel is inside the image
+template <class RC>
+__device__ __forceinline__ bool tile_turns_lanes(const DevGrid& g, const RC& rc, const unsigned long long am) {
+  if (!((am & 1ull) && (am >> 1 & 1ull) && (am >> 8 & 1ull))) return false;
+  const float d0[3] = {readlane_f32(rc.d[0], 0), readlane_f32(rc.d[1], 0), readlane_f32(rc.d[2], 0)};
+  const float dx[3] = {readlane_f32(rc.d[0], 1), readlane_f32(rc.d[1], 1), readlane_f32(rc.d[2], 1)};
+  const float dy[3] = {readlane_f32(rc.d[0], 8), readlane_f32(rc.d[1], 8), readlane_f32(rc.d[2], 8)};
+  return tile_lanes_down_columns(g, d0, dx, dy);
+}
+
+// Does the 8x8 tile fit the lateral window of the backward?  (the split decision of render_bwd_tile_kernel)  split: 0 whole |
+// 1 / 2 halves along lane bit 2 / 5 | 3 quadrants.  dr0 / dr1 / dr8: the ray directions of the wave's lanes 0, 1 and 8 in the
+// tile's FINAL orientation (both pixels inside the image); zref: un-jittered depth of the segment's last sample ke, zprev():
+// of sample max(ke - 1, 0) (asked for only when the tile splits).  Plain values: the render kernels pass wave-uniform ones
+// (tile_split_decision), the schedule pass evaluates a tile's segments side by side, one per lane.
+template <int KL, bool PREC, bool DEP, class ZPrev>
+__device__ __forceinline__ void tile_split_core(const DevGrid& g, const float (&dr0)[3], const float (&dr1)[3], const float (&dr8)[3],
+                                                const float zref, ZPrev zprev, const float fit_lat_arg, const float fit_m,
+                                                const int phases, int& split, bool& phases_fit, bool& phases_skew) {
+  const int N[3] = {g.X, g.Y, g.Z};
+  float d0[3], ex3[3], ey3[3];
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    const float s = g.scale[ax] * 0.5f * (float)N[ax];
+    const float da = dr0[ax];
+    d0[ax] = fabsf(da * s);
+    ex3[ax] = fabsf((dr1[ax] - da) * s * zref);
+    ey3[ax] = fabsf((dr8[ax] - da) * s * zref);
+  }
+  const int m = (d0[0] >= d0[1] && d0[0] >= d0[2]) ? 0 : ((d0[1] >= d0[2]) ? 1 : 2);
+  const float fit_lat = fit_lat_arg > 0.0f ? fit_lat_arg : (float)KL - 2.5f;
+  // r06: with the per-lane sample shift of the skewed march (bwd4_march, LK) a pass's extent along the march axis is no
+  // constraint any more; what counts is its lateral extent at equal LAYER: sliding a ray back by its lead along m moves it
+  // sideways by lead x |d_lat / d_m|
+  const bool skew_ok = VOXE_T4_SKEW == 1 && !PREC && !DEP && phases >= 0;
+  auto fits_pass = [&](float wx, float wy) {
+    float e[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) e[ax] = wx * ex3[ax] + wy * ey3[ax];
+    const float alongm = (m == 0) ? e[0] : ((m == 1) ? e[1] : e[2]);
+    const float dm = (m == 0) ? d0[0] : ((m == 1) ? d0[1] : d0[2]);
+    float lat = 0.0f;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+      if (ax != m) lat = fmaxf(lat, skew_ok ? e[ax] + alongm * (d0[ax] / dm) : e[ax]);
+    return lat <= fit_lat && (skew_ok || alongm <= fit_m);
+  };
+  if (!fits_pass(7.0f, 7.0f)) {
+    const bool hx = fits_pass(3.0f, 7.0f), hy = fits_pass(7.0f, 3.0f);
+    const float sx = ex3[0] + ex3[1] + ex3[2], sy = ey3[0] + ey3[1] + ey3[2];
+    if (hx && hy) split = (sx >= sy) ? 1 : 2;
+    else split = hx ? 1 : (hy ? 2 : 3);
+    // sample phases (bwd4_march, NP) put NP consecutive samples of a ray into one wave iteration: the part's extent along the
+    // march axis grows by (NP - 1) x the layers a sample advances.  Only parts that still fit the ring run phased -- the others
+    // would send their samples down the per-corner global-atomic path (100x100, oblique views: 0.25 -> 0.34 ms, r06l)
+    const float pe = ((split == 2) ? 7.0f : 3.0f) * ((m == 0) ? ex3[0] : ((m == 1) ? ex3[1] : ex3[2])) +
+                     ((split == 1) ? 7.0f : 3.0f) * ((m == 0) ? ey3[0] : ((m == 1) ? ey3[1] : ey3[2]));
+    const float dzs = fabsf(zref - zprev());
+    const float per_sample = ((m == 0) ? d0[0] : ((m == 1) ? d0[1] : d0[2])) * dzs;
+    const float more = (float)((split == 3) ? 3 : 1) * per_sample;
+    phases_fit = pe + more <= fit_m + VOXE_T4_PHASE_MARGIN;
+    if (VOXE_T4_SKEW == 2 && !phases_fit) {
+      // a part that splits for its extent ALONG the march axis: with every lane shifted by its ray's lead (bwd4_march: koff) the
+      // part occupies one ray's layers (+ 1 for the rounding of the shift) -- at the price of its lateral extent at equal layer,
+      // lead x |d_lat / d_m| wider, which has to fit the window as well
+      const float wx = (split == 2) ? 7.0f : 3.0f, wy = (split == 1) ? 7.0f : 3.0f;
+      const float dmm = (m == 0) ? d0[0] : ((m == 1) ? d0[1] : d0[2]);
+      float lat = 0.0f;
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax)
+        if (ax != m) lat = fmaxf(lat, wx * ex3[ax] + wy * ey3[ax] + pe * (d0[ax] / dmm));
+      phases_skew = lat <= fit_lat && 1.0f + more <= fit_m + VOXE_T4_PHASE_MARGIN;
+      phases_fit = phases_skew;
+    }
+  }
+}
+// ... of the tile whose rays the wave holds in its final orientation (wave-uniform)
+template <int KL, bool PREC, bool DEP, class RC>
+__device__ __forceinline__ void tile_split_decision(const DevGrid& g, const RC& rc, const int ke, const float fit_lat_arg,
+                                                    const float fit_m, const int phases, int& split, bool& phases_fit,
+                                                    bool& phases_skew) {
+  const float dr0[3] = {readlane_f32(rc.d[0], 0), readlane_f32(rc.d[1], 0), readlane_f32(rc.d[2], 0)};
+  const float dr1[3] = {readlane_f32(rc.d[0], 1), readlane_f32(rc.d[1], 1), readlane_f32(rc.d[2], 1)};
+  const float dr8[3] = {readlane_f32(rc.d[0], 8), readlane_f32(rc.d[1], 8), readlane_f32(rc.d[2], 8)};
+  tile_split_core<KL, PREC, DEP>(g, dr0, dr1, dr8, readlane_f32(rc.dg.zlin(ke), 0),
+                                 [&] { return readlane_f32(rc.dg.zlin(max(ke - 1, 0)), 0); }, fit_lat_arg, fit_m, phases, split,
+                                 phases_fit, phases_skew);
+}
+
+// The windowed forward's route of one (tile, depth segment) (render_fwd_tile_kernel's decision): m = the axis its texel window
+// marches along, -1 = the lean loop with gathers from global memory; the window's reference lane is fwd_ref_lane() of the lanes
+// with a sample inside the segment (hm != 0).  dr0 / dr1 / dr8 / dref: ray directions of lanes 0, 1, 8 (lanes along the pixel
+// rows, all three pixels inside the image) and of the reference lane; zref / zprev: un-jittered depths of the segment's last
+// sample ke and of sample max(ke - 1, 0).  Plain values, like tile_split_core.
+__device__ __forceinline__ int fwd_ref_lane(const unsigned long long hm) { return ((hm >> 27) & 1ull) ? 27 : (__ffsll((long long)hm) - 1); }
+__device__ __forceinline__ int fwd_route_core(const DevGrid& g, const float (&dr0)[3], const float (&dr1)[3], const float (&dr8)[3],
+                                              const float (&dref)[3], const float zref, const float zprev, const float fit_lat,
+                                              const float fit_m, const float zdom, const float max_adv) {
+  const int N[3] = {g.X, g.Y, g.Z};
+  float ad[3], e3[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float sc = g.scale[a] * 0.5f * (float)N[a];
+    const float da = dr0[a];
+    ad[a] = fabsf(dref[a] * sc);
+    e3[a] = 7.0f * (fabsf((dr1[a] - da) * sc * zref) + fabsf((dr8[a] - da) * sc * zref));
+  }
+  const int mxy = ad[0] >= ad[1] ? 0 : 1;
+  const int mm = (ad[2] >= fabsf(zdom) * ad[mxy]) ? 2 : mxy;
+  float lat = 0.0f, alongm = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { if (a == mm) alongm = e3[a]; else lat = fmaxf(lat, e3[a]); }
+  const float admm = (mm == 0) ? ad[0] : ((mm == 1) ? ad[1] : ad[2]);
+  const float adv = admm * fabsf(zref - zprev);
+  return (lat <= fit_lat && alongm <= fit_m && adv <= max_adv && (mm != 2 || zdom < 0.0f) && g.X > 1 && g.Y > 1 && g.Z > 1) ? mm : -1;
+}
+// ... of the tile whose rays the wave holds, lanes along the pixel rows (wave-uniform); hm / am: ballots of the lanes with a
+// sample inside the segment / with a pixel inside the image
+template <class RC>
+__device__ __forceinline__ void fwd_tile_route(const DevGrid& g, const RC& rc, const unsigned long long hm, const unsigned long long am,
+                                               const int ke, const float fit_lat, const float fit_m, const float zdom,
+                                               const float max_adv, int& m, int& ref) {
+  if (hm != 0ull && (am & 1ull) && (am >> 1 & 1ull) && (am >> 8 & 1ull)) {
+    ref = fwd_ref_lane(hm);
+    const float dr0[3] = {readlane_f32(rc.d[0], 0), readlane_f32(rc.d[1], 0), readlane_f32(rc.d[2], 0)};
+    const float dr1[3] = {readlane_f32(rc.d[0], 1), readlane_f32(rc.d[1], 1), readlane_f32(rc.d[2], 1)};
+    const float dr8[3] = {readlane_f32(rc.d[0], 8), readlane_f32(rc.d[1], 8), readlane_f32(rc.d[2], 8)};
+    const float dref[3] = {readlane_f32(rc.d[0], ref), readlane_f32(rc.d[1], ref), readlane_f32(rc.d[2], ref)};
+    // (every ray of a launch of the lean kernels has the launch's (near, far): the un-jittered depths are the same on every lane)
+    m = fwd_route_core(g, dr0, dr1, dr8, dref, readlane_f32(rc.dg.zlin(ke), 0), readlane_f32(rc.dg.zlin(ke > 0 ? ke - 1 : 0), ref),
+                       fit_lat, fit_m, zdom, max_adv);
+  }
+}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // Cost-ordered block list of the lean forward and backward.  A launch is one one-wave block per (pixel tile,
@@ -102,6 +267,54 @@ constexpr long long kSchedMaxBlocks = 1ll << 18;   // (every scatter block reads
 #endif
 static_assert(VOXE_SCHED_BUCKET >= 4 && 32 / VOXE_SCHED_BUCKET + 1 <= kSchedMaxBuckets, "bucket rows of the schedule histogram");
 
+// The per-tile plan (r08): what a block of the lean kernels derives from its index, the tile's rays and the launch geometry before
+// it marches is a pure function of (tile slot, segment, rays, configuration), and pass 1 already sits on every tile slot with
+// the tile's rays loaded.  It writes one 8-byte record per (tile slot, segment), pass 2 copies the record to the block's place
+// in the list: the planned instantiations (render_bwd_tile4_plan_kernel, render_fwd_tile4w_plan_kernel) read
+// it with one scalar load.
+//   x: bit 31 no sample inside the volume (kSchedEmpty) | 24-29 segment | 18-23 wave iterations | 13-17 first sample (kmin) - ks |
+//      7-12 reference lane of the forward's window | 6 forward: lanes down the columns | 4-5 forward route (fwd_tile_route's
+//      m + 1) | 2-3 backward split code | 1 backward: lanes down the columns
+//   y: 0-23 ray of the tile's pixel (0, 0) | 24-27, 28-31 columns, rows of the tile inside its image (0: launch padding)
+// The tile slot is implied (y names its rays); what depends on the reference lane among the rays WITH samples of a pass -- the
+// window geometry -- stays in the kernels.
+struct PlanCfg {
+  float bwd_fit_lat, bwd_fit_m;                  // the lean backward's split bounds (launch_bwd_tile_t, qsplit 1, 8-wide window)
+  int bwd_phases;
+  float fwd_fit_lat, fwd_fit_m, zdom, max_adv;   // the windowed forward's (launch_fwd_tile4)
+};
+__device__ __forceinline__ int plan_seg(int x) { return (x >> 24) & 63; }
+__device__ __forceinline__ int plan_iters(int x) { return (x >> 18) & 63; }
+__device__ __forceinline__ int plan_kmin_off(int x) { return (x >> 13) & 31; }
+__device__ __forceinline__ int plan_fwd_ref(int x) { return (x >> 7) & 63; }
+__device__ __forceinline__ bool plan_fwd_columns(int x) { return (x >> 6) & 1; }
+__device__ __forceinline__ int plan_fwd_route(int x) { return ((x >> 4) & 3) - 1; }
+__device__ __forceinline__ int plan_bwd_split(int x) { return (x >> 2) & 3; }
+__device__ __forceinline__ bool plan_bwd_columns(int x) { return (x >> 1) & 1; }
+__device__ __forceinline__ int plan_r0(int y) { return y & 0xffffff; }
+__device__ __forceinline__ int plan_nx(int y) { return (y >> 24) & 15; }
+__device__ __forceinline__ int plan_ny(int y) { return (int)((unsigned)y >> 28); }
+constexpr long long kPlanMaxRays = 1ll << 24;   // (ray index field of a record)
+
+// wave-wide integer min with the DPP operand folded into v_min_i32 (wave_min_i32 of voxe_tile_window.hpp compiles to
+// v_mov_b32_dpp + v_min_i32 + s_nop per step); all 64 lanes active
+__device__ __forceinline__ int wave_min_dpp(int v) {
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_min_i32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_min_i32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_min_i32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_min_i32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1"
+      : "+v"(v));
+  const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
+  const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
+  return min(min(a, b), min(c, d));
+}
+
 // this lane's sample range inside the depth segment [ks, ke] (empty: k_lo > k_hi) -- the render kernels' and the schedule's
 // common notion of which samples of a ray a block marches
 template <class RC>
@@ -120,7 +333,8 @@ __device__ __forceinline__ int sched_rank(int it, int nbk) {
 __global__ __launch_bounds__(1024) void tile_sched_cost_kernel(const DevGrid g, const DevCfg c, const float* __restrict__ rays_o,
                                                                const float* __restrict__ rays_d, const int ntp, const int nbk,
                                                                const int hstride, unsigned char* __restrict__ cost,
-                                                               unsigned char* __restrict__ hist) {
+                                                               unsigned char* __restrict__ hist, const PlanCfg pc,
+                                                               int2* __restrict__ plan) {
   __shared__ unsigned char rk[kSchedMaxSegs][16];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int rb = blockIdx.x * 16 + w;
@@ -130,6 +344,7 @@ __global__ __launch_bounds__(1024) void tile_sched_cost_kernel(const DevGrid g, 
   if (tile < 0) {   // (wave-uniform) launch padding: blocks without work; slots behind the launch: in no bucket
     for (int seg = lane; seg < nseg; seg += 64) {
       if (rb < ntp) cost[(long long)seg * ntp + rb] = 0;
+      if (rb < ntp && plan) plan[(long long)seg * ntp + rb] = make_int2(seg << 24, 0);
       rk[seg][w] = rb < ntp ? (unsigned char)(nbk - 1) : (unsigned char)255;
     }
   } else {
@@ -139,17 +354,57 @@ __global__ __launch_bounds__(1024) void tile_sched_cost_kernel(const DevGrid g, 
     const long long r = alive ? r_px : 0;
     RayCtx<3, 1, 1> rc;
     rc.init(g, c, r, rays_o, rays_d, nullptr);
+    // per tile: its lane orientation (this wave's lanes run along the rows whatever it says), the rays of its pixels
+    const unsigned long long am = __ballot(alive);
+    const bool turns = tile_turns_lanes(g, rc, am);            // wave-uniform
+    const bool bwd_columns = VOXE_T4_ORIENT && turns;
+    long long r00;
+    (void)tile_pixel_ray(c, ty, 0, tx << 3, 8, r00);
+    const int per = (c.image_height + 7) >> 3, tyi = ty % per;
+    const int nx = min(8, c.image_width - (tx << 3)), ny = min(8, c.image_height - (tyi << 3));
+    const int py = (int)r00 | (nx << 24) | (int)((unsigned)ny << 28);
+    // per segment: the span of the tile's samples; lane `seg` keeps what the decisions of that segment need
+    int my_it = 0, my_kmin = 0;
+    unsigned long long my_hm = 0ull;
     for (int seg = 0; seg < nseg; ++seg) {
       const int ks = seg * c.seg_len, ke = min(c.S, ks + c.seg_len) - 1;
       int k_lo, k_hi;
       seg_sample_range(rc, alive, ks, ke, k_lo, k_hi);
       const bool has = k_lo <= k_hi;
-      const int kmin = wave_min_i32(has ? k_lo : INT_MAX);
-      const int kmax = wave_max_i32(has ? k_hi : -1);
+      const unsigned long long hm = __ballot(has);
+      const int kmin = wave_min_dpp(has ? k_lo : INT_MAX);      // (all 64 lanes active)
+      const int kmax = -wave_min_dpp(has ? -k_hi : 1);
       const int it = kmin <= kmax ? kmax - kmin + 1 : 0;
-      if (lane == 0) {
-        cost[(long long)seg * ntp + rb] = (unsigned char)it;
-        rk[seg][w] = (unsigned char)sched_rank(it, nbk);
+      if (lane == seg) { my_it = it; my_kmin = it ? kmin - ks : 0; my_hm = hm; }
+    }
+    // the decisions of the render kernels' prologues, taken here once per (tile slot, segment): lane l takes those of segment l
+    // (nseg <= kSchedMaxSegs = 64), from the same functions on the same values
+    {
+      const int seg = min(lane, nseg - 1);
+      const int ke = min(c.S, seg * c.seg_len + c.seg_len) - 1;
+      const float zref = rc.dg.zlin(ke), zprev = rc.dg.zlin(max(ke - 1, 0));   // (launch-wide near / far: the same on every lane)
+      const float dr0[3] = {readlane_f32(rc.d[0], 0), readlane_f32(rc.d[1], 0), readlane_f32(rc.d[2], 0)};
+      const float dr1[3] = {readlane_f32(rc.d[0], 1), readlane_f32(rc.d[1], 1), readlane_f32(rc.d[2], 1)};
+      const float dr8[3] = {readlane_f32(rc.d[0], 8), readlane_f32(rc.d[1], 8), readlane_f32(rc.d[2], 8)};
+      const bool ok3 = (am & 1ull) && (am >> 1 & 1ull) && (am >> 8 & 1ull);
+      const int fref = my_hm != 0ull ? fwd_ref_lane(my_hm) : 0;
+      const float dref[3] = {__shfl(rc.d[0], fref, 64), __shfl(rc.d[1], fref, 64), __shfl(rc.d[2], fref, 64)};   // (all lanes active)
+      int fm = -1;
+      if (my_hm != 0ull && ok3) fm = fwd_route_core(g, dr0, dr1, dr8, dref, zref, zprev, pc.fwd_fit_lat, pc.fwd_fit_m, pc.zdom, pc.max_adv);
+      const bool fwd_columns = fm < 0 && turns;
+      int split = 0;
+      bool phases_fit = false, phases_skew = false;
+      if ((am >> 1 & 1ull) && (am >> 8 & 1ull)) {   // (lanes 1 and 8 of the tile's final orientation: the same two pixels either way)
+        const float b1[3] = {bwd_columns ? dr8[0] : dr1[0], bwd_columns ? dr8[1] : dr1[1], bwd_columns ? dr8[2] : dr1[2]};
+        const float b8[3] = {bwd_columns ? dr1[0] : dr8[0], bwd_columns ? dr1[1] : dr8[1], bwd_columns ? dr1[2] : dr8[2]};
+        tile_split_core<8, false, false>(g, dr0, b1, b8, zref, [&] { return zprev; }, pc.bwd_fit_lat, pc.bwd_fit_m, pc.bwd_phases, split, phases_fit, phases_skew);
+      }
+      if (lane < nseg) {
+        cost[(long long)seg * ntp + rb] = (unsigned char)my_it;
+        rk[seg][w] = (unsigned char)sched_rank(my_it, nbk);
+        const int px = (seg << 24) | (my_it << 18) | (my_kmin << 13) | ((my_hm != 0ull && ok3 ? fref : 0) << 7) | ((fwd_columns ? 1 : 0) << 6) |
+                       ((fm + 1) << 4) | (split << 2) | ((bwd_columns ? 1 : 0) << 1);
+        if (plan) plan[(long long)seg * ntp + rb] = make_int2(px, py);
       }
     }
   }
@@ -177,7 +432,8 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 __global__ __launch_bounds__(256) void tile_sched_scatter_kernel(const unsigned char* __restrict__ cost,
                                                                  const unsigned char* __restrict__ hist, const int ntp,
                                                                  const int ngrp, const int nbk, const int hstride,
-                                                                 int* __restrict__ list) {
+                                                                 int* __restrict__ list, const int2* __restrict__ plan,
+                                                                 int2* __restrict__ plist) {
   __shared__ int s_tot[kSchedMaxBuckets], s_pre[kSchedMaxBuckets], s_base[kSchedMaxBuckets];
   __shared__ int s_wc[kSchedMaxBuckets][4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -203,6 +459,7 @@ __global__ __launch_bounds__(256) void tile_sched_scatter_kernel(const unsigned 
   const bool valid = rb < ntp;
   const int b = seg * ntp + rb;
   const int it = valid ? (int)cost[b] : 0;
+  const int2 rec = (valid && plan) ? plan[b] : make_int2(0, 0);
   const int rank = valid ? sched_rank(it, nbk) : -1;
   int within = 0, mine = 0;
   for (int r = 0; r < nbk; ++r) {
@@ -222,6 +479,7 @@ __global__ __launch_bounds__(256) void tile_sched_scatter_kernel(const unsigned 
     int pos = s_base[rank] + within;
     for (int i = 0; i < w; ++i) pos += s_wc[rank][i];
     list[pos] = it == 0 ? (b | kSchedEmpty) : b;
+    if (plist) plist[pos] = make_int2(it == 0 ? (rec.x | kSchedEmpty) : rec.x, rec.y);   // the block's plan, where the block looks for it
   }
 }
 
@@ -248,7 +506,29 @@ size_t tile_sched_bytes(long long R, int W, int H1, int S) {
   if (nb > kSchedMaxBlocks) return 0;
   return (size_t)nb * sizeof(int) + (size_t)sched_cost_bytes(nb) + (size_t)(kSchedMaxBuckets * sched_hist_stride(ntp, nseg));
 }
-static void build_tile_sched(const DevGrid& g, const HostCfg& c, const float* rays_o, const float* rays_d, int* sched, hipStream_t st) {
+// the split bounds launch_bwd_tile_t gives the lean backward of this configuration when it runs one block per (tile, segment)
+// on the 8-wide window -- the launches that read a plan (launch_bwd_tile4 checks what it was handed against these)
+static void plan_bwd_bounds(const HostCfg& c, float& fit_m, float& fit_lat) {
+  const long long tile_segs = (long long)((c.image_width + 7) / 8) * tile_rows_total(c, 8) * num_segments(c.S, c.seg_len);
+  fit_m = tile_bwd_fit_m(c, 1, false, tile_segs);
+  fit_lat = c.disp.tile_fit_lat;
+}
+// launches of the planned kernels (forward, backward) by this process: a launch that falls back to the unplanned kernel gives the
+// same results, so only a count can tell a test that the plan is in use
+static std::atomic<long long> g_plan_launches[2];
+void tile_plan_launch_counts(int64_t out[2]) {
+  for (int i = 0; i < 2; ++i) out[i] = (int64_t)g_plan_launches[i].load(std::memory_order_relaxed);
+}
+// may the blocks of this launch take their tile from a plan record?  (its ray-index field)
+static bool tile_plan_applies(const HostCfg& c) { return c.R < kPlanMaxRays && c.image_height > 0; }
+// [plan records in list order: nb x 8 bytes | plan records in launch order (pass 1 -> pass 2): nb x 8 bytes]
+size_t tile_plan_bytes(const HostCfg& c) {
+  if (!tile_sched_applies(c) || !tile_plan_applies(c)) return 0;
+  const long long nb = (long long)blocks_for_tiles(c.map_mode, (c.image_width + 7) / 8, tile_rows_total(c, 8)) * num_segments(c.S, c.seg_len);
+  return 2 * (size_t)nb * sizeof(int2);
+}
+static void build_tile_sched(const DevGrid& g, const HostCfg& c, const float* rays_o, const float* rays_d, int* sched, int2* plist,
+                             const float fwd_fit_lat, const float fwd_fit_m, const float zdom, const float max_adv, hipStream_t st) {
   const int nseg = num_segments(c.S, c.seg_len);
   const int ntp = blocks_for_tiles(c.map_mode, (c.image_width + 7) / 8, tile_rows_total(c, 8));
   const int nb = ntp * nseg;
@@ -256,8 +536,13 @@ static void build_tile_sched(const DevGrid& g, const HostCfg& c, const float* ra
   unsigned char* hist = cost + sched_cost_bytes(nb);
   const int nbk = (c.seg_len + VOXE_SCHED_BUCKET - 1) / VOXE_SCHED_BUCKET + 1;
   const int ngrp = (ntp + 15) / 16, hstride = (int)sched_hist_stride(ntp, nseg);
-  tile_sched_cost_kernel<<<ngrp, 1024, 0, st>>>(g, c, rays_o, rays_d, ntp, nbk, hstride, cost, hist);
-  tile_sched_scatter_kernel<<<dim3((ntp + 255) / 256, nseg), 256, 0, st>>>(cost, hist, ntp, ngrp, nbk, hstride, sched);
+  PlanCfg pc;
+  plan_bwd_bounds(c, pc.bwd_fit_m, pc.bwd_fit_lat);
+  pc.bwd_phases = c.disp.tile_phases;
+  pc.fwd_fit_lat = fwd_fit_lat; pc.fwd_fit_m = fwd_fit_m; pc.zdom = zdom; pc.max_adv = max_adv;
+  int2* const plan = plist ? plist + nb : nullptr;     // (no plan buffer: the list alone)
+  tile_sched_cost_kernel<<<ngrp, 1024, 0, st>>>(g, c, rays_o, rays_d, ntp, nbk, hstride, cost, hist, pc, plan);
+  tile_sched_scatter_kernel<<<dim3((ntp + 255) / 256, nseg), 256, 0, st>>>(cost, hist, ntp, ngrp, nbk, hstride, sched, plan, plist);
 }
 
 // what a deposit pass multiplies the sample's sources with (this lane's ray, this block's channel group):
@@ -318,45 +603,6 @@ __device__ __forceinline__ void global_add_f32(gchar* base, unsigned voff, float
   asm volatile("" : "+v"(voff));
   __hip_atomic_fetch_add(reinterpret_cast<gfloat*>(base + (size_t)voff), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// wave-wide integer min with the DPP operand folded into v_min_i32 (wave_min_i32 of voxe_tile_window.hpp compiles to
-// v_mov_b32_dpp + v_min_i32 + s_nop per step); all 64 lanes active
-__device__ __forceinline__ int wave_min_dpp(int v) {
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_min_i32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_i32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_i32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_i32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1"
-      : "+v"(v));
-  const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-  const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-  return min(min(a, b), min(c, d));
-}
-
-// Orientation of a tile in its wave (wave-uniform): do the 8 consecutive lanes of a row run along the image rows (false) or down
-// the image columns (true)?  The texel gathers are bound by the texture-address / L1 path (~45 clk per divergent 16-byte wave
-// load; profiles/r05_lean_experiments.txt), and what that path sees is how many cache lines a quad / a row of lanes touches: z
-// runs fastest in memory, so consecutive lanes should step along the image axis whose world step has the larger z share (8 pixels
-// x ~0.4 voxel along z = one 128-byte line instead of eight).  Same forward, bit for bit (results are per ray); the backward's
-// parity-class deposit is conflict free for ANY lane -> pixel map.  d0 / dx / dy: directions of pixels (0, 0), (1, 0), (0, 1).
-__device__ __forceinline__ bool tile_lanes_down_columns(const DevGrid& g, const float (&d0)[3], const float (&dx)[3], const float (&dy)[3]) {
-  float ex[3], ey[3];
-  const int N[3] = {g.X, g.Y, g.Z};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float s = g.scale[a] * (float)N[a];
-    ex[a] = (dx[a] - d0[a]) * s;
-    ey[a] = (dy[a] - d0[a]) * s;
-  }
-  const float lat_x = ex[0] * ex[0] + ex[1] * ex[1], lat_y = ey[0] * ey[0] + ey[1] * ey[1];
-  // the z share of the column step beats the row step's:  ey.z^2 / lat_y > ex.z^2 / lat_x
-  return (ey[2] * ey[2]) * lat_x > (ex[2] * ex[2]) * lat_y;
-}
-
 // One pass of one (tile, depth segment) with the march axis MA as a compile-time constant.
 // PREC (VoxeDispatch::precise_grad): the suffix sum behind sample k, sum_{j > k} dL/dw_j w_j, is what remains of the segment's
 // LOCAL sums (double, from the forward: the same float products, subtracted here in the same order -- exact to 1e-16 of the
@@ -1037,19 +1283,26 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
 
 // NCU_DEP > 0: the deposit pass of a view-dependent grid with NCU_DEP coefficients per colour (MODE 2 of render_bwd_tile_kernel:
 // same block order -- channel group outermost --, same lanes -> pixels, same source-buffer slots as its source pass)
-template <int KL, bool PREC, int NCU_DEP = 0>
-#ifndef VOXE_TILE4_LB_PREC
-#define VOXE_TILE4_LB_PREC 2   // the precise kernels at 3 waves per SIMD spill inside the sample loop (0.64 vs 0.50 ms on the bench camera)
-#endif
-__global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE_TILE4_LB)) void render_bwd_tile4_kernel(const DevGrid g, const DevCfg c, const Tile4Args a_in) {
+// PLAN (planned instantiation): `a_in.plan` is the launch's plan in list order (build_tile_sched) -- which tile,
+// which segment, how its lanes lie and how it splits come out of one 8-byte record instead of the block index, the tile's rays and
+// the launch geometry.  Same decisions (tile_turns_lanes / tile_split_decision, taken by the schedule pass), same passes.
+// The body is shared by the kernels below it: render_bwd_tile4_kernel<KL, PREC, NCU_DEP>, unplanned as ever, and
+// render_bwd_tile4_plan_kernel, the planned instantiation of <8, false, 0> for launches that built a list and a plan.
+template <int KL, bool PREC, int NCU_DEP, bool PLAN>
+__device__ __forceinline__ void render_bwd_tile4_body(const DevGrid g, const DevCfg c, const Tile4Args a_in) {
   constexpr bool DEP = NCU_DEP > 0;
+  static_assert(!PLAN || (KL == 8 && !PREC && !DEP), "planned instantiation: the SH-0 float kernel of the 8-wide window only");
   __shared__ double win[WinMap<KL, 4>::kDoubles];
   __shared__ int2 tab[kTabKeys];
   const int lane = threadIdx.x;
   // cost-ordered launches (Tile4Args::sched): this block does the work of launch-order block sched[blockIdx.x]; a block without
   // a sample inside the volume has nothing to do
   int bid = blockIdx.x;
-  if constexpr (!DEP) {
+  int2 pe = make_int2(0, 0);
+  if constexpr (PLAN) {
+    pe = a_in.plan[blockIdx.x];   // (wave-uniform address: a scalar load)
+    if (pe.x < 0) return;
+  } else if constexpr (!DEP) {
     if (a_in.sched) {
       bid = a_in.sched[blockIdx.x];
       if (bid < 0) return;   // (wave-uniform)
@@ -1058,6 +1311,7 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
   for (int i = lane; i < WinMap<KL, 4>::kDoubles; i += 64) win[i] = 0.0;
 
   // ---- block -> ([channel group,] pixel tile, depth segment[, part]): the block order of render_bwd_tile_kernel ----------
+  // (PLAN: all of this comes out of the plan record below; what the record replaces is never computed)
   const int W = c.image_width;
   const int ntx = (W + 7) >> 3, nty = (int)tile_rows_total(c, 8);
   const int nseg = num_segments(c.S, c.seg_len);
@@ -1067,102 +1321,45 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
   if constexpr (DEP) { grp = part / (nseg * a_in.qsplit); part -= grp * nseg * a_in.qsplit; }
   Tile4Args a = a_in;
   if constexpr (DEP) a.gpacked = a_in.gpacked + (long long)grp * a_in.nvox * 4;   // the group's plane of the staging gradient
-  const int quad = part / nseg, seg = part - quad * nseg;
-  const int tile = logical_tile_of(c, bid % ntp, ntp, ntx, nty);
+  const int quad = PLAN ? 0 : part / nseg, seg = PLAN ? plan_seg(pe.x) : part - quad * nseg;
+  const int tile = PLAN ? 0 : logical_tile_of(c, bid % ntp, ntp, ntx, nty);
   if (tile < 0) return;  // launch padding (wave-uniform)
   const int ks = seg * c.seg_len, ke = min(c.S, ks + c.seg_len) - 1;
   const int ty = tile / ntx, tx = tile - ty * ntx;
-  long long r_px;
-  bool alive = tile_pixel_ray(c, ty, lane >> 3, (tx << 3) + (lane & 7), 8, r_px);
+  long long r_px = 0;
+  bool alive = PLAN ? false : tile_pixel_ray(c, ty, lane >> 3, (tx << 3) + (lane & 7), 8, r_px);
   long long r = alive ? r_px : 0;
+  bool columns = false;           // lanes run down the image columns (wave-uniform)
+  if constexpr (PLAN) {
+    // the plan record: orientation; ray of the tile's pixel (0, 0) and the pixels of the tile inside its image -- no division, no
+    // second look at the rays
+    columns = plan_bwd_columns(pe.x);
+    const int li = columns ? (lane & 7) : (lane >> 3), lj = columns ? (lane >> 3) : (lane & 7);   // pixel (row, column) inside the tile
+    alive = lj < plan_nx(pe.y) && li < plan_ny(pe.y);
+    r = alive ? (long long)(plan_r0(pe.y) + li * W + lj) : 0;
+  }
 
   RayCtx<3, 1, 1> rc;
   rc.init(g, c, r, a.rays_o, a.rays_d, nullptr);
-#ifndef VOXE_T4_ORIENT
-#define VOXE_T4_ORIENT 1   // 0: lanes always along the pixel rows
-#endif
-  bool columns = false;           // lanes run down the image columns (wave-uniform)
-  if (VOXE_T4_ORIENT && !DEP) {   // lanes along the image rows or down the columns (tile_lanes_down_columns): fewer cache lines per gather
-                                  // (a deposit pass gathers nothing, and its lanes must sit where the source pass's did)
-    const unsigned long long am0 = __ballot(alive);
-    if ((am0 & 1ull) && (am0 >> 1 & 1ull) && (am0 >> 8 & 1ull)) {
-      const float d0[3] = {readlane_f32(rc.d[0], 0), readlane_f32(rc.d[1], 0), readlane_f32(rc.d[2], 0)};
-      const float dx[3] = {readlane_f32(rc.d[0], 1), readlane_f32(rc.d[1], 1), readlane_f32(rc.d[2], 1)};
-      const float dy[3] = {readlane_f32(rc.d[0], 8), readlane_f32(rc.d[1], 8), readlane_f32(rc.d[2], 8)};
-      if (tile_lanes_down_columns(g, d0, dx, dy)) {   // wave-uniform
-        columns = true;
-        alive = tile_pixel_ray(c, ty, lane & 7, (tx << 3) + (lane >> 3), 8, r_px);
-        r = alive ? r_px : 0;
-        rc.init(g, c, r, a.rays_o, a.rays_d, nullptr);
-      }
+  if (VOXE_T4_ORIENT && !DEP && !PLAN) {   // lanes along the image rows or down the columns (tile_turns_lanes): fewer cache lines per gather
+                                           // (a deposit pass gathers nothing, and its lanes must sit where the source pass's did)
+    if (tile_turns_lanes(g, rc, __ballot(alive))) {   // wave-uniform
+      columns = true;
+      alive = tile_pixel_ray(c, ty, lane & 7, (tx << 3) + (lane >> 3), 8, r_px);
+      r = alive ? r_px : 0;
+      rc.init(g, c, r, a.rays_o, a.rays_d, nullptr);
     }
   }
 
-  // ---- does the 8x8 tile fit the lateral window?  (the split decision of render_bwd_tile_kernel) -------------------------
+  // ---- does the 8x8 tile fit the lateral window?  (tile_split_decision; PLAN: taken by the schedule pass) ------------------
   int split = 0;
   bool phases_fit = false;     // (r06) the parts of this tile leave room in the ring for 2 / 4 consecutive samples of a ray
   bool phases_skew = false;    // (r06) ... only when their lanes are shifted by the samples a ray is ahead of the part's reference ray
-  {
+  if constexpr (PLAN) split = plan_bwd_split(pe.x);
+  else {
     const unsigned long long am = __ballot(alive);
-    if ((am >> 1 & 1ull) && (am >> 8 & 1ull)) {
-      const int N[3] = {g.X, g.Y, g.Z};
-      const float zref = readlane_f32(rc.dg.zlin(ke), 0);
-      float d0[3], ex3[3], ey3[3];
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        const float s = g.scale[ax] * 0.5f * (float)N[ax];
-        const float da = readlane_f32(rc.d[ax], 0);
-        d0[ax] = fabsf(da * s);
-        ex3[ax] = fabsf((readlane_f32(rc.d[ax], 1) - da) * s * zref);
-        ey3[ax] = fabsf((readlane_f32(rc.d[ax], 8) - da) * s * zref);
-      }
-      const int m = (d0[0] >= d0[1] && d0[0] >= d0[2]) ? 0 : ((d0[1] >= d0[2]) ? 1 : 2);
-      const float fit_lat = a.fit_lat > 0.0f ? a.fit_lat : (float)KL - 2.5f;
-      // r06: with the per-lane sample shift of the skewed march (bwd4_march, LK) a pass's extent along the march axis is no
-      // constraint any more; what counts is its lateral extent at equal LAYER: sliding a ray back by its lead along m moves it
-      // sideways by lead x |d_lat / d_m|
-      const bool skew_ok = VOXE_T4_SKEW == 1 && !PREC && !DEP && a.phases >= 0;
-      auto fits_pass = [&](float wx, float wy) {
-        float e[3];
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) e[ax] = wx * ex3[ax] + wy * ey3[ax];
-        const float alongm = (m == 0) ? e[0] : ((m == 1) ? e[1] : e[2]);
-        const float dm = (m == 0) ? d0[0] : ((m == 1) ? d0[1] : d0[2]);
-        float lat = 0.0f;
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax)
-          if (ax != m) lat = fmaxf(lat, skew_ok ? e[ax] + alongm * (d0[ax] / dm) : e[ax]);
-        return lat <= fit_lat && (skew_ok || alongm <= a.fit_m);
-      };
-      if (!fits_pass(7.0f, 7.0f)) {
-        const bool hx = fits_pass(3.0f, 7.0f), hy = fits_pass(7.0f, 3.0f);
-        const float sx = ex3[0] + ex3[1] + ex3[2], sy = ey3[0] + ey3[1] + ey3[2];
-        if (hx && hy) split = (sx >= sy) ? 1 : 2;
-        else split = hx ? 1 : (hy ? 2 : 3);
-        // sample phases (bwd4_march, NP) put NP consecutive samples of a ray into one wave iteration: the part's extent along the
-        // march axis grows by (NP - 1) x the layers a sample advances.  Only parts that still fit the ring run phased -- the others
-        // would send their samples down the per-corner global-atomic path (100x100, oblique views: 0.25 -> 0.34 ms, r06l)
-        const float pe = ((split == 2) ? 7.0f : 3.0f) * ((m == 0) ? ex3[0] : ((m == 1) ? ex3[1] : ex3[2])) +
-                         ((split == 1) ? 7.0f : 3.0f) * ((m == 0) ? ey3[0] : ((m == 1) ? ey3[1] : ey3[2]));
-        const float dzs = fabsf(zref - readlane_f32(rc.dg.zlin(max(ke - 1, 0)), 0));
-        const float per_sample = ((m == 0) ? d0[0] : ((m == 1) ? d0[1] : d0[2])) * dzs;
-        const float more = (float)((split == 3) ? 3 : 1) * per_sample;
-        phases_fit = pe + more <= a.fit_m + VOXE_T4_PHASE_MARGIN;
-        if (VOXE_T4_SKEW == 2 && !phases_fit) {
-          // a part that splits for its extent ALONG the march axis: with every lane shifted by its ray's lead (bwd4_march: koff) the
-          // part occupies one ray's layers (+ 1 for the rounding of the shift) -- at the price of its lateral extent at equal layer,
-          // lead x |d_lat / d_m| wider, which has to fit the window as well
-          const float wx = (split == 2) ? 7.0f : 3.0f, wy = (split == 1) ? 7.0f : 3.0f;
-          const float dmm = (m == 0) ? d0[0] : ((m == 1) ? d0[1] : d0[2]);
-          float lat = 0.0f;
-#pragma unroll
-          for (int ax = 0; ax < 3; ++ax)
-            if (ax != m) lat = fmaxf(lat, wx * ex3[ax] + wy * ey3[ax] + pe * (d0[ax] / dmm));
-          phases_skew = lat <= fit_lat && 1.0f + more <= a.fit_m + VOXE_T4_PHASE_MARGIN;
-          phases_fit = phases_skew;
-        }
-      }
-    }
+    if ((am >> 1 & 1ull) && (am >> 8 & 1ull))
+      tile_split_decision<KL, PREC, DEP>(g, rc, ke, a.fit_lat, a.fit_m, a.phases, split, phases_fit, phases_skew);
   }
   // the strata of this depth segment: lane l holds (lower, span) of sample ks + l (DepthGen's own expressions)
   float strat_lo = 0.0f, strat_sp = 0.0f;
@@ -1296,8 +1493,8 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
     return split == 0 ? 36 : (split == 1 ? 33 + 4 * q : (split == 2 ? 12 + 32 * q : 9 + 4 * (q & 1) + 32 * (q >> 1)));
   };
   const int nparts = split == 0 ? 1 : (split == 3 ? 4 : 2);
-  const int q_begin = a.qsplit == 4 ? quad : 0;
-  const int q_end = a.qsplit == 4 ? min(quad + 1, nparts) : nparts;
+  const int q_begin = (!PLAN && a.qsplit == 4) ? quad : 0;      // (planned launches: qsplit 1)
+  const int q_end = (!PLAN && a.qsplit == 4) ? min(quad + 1, nparts) : nparts;
   // r06: the parts of a split tile with 2 / 4 sample phases per ray -- the lanes outside part q take the other phases of the
   // part's rays (lane bits 2 / 5 say which part a lane's own pixel is in: xor-ing them with q gives the phase, forcing them to q
   // the lane whose ray this lane works on)
@@ -1316,7 +1513,7 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
                                   // stay in the source (tests build them: tools/variants.py -DVOXE_T4_PHASES_KL10=1) as a measured alternative.
 #endif
   constexpr bool kPhases = !PREC && !DEP && (KL >= 9 ? VOXE_T4_PHASES_KL10 != 0 : VOXE_T4_PHASES_KL8 != 0);
-  if constexpr (kPhases) {
+  if constexpr (kPhases && !PLAN) {   // (a plan carries no phase decision: planned blocks run the one-sample passes)
    if (split != 0 && a.phases >= 0 && phases_fit) {
     const int bx = (lane >> 2) & 1, by = (lane >> 5) & 1;
     for (int q = q_begin; q < q_end; ++q) {
@@ -1339,6 +1536,19 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
     run_pass(alive && in_part(q), centre_of(q), centre2_of(q), std::integral_constant<int, 1>(), 0, 0, 0);
     __syncthreads();
   }
+}
+
+#ifndef VOXE_TILE4_LB_PREC
+#define VOXE_TILE4_LB_PREC 2   // the precise kernels at 3 waves per SIMD spill inside the sample loop (0.64 vs 0.50 ms on the bench camera)
+#endif
+// builds whose split decision reads more than a plan record holds (sample phases, the skewed march) have no planned instantiation
+constexpr bool kPlanBuild = VOXE_T4_PHASES_KL8 == 0 && VOXE_T4_SKEW != 1;
+template <int KL, bool PREC, int NCU_DEP = 0>
+__global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE_TILE4_LB)) void render_bwd_tile4_kernel(const DevGrid g, const DevCfg c, const Tile4Args a_in) {
+  render_bwd_tile4_body<KL, PREC, NCU_DEP, false>(g, c, a_in);
+}
+__global__ __launch_bounds__(64, VOXE_TILE4_LB) void render_bwd_tile4_plan_kernel(const DevGrid g, const DevCfg c, const Tile4Args a_in) {
+  render_bwd_tile4_body<8, false, 0, kPlanBuild>(g, c, a_in);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1747,76 +1957,77 @@ __device__ __forceinline__ void fwd4w_march(const DevGrid& g, const DevCfg& c, c
   }
 }
 
-template <bool PREC>
-__global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_kernel(const DevGrid g, const DevCfg c,
-                                                                              const float* __restrict__ packed,
-                                                                              const float* __restrict__ rays_o,
-                                                                              const float* __restrict__ rays_d,
-                                                                              float* __restrict__ segbuf, double* __restrict__ segsum,
-                                                                              const float fit_lat, const float fit_m, const float zdom,
-                                                                              const float max_adv, const int* __restrict__ sched) {
+// PLAN (planned instantiation): `plan` is the launch's plan in list order -- tile, segment, route, reference lane,
+// lane orientation and the wave's sample span come out of the block's 8-byte record (fwd_tile_route / tile_turns_lanes, taken by
+// the schedule pass); the rays are loaded once, in the tile's final orientation.
+// The body is shared by the kernels below it: render_fwd_tile4w_kernel<PREC>, unplanned as ever, and render_fwd_tile4w_plan_kernel,
+// the planned instantiation of <false>.
+template <bool PREC, bool PLAN>
+__device__ __forceinline__ void render_fwd_tile4w_body(const DevGrid g, const DevCfg c, const float* __restrict__ packed,
+                                                       const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                       float* __restrict__ segbuf, double* __restrict__ segsum, const float fit_lat,
+                                                       const float fit_m, const float zdom, const float max_adv,
+                                                       const int* __restrict__ sched, const int2* __restrict__ plan) {
   constexpr int COUT = 3, NC = COUT + 3;
+  static_assert(!(PLAN && PREC), "planned instantiation: the float kernel only");
   __shared__ float4 tex[kF4Ring * 64];
   __shared__ int4 org[kF4Table];
   const int lane = threadIdx.x;
+  int seg, ks, ke, m = -1, ref = 0, k_lo, k_hi, kmin, kmax;
+  bool alive, has;
+  long long r;
+  RayCtx<COUT, 1, 1> rc;
+  if constexpr (PLAN) {
+    const int2 pe = plan[blockIdx.x];   // (wave-uniform address: a scalar load)
+    if (plan_ny(pe.y) == 0) return;                                     // launch padding
+    seg = plan_seg(pe.x);
+    m = plan_fwd_route(pe.x); ref = plan_fwd_ref(pe.x);
+    const bool columns = plan_fwd_columns(pe.x);
+    const int li = columns ? (lane & 7) : (lane >> 3), lj = columns ? (lane >> 3) : (lane & 7);   // pixel (row, column) inside the tile
+    alive = lj < plan_nx(pe.y) && li < plan_ny(pe.y);
+    r = alive ? (long long)(plan_r0(pe.y) + li * c.image_width + lj) : 0;
+    rc.init(g, c, r, rays_o, rays_d, nullptr);
+    ks = seg * c.seg_len; ke = min(c.S, ks + c.seg_len) - 1;
+    seg_sample_range(rc, alive, ks, ke, k_lo, k_hi);
+    has = k_lo <= k_hi;
+    // the span of the tile's rays inside the segment (bit 31 of x, no sample: an empty span -- the rays still get their
+    // identity segment records below)
+    kmin = ks + plan_kmin_off(pe.x);
+    kmax = pe.x < 0 ? kmin - 1 : kmin + plan_iters(pe.x) - 1;
+  } else {
   const int nseg = num_segments(c.S, c.seg_len);
   const int nrb = gridDim.x / nseg;                    // tile slots (segment-major block order, like render_fwd_seg_kernel)
   // cost-ordered launches: the work of launch-order block sched[blockIdx.x] (bit 31: no sample inside the volume -- its rays
   // still get their identity segment records below)
   const int bid = sched ? (sched[blockIdx.x] & 0x7fffffff) : (int)blockIdx.x;
-  const int seg = bid / nrb, rb = bid - seg * nrb;
+  seg = bid / nrb;
+  const int rb = bid - seg * nrb;
   const int W = c.image_width;
   const int ntx = (W + 7) >> 3, nty = (int)tile_rows_total(c, 8);
   const int tile = logical_tile_of(c, rb, nrb, ntx, nty);
   if (tile < 0) return;
   const int ty = tile / ntx, tx = tile - ty * ntx;
   long long r_px;
-  bool alive = tile_pixel_ray(c, ty, lane >> 3, (tx << 3) + (lane & 7), 8, r_px);
-  long long r = alive ? r_px : 0;
-  RayCtx<COUT, 1, 1> rc;
+  alive = tile_pixel_ray(c, ty, lane >> 3, (tx << 3) + (lane & 7), 8, r_px);
+  r = alive ? r_px : 0;
   rc.init(g, c, r, rays_o, rays_d, nullptr);
-  const int ks = seg * c.seg_len, ke = min(c.S, ks + c.seg_len) - 1;
-  // ---- per tile (wave-uniform): through the window along axis m, or the lean loop (render_fwd_tile_kernel's decision) ----
-  int m = -1, ref = 0;
+  ks = seg * c.seg_len; ke = min(c.S, ks + c.seg_len) - 1;
+  // ---- per tile (wave-uniform): through the window along axis m, or the lean loop (fwd_tile_route) ----
   {
     const int k_lo0 = max(rc.k_lo, ks), k_hi0 = alive ? min(rc.k_hi, ke) : k_lo0 - 1;
     const unsigned long long hm = __ballot(k_lo0 <= k_hi0), am = __ballot(alive);
-    if (hm != 0ull && (am & 1ull) && (am >> 1 & 1ull) && (am >> 8 & 1ull)) {
-      ref = ((hm >> 27) & 1ull) ? 27 : (__ffsll((long long)hm) - 1);
-      const int N[3] = {g.X, g.Y, g.Z};
-      const float zref = readlane_f32(rc.dg.zlin(ke), 0);
-      float ad[3], e3[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float sc = g.scale[a] * 0.5f * (float)N[a];
-        const float da = readlane_f32(rc.d[a], 0);
-        ad[a] = fabsf(readlane_f32(rc.d[a], ref) * sc);
-        e3[a] = 7.0f * (fabsf((readlane_f32(rc.d[a], 1) - da) * sc * zref) + fabsf((readlane_f32(rc.d[a], 8) - da) * sc * zref));
-      }
-      const int mxy = ad[0] >= ad[1] ? 0 : 1;
-      const int mm = (ad[2] >= fabsf(zdom) * ad[mxy]) ? 2 : mxy;
-      float lat = 0.0f, alongm = 0.0f;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) { if (a == mm) alongm = e3[a]; else lat = fmaxf(lat, e3[a]); }
-      const float adv = ad[mm] * fabsf(readlane_f32(rc.dg.zlin(ke) - rc.dg.zlin(ke > 0 ? ke - 1 : 0), ref));
-      if (lat <= fit_lat && alongm <= fit_m && adv <= max_adv && (mm != 2 || zdom < 0.0f) && g.X > 1 && g.Y > 1 && g.Z > 1) m = mm;
-    }
-    if (m < 0 && (am & 1ull) && (am >> 1 & 1ull) && (am >> 8 & 1ull)) {   // gathers from global memory: the lane orientation that touches fewer lines
-      const float d0[3] = {readlane_f32(rc.d[0], 0), readlane_f32(rc.d[1], 0), readlane_f32(rc.d[2], 0)};
-      const float dx[3] = {readlane_f32(rc.d[0], 1), readlane_f32(rc.d[1], 1), readlane_f32(rc.d[2], 1)};
-      const float dy[3] = {readlane_f32(rc.d[0], 8), readlane_f32(rc.d[1], 8), readlane_f32(rc.d[2], 8)};
-      if (tile_lanes_down_columns(g, d0, dx, dy)) {   // wave-uniform
-        alive = tile_pixel_ray(c, ty, lane & 7, (tx << 3) + (lane >> 3), 8, r_px);
-        r = alive ? r_px : 0;
-        rc.init(g, c, r, rays_o, rays_d, nullptr);
-      }
+    fwd_tile_route(g, rc, hm, am, ke, fit_lat, fit_m, zdom, max_adv, m, ref);
+    if (m < 0 && tile_turns_lanes(g, rc, am)) {   // gathers from global memory: the lane orientation that touches fewer lines (wave-uniform)
+      alive = tile_pixel_ray(c, ty, lane & 7, (tx << 3) + (lane >> 3), 8, r_px);
+      r = alive ? r_px : 0;
+      rc.init(g, c, r, rays_o, rays_d, nullptr);
     }
   }
-  int k_lo, k_hi;
   seg_sample_range(rc, alive, ks, ke, k_lo, k_hi);
-  const bool has = k_lo <= k_hi;
-  const int kmin = wave_min_dpp(has ? k_lo : INT_MAX);
-  const int kmax = -wave_min_dpp(has ? -k_hi : INT_MAX);
+  has = k_lo <= k_hi;
+  kmin = wave_min_dpp(has ? k_lo : INT_MAX);
+  kmax = -wave_min_dpp(has ? -k_hi : INT_MAX);
+  }
   float csum[COUT];
   double csum_d[COUT];
 #pragma unroll
@@ -1845,6 +2056,26 @@ __global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_kernel(co
   segbuf[(base + 2 + COUT) * c.R + r] = dsum;
 }
 
+template <bool PREC>
+__global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_kernel(const DevGrid g, const DevCfg c,
+                                                                              const float* __restrict__ packed,
+                                                                              const float* __restrict__ rays_o,
+                                                                              const float* __restrict__ rays_d,
+                                                                              float* __restrict__ segbuf, double* __restrict__ segsum,
+                                                                              const float fit_lat, const float fit_m, const float zdom,
+                                                                              const float max_adv, const int* __restrict__ sched) {
+  render_fwd_tile4w_body<PREC, false>(g, c, packed, rays_o, rays_d, segbuf, segsum, fit_lat, fit_m, zdom, max_adv, sched, nullptr);
+}
+// (the decision bounds are the schedule pass's business)
+__global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_plan_kernel(const DevGrid g, const DevCfg c,
+                                                                                   const float* __restrict__ packed,
+                                                                                   const float* __restrict__ rays_o,
+                                                                                   const float* __restrict__ rays_d,
+                                                                                   float* __restrict__ segbuf,
+                                                                                   const int2* __restrict__ plan) {
+  render_fwd_tile4w_body<false, true>(g, c, packed, rays_o, rays_d, segbuf, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, nullptr, plan);
+}
+
 // the lean forward takes what the lean backward takes (the window width does not matter to it)
 bool fwd_tile4_supported(const DevGrid& g, const HostCfg& c, const FwdArgs& a, int cout, int ncm) {
   if (c.disp.tile_lean < 0 || ncm != 1 || !((cout == 3 && !c.attn) || (cout == 1 && c.attn))) return false;
@@ -1859,13 +2090,17 @@ void launch_fwd_tile4(const DevGrid& g, const HostCfg& c, const FwdArgs& a, hipS
   // the cost-ordered block list of these rays: built here for the windowed forward AND for the lean backward of the same rays,
   // whichever forward kernel of this function runs (launch_bwd_tile4 counts on it under the same condition)
   int* const sched = (a.sched && tile_sched_applies(c)) ? a.sched : nullptr;
-  if (sched) build_tile_sched(g, c, a.rays_o, a.rays_d, sched, st);
+  const float fit_lat = disp_or(c.disp.fwd_fit_lat, 5.5f), fit_m = disp_or(c.disp.fwd_fit_m, (float)kF4Ring - 1.5f);
+  const float zdom = disp_or(c.disp.fwd_zdom, VOXE_FWD4W_ZDOM), max_adv = disp_or(c.disp.fwd_max_adv, 1.7f);
+  int2* const plist = (kPlanBuild && sched && a.plan && tile_plan_bytes(c) > 0) ? a.plan : nullptr;
+  if (sched) build_tile_sched(g, c, a.rays_o, a.rays_d, sched, plist, fit_lat, fit_m, zdom, max_adv, st);
   if (c.attn) render_fwd_tile4_kernel<1, false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr);
   else if (c.disp.fwd_window >= 0 && (reinterpret_cast<uintptr_t>(a.packed) & 15) == 0) {   // r06: corners from an LDS window of the tile's texels
-    const float fit_lat = disp_or(c.disp.fwd_fit_lat, 5.5f), fit_m = disp_or(c.disp.fwd_fit_m, (float)kF4Ring - 1.5f);
-    const float zdom = disp_or(c.disp.fwd_zdom, VOXE_FWD4W_ZDOM), max_adv = disp_or(c.disp.fwd_max_adv, 1.7f);
     if (a.segsum_d) render_fwd_tile4w_kernel<true><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, a.segsum_d, fit_lat, fit_m, zdom, max_adv, sched);
-    else render_fwd_tile4w_kernel<false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr, fit_lat, fit_m, zdom, max_adv, sched);
+    else if (plist) {   // a list and its plan were built: the planned instantiation
+      g_plan_launches[0].fetch_add(1, std::memory_order_relaxed);
+      render_fwd_tile4w_plan_kernel<<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, plist);
+    } else render_fwd_tile4w_kernel<false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr, fit_lat, fit_m, zdom, max_adv, sched);
   }
   else if (a.segsum_d) render_fwd_tile4_kernel<3, true><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, a.segsum_d);
   else render_fwd_tile4_kernel<3, false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr);
@@ -1936,7 +2171,7 @@ void launch_bwd_tile4_dep(const DevGrid& g, const HostCfg& c, const BwdArgs& a, 
   t.qsplit = qsplit; t.fit_m = fit_m; t.fit_lat = fit_lat; t.want_d = 1; t.want_f = 1;
   t.segsum = nullptr; t.phases = -1;
   t.sample_src = reinterpret_cast<const float4*>(a.sample_src);
-  t.sched = nullptr;
+  t.sched = nullptr; t.plan = nullptr;
   const int cm = 3 * ncu + 1;
   t.ngrp = ngrp; t.ng = cm; t.nvox = (long long)g.X * g.Y * g.Z;
   (void)hipMemsetAsync(a.grad_planar, 0, tile_planar_bytes(t.nvox, cm), st);
@@ -1959,11 +2194,21 @@ void launch_bwd_tile4(const DevGrid& g, const HostCfg& c, const BwdArgs& a, int 
   // the forward of these rays left its cost-ordered block list next to the depth-segment states (launch_fwd_tile4, same
   // condition); sibling-part launches (qsplit 4) have another block count and keep the launch order
   t.sched = (a.sched && qsplit == 1 && tile_sched_applies(c)) ? a.sched : nullptr;
+  t.plan = nullptr;
   if (a.segsum_d) {   // VoxeDispatch::precise_grad
     if (kl == 10) render_bwd_tile4_kernel<10, true><<<nb, 64, 0, st>>>(g, c, t);
     else render_bwd_tile4_kernel<8, true><<<nb, 64, 0, st>>>(g, c, t);
   } else if (kl == 10) render_bwd_tile4_kernel<10, false><<<nb, 64, 0, st>>>(g, c, t);
-  else render_bwd_tile4_kernel<8, false><<<nb, 64, 0, st>>>(g, c, t);
+  else {
+    // a list was built, and its plan was made with the bounds this launch was handed: the planned instantiation
+    float plan_fit_m, plan_fit_lat;
+    plan_bwd_bounds(c, plan_fit_m, plan_fit_lat);
+    if (kPlanBuild && t.sched && a.plan && tile_plan_bytes(c) > 0 && plan_fit_m == fit_m && plan_fit_lat == fit_lat) {
+      t.plan = a.plan;
+      g_plan_launches[1].fetch_add(1, std::memory_order_relaxed);
+      render_bwd_tile4_plan_kernel<<<nb, 64, 0, st>>>(g, c, t);
+    } else render_bwd_tile4_kernel<8, false><<<nb, 64, 0, st>>>(g, c, t);
+  }
 }
 
 }  // namespace voxe

@@ -196,6 +196,7 @@ HIP_ONLY = {
     "strerror": (C.c_char_p, [C.c_int]),
     "device_check": (C.c_int, [C.c_char_p, C.c_size_t]),
     "workspace_bytes": (C.c_size_t, [_GD, _RC, C.c_int64]),
+    "tile_plan_bytes": (C.c_size_t, [_GD, _RC, C.c_int64]),
     # fused optimiser step of a grid (gradient stays in the workspace between the two calls)
     "render_bwd_acc": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_int32), _P, C.c_size_t, _P]),

@@ -125,6 +125,12 @@ class Workspace:
         self.state_key = None
 
 
+def _render_ws_bytes(L, g, c, R) -> int:
+    """workspace of a render call: what the library asks for plus, behind it, room for the per-tile plan of the lean tile kernels
+    (voxe.h: voxe_tile_plan_bytes; 0 where none is built)"""
+    return L.voxe_workspace_bytes(C.byref(g), C.byref(c), R) + L.voxe_tile_plan_bytes(C.byref(g), C.byref(c), R)
+
+
 def _pack_key(spec: GridSpec, densities: torch.Tensor, features: torch.Tensor):
     return (densities.data_ptr(), densities._version, features.data_ptr(), features._version,
             tuple(features.shape), spec.density_scale, spec.density_pre_act, spec.feature_kind)
@@ -189,7 +195,7 @@ def render_fwd_into(spec: GridSpec, params: RenderParams, densities, features, r
     g, c = _descs(spec, params, densities, features, rng[0], rng[1], workspace.key == key)
     with torch.cuda.device(device):
         c.ray_state_valid = 0 if keep_for_backward else -1     # (-1: the size query leaves out everything only a backward reads)
-        ws = workspace.ensure(L.voxe_workspace_bytes(C.byref(g), C.byref(c), R), device)
+        ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
         c.reuse_packed_grid = int(workspace.key == key)
         check(L.voxe_render_fwd(C.byref(g), C.byref(c), ptr(rays_o), ptr(rays_d), R, ptr(jitter), ptr(colour),
                                 ptr(depth), ptr(acc), ptr(disparity), ptr(ws), ws.numel(),
@@ -208,7 +214,7 @@ def render_bwd_into(spec: GridSpec, params: RenderParams, densities, features, r
     key = _pack_key(spec, densities, features)
     g, c = _descs(spec, params, densities, features, rng[0], rng[1], workspace.key == key)
     with torch.cuda.device(device):
-        ws = workspace.ensure(L.voxe_workspace_bytes(C.byref(g), C.byref(c), R), device)
+        ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
         c.reuse_packed_grid = int(workspace.key == key)
         c.ray_state_valid = int(workspace.state_key == _state_key(key, params, rays_o, rays_d, jitter, rng, _route(g, c, R)))
         check(L.voxe_render_bwd(C.byref(g), C.byref(c), ptr(rays_o), ptr(rays_d), R, ptr(jitter), ptr(colour),
@@ -661,7 +667,7 @@ def render_bwd_acc(spec: GridSpec, params: RenderParams, densities, features, ra
     if expect_layout != abi.GRAD_ANY and R > 0 and expect_layout != predicted_grad_layout(spec, params, densities, features, R):
         return None
     with torch.cuda.device(device):
-        ws = workspace.ensure(L.voxe_workspace_bytes(C.byref(g), C.byref(c), R), device)
+        ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
         c.reuse_packed_grid = int(workspace.key == key)
         c.ray_state_valid = int(workspace.state_key == _state_key(key, params, rays_o, rays_d, jitter, rng, _route(g, c, R)))
         gws = None if grad_workspace is None else grad_workspace.buf
@@ -825,7 +831,7 @@ def attn_refine_step_(spec: GridSpec, params: RenderParams, densities, attn, ray
     rs.losses, rs.attn_render = ptr(losses), ptr(attn_render)
     with torch.cuda.device(device):
         had = workspace.buf
-        ws = workspace.ensure(L.voxe_workspace_bytes(C.byref(g), C.byref(c), R), device)
+        ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
         # (a buffer this call allocated holds whatever torch.empty returned in its gradient region)
         rs.zero_gradient_first = int(bool(zero_gradient_first) or ws is not had)
         c.reuse_packed_grid = int(workspace.key == key)
