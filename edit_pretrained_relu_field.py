@@ -58,6 +58,8 @@ def edit_stage_intrinsics(checkpoint_intrinsics, dataset, data_downsample_factor
         return dataset.camera_intrinsics
     h, w, f = checkpoint_intrinsics
     factor = float(data_downsample_factor)
+    if hasattr(checkpoint_intrinsics, "scaled"):   # a PinholeCamera keeps fy, cx, cy and its lens (the same truncated size)
+        return checkpoint_intrinsics.scaled(factor)
     return type(checkpoint_intrinsics)(max(int(h / factor), 1), max(int(w / factor), 1), f / factor)
 
 

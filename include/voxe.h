@@ -860,6 +860,58 @@ int voxe_grid_resample(const float* src_densities /* [X,Y,Z,1] or NULL */, const
                        int32_t X2, int32_t Y2, int32_t Z2,
                        const VoxeResample* xf, uint8_t* taken /* [X2,Y2,Z2] or NULL */, void* stream);
 
+/* ---- real-capture cameras: intrinsics and lens distortion (not in the reference) ------------------------------
+ * An added symbol is backward compatible: VOXE_ABI_VERSION stays 13.  No voxe_cpu_ twin; the float64 restatement and the
+ * float32 restatement of the kernel's iteration are tests/camera_ref.py.  voxe_cast_rays, voxe_cast_rays_indexed,
+ * voxe_cast_rays_bwd, VoxeReconStep and voxe_recon_step / voxe_recon_prefetch keep the (H, W, focal) camera.
+ *
+ * VoxeCamera: one pinhole camera with the OpenCV radial / tangential lens model, shared by the K poses of a call.  Pixel
+ * (px, py) has its centre at (px + 0.5, py + 0.5); fx, fy, cx, cy are in pixels.
+ *
+ * voxe_cast_rays_camera: per ray, in float32 without FMA,
+ *       x = px + 0.5, y = py + 0.5, xd = (x - cx) / fx, yd = (y - cy) / fy                      (yd is image-down)
+ *       (xu, yu) solves D(xu, yu) = (xd, yd),  r2 = xu^2 + yu^2,  rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *         D_x = xu rad + 2 p1 xu yu + p2 (r2 + 2 xu^2),    D_y = yu rad + p1 (r2 + 2 yu^2) + 2 p2 xu yu
+ *       dir_cam = (xu, -yu, -1),  rays_d = R dir_cam,  rays_o = t.
+ *   The solve starts at (xd, yd) and takes 6 Newton steps with the analytic 2x2 Jacobian on every lane: no early exit, no
+ *   data-dependent branch, so a ray's bits depend on that ray only (not on B or its place in the batch).  When all five
+ *   coefficients are exactly 0, (xu, yu) = (xd, yd) and no iteration runs; with also fx == fy == focal, cx == W * 0.5f and
+ *   cy == H * 0.5f the rays equal those of voxe_cast_rays_indexed bit for bit.  The kernel does not detect a lens model that is
+ *   not invertible over the image: that check is the host's (PinholeCamera.validate()).
+ *   flat_index (device int64 [B], (camera * H + y) * W + x) picks pixels and is decoded and clamped as voxe_cast_rays_indexed
+ *   does; NULL: ray i is pixel i of K whole images and B must be K * H * W.  B == 0: VOXE_OK, no launch.
+ *   H, W, K <= 0, B < 0, fx or fy not finite and > 0, cx, cy or a coefficient not finite: VOXE_ERR_BAD_SHAPE.
+ *
+ * voxe_cast_rays_camera_bwd: the chain rule of voxe_cast_rays_camera by the implicit-function theorem at the forward's
+ *   solution (the iterations are not differentiated).  With g = R^T d_rays_d, (g_xu, g_yu) = (g_0, -g_1),
+ *   (g_xd, g_yd) = J^-T (g_xu, g_yu), J = dD / d(xu, yu):
+ *       d_fx = sum -g_xd xd / fx,  d_cx = sum -g_xd / fx,  d_fy = sum -g_yd yd / fy,  d_cy = sum -g_yd / fy,
+ *       d_kj = sum -(g_xd, g_yd) . dD/dkj,   dD/dk1 = r2 (xu, yu), dD/dk2 = r2^2 (xu, yu), dD/dk3 = r2^3 (xu, yu),
+ *       dD/dp1 = (2 xu yu, r2 + 2 yu^2), dD/dp2 = (r2 + 2 xu^2, 2 xu yu),
+ *   and d_poses as voxe_cast_rays_bwd with this dir_cam.  d_intrinsics: device float[4] (fx fy cx cy); d_distortion: device
+ *   float[5] (k1 k2 p1 p2 k3); each of the three outputs may be NULL (not computed).  Either d_rays_* may be NULL (= 0).  The
+ *   sums are carried in double, 12 per camera plus 9 global ones in `scratch` (voxe_cast_rays_camera_bwd_scratch_bytes(K); NULL
+ *   or too small: VOXE_ERR_WORKSPACE), then cast once into the outputs, added to them when accumulate != 0.  Cameras with no ray
+ *   get an exact 0.  B == 0 or all three outputs NULL: VOXE_OK with no launch (B == 0 and accumulate == 0: the outputs are set
+ *   to 0).  The 9 global sums are reduced inside the wave before one lane adds, the per-camera sums as voxe_cast_rays_bwd; the
+ *   adds are double atomics, so the result is NOT promised bit-reproducible from run to run.  Validation and error codes are
+ *   those of voxe_cast_rays_camera and voxe_cast_rays_bwd.  Caller's stream, no host synchronisation, no allocation.        */
+typedef struct VoxeCamera {
+  int32_t H, W;
+  float fx, fy, cx, cy;          /* pixels; pixel (px,py) has centre (px+0.5, py+0.5) */
+  float k1, k2, p1, p2, k3;      /* OpenCV radial / tangential coefficients */
+} VoxeCamera;
+
+int voxe_cast_rays_camera(const VoxeCamera* cam, const float* poses /* device [K,3,4] */, int32_t K,
+                          const int64_t* flat_index /* device [B] or NULL: ray i = pixel i of K whole images */,
+                          int64_t B, float* rays_o, float* rays_d, void* stream);
+size_t voxe_cast_rays_camera_bwd_scratch_bytes(int32_t K);
+int voxe_cast_rays_camera_bwd(const VoxeCamera* cam, const float* poses, int32_t K, const int64_t* flat_index, int64_t B,
+                              const float* d_rays_o, const float* d_rays_d /* [B,3], either may be NULL */,
+                              float* d_poses /* [K,3,4] or NULL */, float* d_intrinsics /* device float[4] fx fy cx cy, or NULL */,
+                              float* d_distortion /* device float[5] k1 k2 p1 p2 k3, or NULL */,
+                              int32_t accumulate, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.

@@ -22,6 +22,7 @@ from thre3d_atom.utils.imaging_utils import (  # noqa: E402
     CameraPose,
     get_thre360_animation_poses,
     get_thre360_spiral_animation_poses,
+    novel_view_camera,
     postprocess_depth_map,
     scale_camera_intrinsics,
     to8b,
@@ -67,7 +68,7 @@ def main(**kwargs) -> None:
         data = PosedImagesDataset(Path(cfg.data_path) / "train", Path(cfg.data_path) / "train_camera_params.json",
                                   rgba_white_bkgd=True)
         poses = [CameraPose(p[:, :3], p[:, 3:]) for p in data.poses]
-    intrinsics = scale_camera_intrinsics(intrinsics, cfg.render_scale_factor)
+    intrinsics = scale_camera_intrinsics(novel_view_camera(intrinsics), cfg.render_scale_factor)   # (no lens on a novel view)
     frames, geometry = [], []
     for n, pose in enumerate(poses):
         if cfg.render_geometry:

@@ -30,6 +30,7 @@ from thre3d_atom.utils.imaging_utils import (  # noqa: E402
     CameraPose,
     get_thre360_animation_poses,
     get_thre360_spiral_animation_poses,
+    novel_view_camera,
     scale_camera_intrinsics,
     to8b,
 )
@@ -97,7 +98,7 @@ def main(**kwargs) -> None:
         data = PosedImagesDataset(Path(cfg.data_path) / "train", Path(cfg.data_path) / "train_camera_params.json",
                                   rgba_white_bkgd=vol_mod.render_config.white_bkgd)
         poses = [CameraPose(p[:, :3], p[:, 3:]) for p in data.poses]
-    intrinsics = scale_camera_intrinsics(intrinsics, cfg.render_scale_factor)
+    intrinsics = scale_camera_intrinsics(novel_view_camera(intrinsics), cfg.render_scale_factor)   # (no lens on a novel view)
     frames = []
     for n, pose in enumerate(poses):
         log.info(f"rendering frame number: ({n + 1}/{len(poses)})")

@@ -73,6 +73,8 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
               help="weight of the distortion loss on the ray batch (against floaters); 0 = off")
 @click.option("--pose_learning_rate", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
               help="> 0: refine the training cameras while training (Adam at this rate on per-camera pose deltas); 0 = off")
+@click.option("--intrinsics_learning_rate", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
+              help="> 0 (with --pose_learning_rate): also learn fx, fy, cx, cy of the shared camera at this rate; 0 = off")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -109,7 +111,8 @@ def main(**kwargs) -> None:
         apply_diffuse_render_regularization=cfg.apply_diffuse_render_regularization, fast_debug_mode=cfg.fast_debug_mode,
         save_freq=cfg.save_frequency, test_freq=cfg.test_frequency, feedback_freq=cfg.feedback_frequency,
         summary_freq=cfg.summary_frequency, verbose_rendering=cfg.verbose_rendering, lpips_weight=cfg.lpips_weight,
-        num_workers=cfg.num_workers, distortion_weight=cfg.distortion_weight, pose_learning_rate=cfg.pose_learning_rate)
+        num_workers=cfg.num_workers, distortion_weight=cfg.distortion_weight, pose_learning_rate=cfg.pose_learning_rate,
+        intrinsics_learning_rate=cfg.intrinsics_learning_rate)
 
 
 if __name__ == "__main__":

@@ -1585,6 +1585,59 @@ int voxe_cast_rays_bwd(int32_t H, int32_t W, float focal, const float* poses, in
   return finish();
 }
 
+// ---- real-capture cameras -------------------------------------------------------------------------------------
+static bool camera_ok(const VoxeCamera* c) {
+  if (c->H <= 0 || c->W <= 0) return false;
+  if (!(c->fx > 0.0f) || !(c->fy > 0.0f) || !std::isfinite(c->fx) || !std::isfinite(c->fy)) return false;
+  const float rest[7] = {c->cx, c->cy, c->k1, c->k2, c->p1, c->p2, c->k3};
+  for (float v : rest)
+    if (!std::isfinite(v)) return false;
+  return true;
+}
+
+static int camera_call_ok(const VoxeCamera* cam, const float* poses, int32_t K, const int64_t* flat_index, int64_t B) {
+  if (!cam) return VOXE_ERR_NULL_POINTER;
+  if (!camera_ok(cam) || K <= 0 || B < 0) return VOXE_ERR_BAD_SHAPE;
+  if (K > (1 << 24) || (int64_t)K * cam->H * cam->W >= (1LL << 40)) return VOXE_ERR_BAD_SHAPE;
+  if (!flat_index && B != (int64_t)K * cam->H * cam->W) return VOXE_ERR_BAD_SHAPE;
+  if (!poses) return VOXE_ERR_NULL_POINTER;
+  return VOXE_OK;
+}
+
+int voxe_cast_rays_camera(const VoxeCamera* cam, const float* poses, int32_t K, const int64_t* flat_index, int64_t B,
+                          float* rays_o, float* rays_d, void* stream) {
+  const int ok = camera_call_ok(cam, poses, K, flat_index, B);
+  if (ok != VOXE_OK) return ok;
+  if (B == 0) return VOXE_OK;   // (nothing is written: the outputs of an empty batch may have no address)
+  if (!rays_o || !rays_d) return VOXE_ERR_NULL_POINTER;
+  launch_cast_rays_camera(*cam, poses, K, (const long long*)flat_index, B, rays_o, rays_d, (hipStream_t)stream);
+  return finish();
+}
+
+size_t voxe_cast_rays_camera_bwd_scratch_bytes(int32_t K) { return cast_rays_camera_bwd_scratch_bytes(K); }
+
+int voxe_cast_rays_camera_bwd(const VoxeCamera* cam, const float* poses, int32_t K, const int64_t* flat_index, int64_t B,
+                              const float* d_rays_o, const float* d_rays_d, float* d_poses, float* d_intrinsics,
+                              float* d_distortion, int32_t accumulate, void* scratch, size_t scratch_bytes, void* stream) {
+  const int ok = camera_call_ok(cam, poses, K, flat_index, B);
+  if (ok != VOXE_OK) return ok;
+  if (!d_poses && !d_intrinsics && !d_distortion) return VOXE_OK;
+  if (!scratch || scratch_bytes < cast_rays_camera_bwd_scratch_bytes(K)) return VOXE_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (B == 0) {   // nothing to sum: an overwriting call leaves exact zeros, no kernel runs
+    if (!accumulate) {
+      if (d_poses && hipMemsetAsync(d_poses, 0, sizeof(float) * 12 * (size_t)K, st) != hipSuccess) return VOXE_ERR_LAUNCH;
+      if (d_intrinsics && hipMemsetAsync(d_intrinsics, 0, sizeof(float) * 4, st) != hipSuccess) return VOXE_ERR_LAUNCH;
+      if (d_distortion && hipMemsetAsync(d_distortion, 0, sizeof(float) * 5, st) != hipSuccess) return VOXE_ERR_LAUNCH;
+    }
+    return VOXE_OK;
+  }
+  if (launch_cast_rays_camera_bwd(*cam, poses, K, (const long long*)flat_index, B, d_rays_o, d_rays_d, d_poses, d_intrinsics,
+                                  d_distortion, accumulate, scratch, st) != hipSuccess)
+    return VOXE_ERR_LAUNCH;
+  return finish();
+}
+
 // ---- rigid transform / re-gridding / composition ------------------------------------------------------------
 static bool resample_dims_ok(int32_t X, int32_t Y, int32_t Z, int32_t C) {
   if (X <= 0 || Y <= 0 || Z <= 0) return false;

@@ -250,6 +250,15 @@ hipError_t launch_cast_rays_bwd(int H, int W, float focal, const float* poses, i
                                 const float* d_o, const float* d_d, float* d_poses, float* d_focal, int accumulate, void* scratch,
                                 hipStream_t st);
 
+// voxe_camera.hip: ray casting through a VoxeCamera (intrinsics + lens distortion) and its chain rule (12 doubles
+// per camera + 9 global ones in `scratch`); arguments validated by the API
+void launch_cast_rays_camera(const VoxeCamera& cam, const float* poses, int K, const long long* flat_index, long long B,
+                             float* rays_o, float* rays_d, hipStream_t st);
+size_t cast_rays_camera_bwd_scratch_bytes(int K);
+hipError_t launch_cast_rays_camera_bwd(const VoxeCamera& cam, const float* poses, int K, const long long* flat_index, long long B,
+                                       const float* d_o, const float* d_d, float* d_poses, float* d_intrinsics,
+                                       float* d_distortion, int accumulate, void* scratch, hipStream_t st);
+
 // voxe_transform.hip: rigid transform / re-gridding / composition of grids; arguments validated by the API
 void launch_grid_resample(const float* src_dens, const float* src_feat, int X, int Y, int Z, int C, float* dst_dens, float* dst_feat,
                           int X2, int Y2, int Z2, const VoxeResample& xf, uint8_t* taken, hipStream_t st);

@@ -40,6 +40,8 @@ STATE_DICT_NAMES = {"u_DENSITIES": "_densities", "u_FEATURES": "_features", "u_A
 CAMERA_JSON_KEYS = {
     "INTRINSIC": "intrinsic", "EXTRINSIC": "extrinsic", "BOUNDS": "bounds", "HEIGHT": "height", "WIDTH": "width",
     "FOCAL": "focal", "ROTATION": "rotation", "TRANSLATION": "translation", "DIRECTION": "dir",
+    # optional, inside INTRINSIC: the real-capture camera model (PinholeCamera; one shared camera per file)
+    "FOCAL_X": "fx", "FOCAL_Y": "fy", "CENTRE_X": "cx", "CENTRE_Y": "cy", "DISTORTION": "distortion",
 }
 
 

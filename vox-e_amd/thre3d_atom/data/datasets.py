@@ -17,10 +17,48 @@ from torch import Tensor
 from torch.utils.data import Dataset
 
 from thre3d_atom.data.constants import (
-    BOUNDS, DIRECTION, EXTRINSIC, FOCAL, HEIGHT, INTRINSIC, ROTATION, TRANSLATION, WIDTH,
+    BOUNDS, CENTRE_X, CENTRE_Y, DIRECTION, DISTORTION, EXTRINSIC, FOCAL, FOCAL_X, FOCAL_Y, HEIGHT, INTRINSIC, ROTATION,
+    TRANSLATION, WIDTH,
 )
 from thre3d_atom.utils.constants import NUM_COLOUR_CHANNELS
-from thre3d_atom.utils.imaging_utils import CameraBounds, CameraIntrinsics, CameraPose
+from thre3d_atom.utils.imaging_utils import CameraBounds, CameraIntrinsics, CameraPose, PinholeCamera
+
+
+CAMERA_MODEL_KEYS = (FOCAL_X, FOCAL_Y, CENTRE_X, CENTRE_Y, DISTORTION)
+
+
+def camera_from_params(params: Dict[str, Any], first: str) -> CameraIntrinsics:
+    """The one camera of a `<split>_camera_params.json`.  Without the optional keys fx, fy, cx, cy, distortion inside "intrinsic":
+    a plain CameraIntrinsics(height, width, focal) of the entry `first`, as ever.  With them: a PinholeCamera; every entry of the
+    file must then carry the same model and image size (one shared camera per dataset)."""
+    intr = params[first][INTRINSIC]
+    if not any(k in entry[INTRINSIC] for entry in params.values() for k in CAMERA_MODEL_KEYS):
+        return CameraIntrinsics(int(intr[HEIGHT]), int(intr[WIDTH]), float(intr[FOCAL]))
+
+    def model(entry):
+        i = entry[INTRINSIC]
+        focal = i.get(FOCAL)
+        fx = i.get(FOCAL_X, focal)
+        if fx is None:
+            raise ValueError(f'a camera needs "{FOCAL_X}" or "{FOCAL}" in its "{INTRINSIC}" entry')
+        return (int(i[HEIGHT]), int(i[WIDTH]), float(fx), float(i.get(FOCAL_Y, fx)), float(i.get(CENTRE_X, int(i[WIDTH]) * 0.5)),
+                float(i.get(CENTRE_Y, int(i[HEIGHT]) * 0.5)), tuple(float(v) for v in i.get(DISTORTION, ())))
+
+    want = model(params[first])
+    for name, entry in params.items():
+        if model(entry) != want:
+            raise ValueError(f"camera parameters of {name!r} differ from those of {first!r}: per-image intrinsics and mixed image "
+                             f"sizes are not supported (one shared camera per dataset): {model(entry)} != {want}")
+    return PinholeCamera(*want).validate()
+
+
+def camera_to_params(camera: CameraIntrinsics) -> Dict[str, Any]:
+    """the "intrinsic" entry (without bounds) that camera_from_params reads back as `camera`"""
+    out = {HEIGHT: int(camera.height), WIDTH: int(camera.width), FOCAL: float(camera.focal)}
+    if isinstance(camera, PinholeCamera):
+        out.update({FOCAL_X: camera.fx, FOCAL_Y: camera.fy, CENTRE_X: camera.cx, CENTRE_Y: camera.cy,
+                    DISTORTION: list(camera.distortion)})
+    return out
 
 
 class InMemoryPosedImages(Dataset):
@@ -50,7 +88,11 @@ class InMemoryPosedImages(Dataset):
         h, w, f = self.camera_intrinsics
         nh, nw = max(int(h / factor), 1), max(int(w / factor), 1)
         images = F.interpolate(self.images, size=(nh, nw), mode="area")
-        return InMemoryPosedImages(images, self.poses, CameraIntrinsics(nh, nw, f / factor), self.camera_bounds)
+        if isinstance(self.camera_intrinsics, PinholeCamera):
+            small = self.camera_intrinsics.scaled(factor)      # (the same truncated size; fx fy cx cy / factor)
+        else:
+            small = CameraIntrinsics(nh, nw, f / factor)
+        return InMemoryPosedImages(images, self.poses, small, self.camera_bounds)
 
     def to(self, device) -> "InMemoryPosedImages":
         return InMemoryPosedImages(self.images.to(device), self.poses.to(device), self.camera_intrinsics,
@@ -100,8 +142,7 @@ class PosedImagesDataset(InMemoryPosedImages):
             rot = np.array(entry[EXTRINSIC][ROTATION], dtype=np.float32).reshape(3, 3)
             trans = np.array(entry[EXTRINSIC][TRANSLATION], dtype=np.float32).reshape(3, 1) * scale
             poses.append(torch.from_numpy(np.concatenate([rot, trans], axis=1)))
-        first = params[files[0].name]
-        intr = CameraIntrinsics(int(first[INTRINSIC][HEIGHT]), int(first[INTRINSIC][WIDTH]), float(first[INTRINSIC][FOCAL]))
+        intr = camera_from_params(params, files[0].name)
         # bounds over ALL cameras of the file: min(near) * 0.9, max(far) * 1.1 (datasets.py:267-277), then the scene scale
         all_bounds = np.vstack([np.array(entry[INTRINSIC][BOUNDS]).astype(np.float32) for entry in params.values()])
         bounds = CameraBounds(float(all_bounds.min() * 0.9) * scale, float(all_bounds.max() * 1.1) * scale)

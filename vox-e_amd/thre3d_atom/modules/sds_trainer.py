@@ -23,7 +23,7 @@ from thre3d_atom.rendering.volumetric.utils.misc import cast_rays, flatten_rays
 from thre3d_atom.thre3d_reprs.renderers import render_sh_voxel_grid
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid
 from thre3d_atom.utils.constants import CAMERA_BOUNDS, CAMERA_INTRINSICS, HEMISPHERICAL_RADIUS
-from thre3d_atom.utils.imaging_utils import CameraBounds, CameraIntrinsics, CameraPose, get_random_pose, to8b
+from thre3d_atom.utils.imaging_utils import CameraBounds, CameraIntrinsics, CameraPose, PinholeCamera, get_random_pose, to8b
 from thre3d_atom.utils.logging import log
 from voxe_hip import ops as _ops
 
@@ -198,6 +198,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images_and_sds(
 
     log.info(f"SDS editing: grid {grid.grid_dims}, image [{im_h} x {im_w}], {num_iterations} iterations")
     intr = CameraIntrinsics(im_h, im_w, camera_intrinsics.focal * im_w / camera_intrinsics.width)
+    if isinstance(camera_intrinsics, PinholeCamera) and not camera_intrinsics.is_legacy():
+        # the SDS poses are novel views: the dataset's pinhole (fx, fy, cx, cy) at the SDS image size, without its lens
+        sx, sy = im_w / camera_intrinsics.width, im_h / camera_intrinsics.height
+        intr = PinholeCamera(im_h, im_w, camera_intrinsics.fx * sx, camera_intrinsics.fy * sx, camera_intrinsics.cx * sx,
+                             camera_intrinsics.cy * sy)
     trained_time, last = 0.0, time.perf_counter()
     rays_batch, direction_batch, pose, pixels_batch = None, None, None, None
     data_cursor = 0

@@ -17,8 +17,8 @@ from torch import Tensor
 from thre3d_atom.modules.optim import FusedGridAdam, VoxeAdam
 from thre3d_atom.modules.testers import test_sh_vox_grid_vol_mod_with_posed_images
 from thre3d_atom.modules.volumetric_model import VolumetricModel
-from thre3d_atom.rendering.volumetric.utils.misc import sample_random_rays_and_pixels_from_cameras
-from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, write_camera_params
+from thre3d_atom.rendering.volumetric.utils.misc import is_general_camera, sample_random_rays_and_pixels_from_cameras
+from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, LearnedIntrinsics, write_camera_params
 from thre3d_atom.thre3d_reprs.renderers import _render_params, render_sh_voxel_grid
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid, scale_voxel_grid_with_required_output_size
 from thre3d_atom.utils.constants import CAMERA_BOUNDS, CAMERA_INTRINSICS, HEMISPHERICAL_RADIUS
@@ -93,6 +93,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                        # one CameraPoseDeltas over all training cameras, shared across the stages, stepped by a
                                        # second Adam at this rate; the refined poses are saved next to the checkpoints.  0 = off,
                                        # nothing changes.  Above 0 the iteration is not the one-call one either
+    intrinsics_learning_rate: float = 0.0,   # addition of this build: > 0 also learns fx, fy, cx, cy of the shared camera (in
+                                             # full-resolution pixels, scaled to each stage's images) by a second parameter group
+                                             # of the pose optimiser; needs pose_learning_rate > 0.  0 = off, nothing changes
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
@@ -130,14 +133,29 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                 render_diffuse=diffuse).colour for diffuse in (False, True)]
         Image.fromarray(to8b(torch.cat(views, dim=1).cpu().numpy())).save(render_dir / f"default_{step}.png")
 
-    pose_deltas = pose_optimizer = None
+    pose_deltas = pose_optimizer = learned_intrinsics = None
+    if intrinsics_learning_rate > 0.0 and not pose_learning_rate > 0.0:
+        raise ValueError("intrinsics_learning_rate > 0 needs pose_learning_rate > 0 (the intrinsics are a parameter group of the "
+                         "pose optimiser)")
     if pose_learning_rate > 0.0:
         pose_deltas = CameraPoseDeltas(len(train_dataset)).to(device)
-        pose_optimizer = torch.optim.Adam(pose_deltas.parameters(), lr=pose_learning_rate)
+        groups = [{"params": list(pose_deltas.parameters()), "lr": pose_learning_rate}]
+        if intrinsics_learning_rate > 0.0:
+            learned_intrinsics = LearnedIntrinsics(train_dataset.camera_intrinsics)   # (a host parameter)
+            groups.append({"params": list(learned_intrinsics.parameters()), "lr": intrinsics_learning_rate})
+        pose_optimizer = torch.optim.Adam(groups)
 
     def save_refined_poses() -> None:
         refined = pose_deltas.apply(train_dataset.poses.to(device)).detach()
-        write_camera_params(model_dir / "refined_train_camera_params.json", train_dataset, refined)
+        camera = None if learned_intrinsics is None else learned_intrinsics.camera()
+        if camera is not None and hasattr(train_dataset, "get_config_dict"):
+            # (a PosedImagesDataset's file holds the camera of the images on disk, before its own downsample factor)
+            factor = float(train_dataset.get_config_dict().get("downsample_factor", 1.0))
+            if factor != 1.0:
+                first = next(iter(train_dataset.camera_parameters.values()))["intrinsic"]
+                camera = type(camera)(int(first["height"]), int(first["width"]), camera.fx * factor, camera.fy * factor,
+                                      camera.cx * factor, camera.cy * factor, camera.distortion)
+        write_camera_params(model_dir / "refined_train_camera_params.json", train_dataset, refined, camera=camera)
 
     global_step, trained = 0, 0.0
     gen = torch.Generator().manual_seed(torch.initial_seed() % (2 ** 31))
@@ -160,6 +178,14 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
             if one_call and stage == 1:
                 log.info("pose_learning_rate > 0: the iterations cast, render and step separately (no one-call iteration)")
             one_call = False
+        if is_general_camera(intr):
+            # voxe_recon_step casts (height, width, focal) cameras only: fx != fy, an off-centre principal point or a lens model
+            # takes the composed iteration with voxe_cast_rays_camera
+            if one_call and stage == 1:
+                log.info("general camera (fx, fy, cx, cy, distortion): the iterations cast with voxe_cast_rays_camera, render and "
+                         "step separately (no one-call iteration)")
+            one_call = False
+        stage_factor = float(scale_factor ** (num_stages - stage))   # (the factor stage_datasets were downsampled by)
         fused_losses = torch.zeros(4, dtype=torch.float32, device=device)
         log.info(f"stage {stage}: grid {vol_mod.thre3d_repr.grid_dims}, images [{intr.height} x {intr.width}], lr {lr:.4f}")
 
@@ -199,6 +225,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                     if pose_deltas is not None:
                         # (the rays carry the render's gradient back to the deltas of the picked cameras)
                         poses_batch, refine = pose_deltas.apply(poses_batch, picks), {"differentiable": True}
+                        if learned_intrinsics is not None:
+                            refine["intrinsics"] = learned_intrinsics.values / stage_factor
                     rays_batch, pixels_batch = sample_random_rays_and_pixels_from_cameras(
                         intr, poses_batch, data.images, ray_batch_size, image_ids=picks, **refine,
                         # (sorting the batch by (camera, row, column) helps the ray-ordered gather of small batches; batches of

@@ -11,7 +11,7 @@ from torch import Tensor
 
 from thre3d_atom.rendering.volumetric.render_interface import Rays, RenderOut, RenderOutAttn
 from thre3d_atom.utils.constants import NUM_COORD_DIMENSIONS
-from thre3d_atom.utils.imaging_utils import CameraIntrinsics, CameraPose
+from thre3d_atom.utils.imaging_utils import CameraIntrinsics, CameraPose, PinholeCamera
 from voxe_hip import ops as _ops
 
 
@@ -22,9 +22,18 @@ def cast_rays(camera_intrinsics: CameraIntrinsics, pose: CameraPose, device: tor
     rot, trans = pose.rotation, pose.translation
     if not isinstance(rot, Tensor):
         rot, trans = torch.from_numpy(np.asarray(rot)), torch.from_numpy(np.asarray(trans))
-    origins, directions = _ops.cast_rays(height, width, focal, rot, trans, device)
+    if is_general_camera(camera_intrinsics):   # fx != fy, an off-centre principal point or a lens model: voxe_cast_rays_camera
+        pose34 = torch.cat([rot.reshape(3, 3).float(), trans.reshape(3, 1).float()], dim=1)[None].to(device)
+        origins, directions = _ops.cast_rays_camera(camera_intrinsics, pose34)
+    else:
+        origins, directions = _ops.cast_rays(height, width, focal, rot, trans, device)
     shape = (int(height), int(width), NUM_COORD_DIMENSIONS)
     return Rays(origins.view(shape), directions.view(shape), image_shape=(int(height), int(width)))
+
+
+def is_general_camera(camera_intrinsics: CameraIntrinsics) -> bool:
+    """a PinholeCamera that (height, width, focal) does not describe: its rays come from voxe_cast_rays_camera"""
+    return isinstance(camera_intrinsics, PinholeCamera) and not camera_intrinsics.is_legacy()
 
 
 def flatten_rays(rays: Rays) -> Rays:
@@ -76,7 +85,7 @@ def sample_random_rays_and_pixels_synchronously(rays: Rays, pixels: Tensor, samp
 def sample_random_rays_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsics, poses: Tensor, images: Tensor,
                                                sample_size: int, image_ids: Any = None,
                                                memory_order: bool = False, fast_subset: bool = False,
-                                               differentiable: bool = False) -> Tuple[Rays, Tensor]:
+                                               differentiable: bool = False, intrinsics: Any = None) -> Tuple[Rays, Tensor]:
     """What the reconstruction loop keeps of `cast_rays` per camera -> `collate_rays` -> pixel concat ->
     `sample_random_rays_and_pixels_synchronously` (modules/trainers.py:290-313), computed for the selected pixels
     only: the same `randperm` draw picks flat (camera, y, x) indices, the HIP kernel casts just those rays and the
@@ -87,7 +96,9 @@ def sample_random_rays_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsi
     are neighbours in the batch then walk neighbouring voxels, which the forward gather rewards (-25 % at 32768 rays).
     `fast_subset=True` draws the subset with voxe_random_subset (same distribution: a uniformly random set of distinct
     pixels; 0.02 ms instead of 0.20 ms for `randperm` over 1.28 M pixels) -- a different random stream than torch's.
-    `differentiable=True` casts the same rays (bit for bit) through cast_rays_from_poses: they carry gradients back to `poses`."""
+    `differentiable=True` casts the same rays (bit for bit) through cast_rays_from_poses: they carry gradients back to `poses`.
+    A general camera (is_general_camera) casts through cast_rays_camera / cast_rays_from_camera; `intrinsics` (tensor [4] fx fy cx
+    cy, differentiable only) then replaces the camera's own and receives a gradient."""
     height, width, focal = camera_intrinsics
     K = int(poses.shape[0])
     per = int(height) * int(width)
@@ -97,8 +108,14 @@ def sample_random_rays_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsi
         subset = torch.randperm(K * per, dtype=torch.long, device=images.device)[:sample_size]
     if memory_order:
         subset = torch.sort(subset).values
-    cast = _ops.cast_rays_from_poses if differentiable else _ops.cast_rays_indexed
-    origins, directions = cast(height, width, focal, poses, subset)
+    if intrinsics is not None or is_general_camera(camera_intrinsics):
+        if differentiable:
+            origins, directions = _ops.cast_rays_from_camera(camera_intrinsics, poses, subset, intrinsics=intrinsics)
+        else:
+            origins, directions = _ops.cast_rays_camera(camera_intrinsics, poses, subset, intrinsics=intrinsics)
+    else:
+        cast = _ops.cast_rays_from_poses if differentiable else _ops.cast_rays_indexed
+        origins, directions = cast(height, width, focal, poses, subset)
     cam = torch.div(subset, per, rounding_mode="floor")
     rem = subset - cam * per
     rows = cam if image_ids is None else torch.as_tensor(image_ids, device=images.device, dtype=torch.long)[cam]

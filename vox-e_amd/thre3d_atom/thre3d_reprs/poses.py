@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from thre3d_atom.data.constants import BOUNDS, EXTRINSIC, FOCAL, HEIGHT, INTRINSIC, ROTATION, TRANSLATION, WIDTH
+from thre3d_atom.data.constants import BOUNDS, EXTRINSIC, HEIGHT, INTRINSIC, ROTATION, TRANSLATION, WIDTH
 
 
 def _hat(w: Tensor) -> Tensor:
@@ -60,6 +60,28 @@ class CameraPoseDeltas(torch.nn.Module):
     forward = apply
 
 
+class LearnedIntrinsics(torch.nn.Module):
+    """fx, fy, cx, cy of the one shared camera as a parameter [4] (pixels), started at the camera's own; the distortion
+    coefficients stay fixed (learning them is out of scope).  Rays cast by voxe_hip.ops.cast_rays_from_camera(camera, poses,
+    index, intrinsics=self.values) carry the render's gradient back to it (voxe_cast_rays_camera_bwd).  The parameter lives on
+    the HOST: the camera is passed to the kernels by value, so a device tensor would cost a synchronisation per iteration."""
+
+    def __init__(self, camera_intrinsics):
+        super().__init__()
+        from thre3d_atom.utils.imaging_utils import PinholeCamera
+
+        if isinstance(camera_intrinsics, PinholeCamera):
+            self.base = camera_intrinsics
+        else:
+            height, width, focal = camera_intrinsics
+            self.base = PinholeCamera(height, width, focal)
+        self.values = torch.nn.Parameter(torch.tensor([self.base.fx, self.base.fy, self.base.cx, self.base.cy], dtype=torch.float32))
+
+    def camera(self):
+        """the PinholeCamera with the learned intrinsics"""
+        return self.base.with_intrinsics(*(float(v) for v in self.values.detach().cpu()))
+
+
 def rotation_error_degrees(poses: Tensor, reference: Tensor) -> Tensor:
     """[K] angle of R_a R_b^T in degrees, poses [K,3,4] or [K,3,3]"""
     rel = poses[:, :, :3].double() @ reference[:, :, :3].double().transpose(1, 2)
@@ -72,10 +94,13 @@ def translation_error(poses: Tensor, reference: Tensor) -> Tensor:
     return (poses[:, :, 3].double() - reference[:, :, 3].double()).norm(dim=1)
 
 
-def write_camera_params(path, dataset, poses: Tensor) -> Path:
+def write_camera_params(path, dataset, poses: Tensor, camera=None) -> Path:
     """Write `poses` [N,3,4] (the dataset's cameras, in its order) as a `<split>_camera_params.json` PosedImagesDataset reads.
     A PosedImagesDataset keeps its file names and per-image intrinsics; any other dataset gets 0000.png ... and its own
-    intrinsics and bounds."""
+    intrinsics (a PinholeCamera with its whole model) and bounds.  `camera` (a PinholeCamera at the FILE's image size, e.g.
+    refined intrinsics) replaces the camera model of every entry."""
+    from thre3d_atom.data.datasets import CAMERA_MODEL_KEYS, camera_to_params
+
     poses = poses.detach().cpu().double()
     if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4) or poses.shape[0] != len(dataset):
         raise ValueError(f"poses must be [{len(dataset)},3,4]; got {tuple(poses.shape)}")
@@ -90,12 +115,19 @@ def write_camera_params(path, dataset, poses: Tensor) -> Path:
         names = [n for n in files if n in source] or files
         entries = {n: json.loads(json.dumps(source[n])) for n in names}
     else:
-        h, w, f = dataset.camera_intrinsics
         near, far = dataset.camera_bounds
         width = max(4, int(math.log10(max(len(dataset), 1))) + 1)
         names = [f"{i:0{width}d}.png" for i in range(len(dataset))]
-        entries = {n: {EXTRINSIC: {}, INTRINSIC: {HEIGHT: int(h), WIDTH: int(w), FOCAL: float(f), BOUNDS: [float(near), float(far)]}}
+        entries = {n: {EXTRINSIC: {}, INTRINSIC: {**camera_to_params(dataset.camera_intrinsics), BOUNDS: [float(near), float(far)]}}
                    for n in names}
+    if camera is not None:
+        for entry in entries.values():
+            if (int(entry[INTRINSIC][HEIGHT]), int(entry[INTRINSIC][WIDTH])) != (camera.height, camera.width):
+                raise ValueError(f"`camera` is {camera.height} x {camera.width}, the file's images are "
+                                 f"{entry[INTRINSIC][HEIGHT]} x {entry[INTRINSIC][WIDTH]}")
+            for k in CAMERA_MODEL_KEYS:
+                entry[INTRINSIC].pop(k, None)
+            entry[INTRINSIC].update(camera_to_params(camera))
     if len(names) != poses.shape[0]:
         raise ValueError(f"{len(names)} images for {poses.shape[0]} poses")
     for n, pose in zip(names, poses):

@@ -21,7 +21,7 @@ from thre3d_atom.rendering.volumetric.utils.misc import cast_rays, flatten_rays
 from thre3d_atom.thre3d_reprs.renderers import _render_params
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid, density_activation_codes
 from thre3d_atom.utils.constants import CAMERA_INTRINSICS, HEMISPHERICAL_RADIUS
-from thre3d_atom.utils.imaging_utils import CameraIntrinsics, CameraPose, get_thre360_animation_poses
+from thre3d_atom.utils.imaging_utils import CameraIntrinsics, CameraPose, get_thre360_animation_poses, novel_view_camera
 from voxe_hip import abi
 from voxe_hip import ops as _ops
 
@@ -63,7 +63,7 @@ def visibility_cameras(extra_info: Dict[str, Any], data_path: Optional[str] = No
         data = PosedImagesDataset(Path(data_path) / "train", Path(data_path) / "train_camera_params.json", rgba_white_bkgd=True)
         return [CameraPose(p[:, :3], p[:, 3:]) for p in data.poses], data.camera_intrinsics
     return (get_thre360_animation_poses(extra_info[HEMISPHERICAL_RADIUS], camera_pitch, num_views),
-            extra_info[CAMERA_INTRINSICS])
+            novel_view_camera(extra_info[CAMERA_INTRINSICS]))
 
 
 def empty_raw_density(pre_act: int, post_act: int, density_scale: float) -> float:

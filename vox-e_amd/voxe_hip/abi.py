@@ -150,6 +150,15 @@ class VoxeResample(C.Structure):
     ]
 
 
+class VoxeCamera(C.Structure):
+    """one pinhole camera with the OpenCV radial / tangential lens model (include/voxe.h)"""
+    _fields_ = [
+        ("H", C.c_int32), ("W", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float),
+    ]
+
+
 RESAMPLE_REPLACE, RESAMPLE_UNION = 0, 1
 SH_ROT_OFFSETS = (0, 1, 10, 35, 84)   # M_l starts at SH_ROT_OFFSETS[l]
 
@@ -248,6 +257,11 @@ HIP_ONLY = {
     # rigid transform / re-gridding / composition of grids (additive, still ABI v13)
     "grid_resample": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                                 C.POINTER(VoxeResample), _P, _P]),
+    # real-capture cameras: intrinsics + lens distortion (additive, still ABI v13)
+    "cast_rays_camera": (C.c_int, [C.POINTER(VoxeCamera), _P, C.c_int32, _P, C.c_int64, _P, _P, _P]),
+    "cast_rays_camera_bwd_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "cast_rays_camera_bwd": (C.c_int, [C.POINTER(VoxeCamera), _P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                       C.c_size_t, _P]),
 }
 
 CPU_ONLY = {
