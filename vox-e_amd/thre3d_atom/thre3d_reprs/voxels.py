@@ -114,9 +114,11 @@ class VoxelGrid(Module):
     # -- tensors ----------------------------------------------------------------------------------
     def add_attn_params(self, attn: Tensor) -> None:
         self.attn = torch.nn.Parameter(attn)
+        self.invalidate_voxe_caches()
 
     def update_orig_densities(self) -> None:
         self.orig_densities = self._densities.clone().detach()
+        self.invalidate_voxe_caches()
 
     @property
     def densities(self) -> Tensor:
@@ -128,6 +130,7 @@ class VoxelGrid(Module):
             raise AssertionError("new densities don't match original densities tensor's dimensions")
         wrap = self._tunable and not isinstance(densities, torch.nn.Parameter)
         self._densities = torch.nn.Parameter(densities) if wrap else densities
+        self.invalidate_voxe_caches()
 
     @property
     def features(self) -> Tensor:
@@ -139,6 +142,7 @@ class VoxelGrid(Module):
             raise AssertionError("new features don't match original feature tensor's dimensions")
         wrap = self._tunable and not isinstance(features, torch.nn.Parameter)
         self._features = torch.nn.Parameter(features) if wrap else features
+        self.invalidate_voxe_caches()
 
     # -- geometry ---------------------------------------------------------------------------------
     @property
@@ -223,6 +227,15 @@ class VoxelGrid(Module):
         if ws is None:
             ws = self._voxe_workspaces[tag] = _ops.Workspace()
         return ws
+
+    def invalidate_voxe_caches(self) -> None:
+        """Forget what the grid's workspaces hold of its tensors (the packed grid, the ray states of the last forward): the
+        next render or query packs the current values.  The renderer notices every write torch counts (in-place ops,
+        `copy_`, optimiser steps, `load_state_dict`, the in-place entry points of voxe_hip) and every replaced tensor by
+        itself; call this after a write it cannot see -- through `tensor.data`, by another library's kernel on the raw
+        pointer, through a DLPack / `__cuda_array_interface__` view ("Writes torch cannot see")."""
+        for ws in self._voxe_workspaces.values():
+            ws.invalidate()
 
     def __deepcopy__(self, memo):
         import copy

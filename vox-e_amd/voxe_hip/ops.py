@@ -3,6 +3,7 @@ the whole-grid passes.  Tensors are plumbing (device memory + streams); all comp
 library.  Nothing here falls back to torch ops or to the CPU oracle."""
 import ctypes as C
 import dataclasses
+import weakref
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -61,8 +62,13 @@ class Workspace:
 
     def __init__(self):
         self.buf: Optional[torch.Tensor] = None
-        self.key = None        # which grid values are packed in the buffer
+        self.key = None        # which grid values are packed in the buffer (_pack_key of the SOURCE tensors)
         self.state_key = None  # which forward call's per-ray depth-segment states it holds
+        # weak references to the storages behind the two keys.  An address and a version counter name a tensor's values only
+        # while its storage lives: a freed block goes back to the caching allocator, and the next tensor of that size gets the
+        # same data_ptr with a fresh counter at the same value.  A dead reference therefore ends the key it belongs to.
+        self._sources = ()
+        self._state_sources = ()
         # A differentiable forward leaves its per-ray states here for its backward.  When a second differentiable
         # forward arrives before that backward (two renders in one loss: specular + diffuse), it runs in `sibling`
         # (own buffers) instead of overwriting the states -- otherwise the first backward must re-march its rays.
@@ -121,8 +127,42 @@ class Workspace:
         return self.buf
 
     def invalidate(self):
+        """forget what the buffer holds: the next call packs the grid and marches its rays again.  For writes that neither
+        torch's version counters nor this module can see (`tensor.data`, another library's kernel, a DLPack view)."""
         self.key = None
         self.state_key = None
+        if self.sibling is not None:
+            self.sibling.invalidate()
+
+    def holds(self, spec: "GridSpec", densities: torch.Tensor, features: torch.Tensor) -> bool:
+        """THE decision "skip the pack pass": does the buffer hold the values of these grid tensors, packed for `spec`?
+        `densities` / `features` are the caller's tensors, BEFORE any conversion to dense float32 (the converted copy is a
+        temporary whose address and version say nothing about the source)."""
+        if self.key is None:
+            return False
+        if not _alive(self._sources):
+            self.key = self.state_key = None
+            return False
+        return self.key == _pack_key(spec, densities, features)
+
+    def remember(self, spec: "GridSpec", densities: torch.Tensor, features: torch.Tensor) -> None:
+        """the buffer now holds these (source) tensors' values packed for `spec`"""
+        self.key = _pack_key(spec, densities, features)
+        self._sources = (_storage_ref(densities), _storage_ref(features))
+
+    def holds_states(self, state_key) -> bool:
+        """THE decision "ray_state_valid = 1": does the buffer hold the per-ray states of exactly the forward `state_key`
+        (_state_key) describes, marched through the packed grid it still holds?"""
+        if self.state_key is None:
+            return False
+        if not (_alive(self._sources) and _alive(self._state_sources)):
+            self.state_key = None
+            return False
+        return self.state_key == state_key
+
+    def remember_states(self, state_key, rays_o, rays_d, jitter) -> None:
+        self.state_key = state_key
+        self._state_sources = tuple(_storage_ref(t) for t in (rays_o, rays_d, jitter) if t is not None)
 
 
 def _render_ws_bytes(L, g, c, R) -> int:
@@ -131,9 +171,24 @@ def _render_ws_bytes(L, g, c, R) -> int:
     return L.voxe_workspace_bytes(C.byref(g), C.byref(c), R) + L.voxe_tile_plan_bytes(C.byref(g), C.byref(c), R)
 
 
+def _storage_ref(t: torch.Tensor):
+    return weakref.ref(t.untyped_storage())
+
+
+def _alive(refs) -> bool:
+    for r in refs:
+        if r() is None:
+            return False
+    return True
+
+
 def _pack_key(spec: GridSpec, densities: torch.Tensor, features: torch.Tensor):
+    """which values a packed grid holds -- of the caller's tensors as they are (any dtype, any strides).  Complete only together
+    with Workspace._sources: equal addresses and versions mean equal values while the storages behind them are alive.
+    (density_post_act is applied per sample, not by the pack: not part of the key.)"""
     return (densities.data_ptr(), densities._version, features.data_ptr(), features._version,
-            tuple(features.shape), spec.density_scale, spec.density_pre_act, spec.feature_kind)
+            tuple(features.shape), spec.density_scale, spec.density_pre_act, spec.feature_kind,
+            densities.dtype, densities.stride(), features.dtype, features.stride())
 
 
 def _state_key(pack_key, params: RenderParams, rays_o, rays_d, jitter, rng, route=None):
@@ -142,8 +197,9 @@ def _state_key(pack_key, params: RenderParams, rays_o, rays_d, jitter, rng, rout
     tables, and the choice also depends on process-level tuning switches that may change between the two calls)"""
     fwd = tuple((k, v) for k, v in vars(params).items() if k not in ("linear_grad", "deterministic", "dispatch"))   # backward-only knobs
     fwd += (("dispatch", params.dispatch if params.dispatch is not None else _dispatch.current()),)
-    return (pack_key, fwd, rays_o.data_ptr(), rays_d.data_ptr(), rays_o.shape[0],
-            None if jitter is None else jitter.data_ptr(), tuple(rng), route)
+    # (the rays' and the jitter's version counters too: the trainers reuse their ray buffers, rewriting them in place)
+    return (pack_key, fwd, rays_o.data_ptr(), rays_o._version, rays_d.data_ptr(), rays_d._version, rays_o.shape[0],
+            None if jitter is None else (jitter.data_ptr(), jitter._version), tuple(rng), route)
 
 
 def _route(g, c, R) -> int:
@@ -183,45 +239,52 @@ def _next_rng():
 
 
 def render_fwd_into(spec: GridSpec, params: RenderParams, densities, features, rays_o, rays_d, jitter,
-                    colour, depth, acc, disparity, workspace: Workspace, rng=(0, 0), keep_for_backward: bool = True) -> None:
+                    colour, depth, acc, disparity, workspace: Workspace, rng=(0, 0), keep_for_backward: bool = True,
+                    source=None) -> None:
     """voxe_render_fwd on caller-provided output tensors (contiguous float32 on one device, no autograd).
     keep_for_backward=False (inference): the forward skips what only a backward of the same rays would read (the per-sample
-    values of view-dependent grids); a later backward on this workspace re-marches."""
+    values of view-dependent grids); a later backward on this workspace re-marches.
+    `source` = (densities, features) as the caller holds them, when `densities` / `features` are dense float32 conversions of
+    those: the packed-grid cache is keyed on the source, never on a temporary."""
     device = densities.device
     ensure_gfx950(device)
     L = lib()
     R = rays_o.shape[0]
-    key = _pack_key(spec, densities, features)
-    g, c = _descs(spec, params, densities, features, rng[0], rng[1], workspace.key == key)
+    src_d, src_f = source if source is not None else (densities, features)
+    g, c = _descs(spec, params, densities, features, rng[0], rng[1], False)
     with torch.cuda.device(device):
         c.ray_state_valid = 0 if keep_for_backward else -1     # (-1: the size query leaves out everything only a backward reads)
         ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
-        c.reuse_packed_grid = int(workspace.key == key)
+        c.reuse_packed_grid = int(workspace.holds(spec, src_d, src_f))
         check(L.voxe_render_fwd(C.byref(g), C.byref(c), ptr(rays_o), ptr(rays_d), R, ptr(jitter), ptr(colour),
                                 ptr(depth), ptr(acc), ptr(disparity), ptr(ws), ws.numel(),
                                 stream_ptr(device)), "voxe_render_fwd")
-    workspace.key = key
-    workspace.state_key = _state_key(key, params, rays_o, rays_d, jitter, rng, _route(g, c, R)) if keep_for_backward else None
+    workspace.remember(spec, src_d, src_f)
+    if keep_for_backward:
+        workspace.remember_states(_state_key(workspace.key, params, rays_o, rays_d, jitter, rng, _route(g, c, R)), rays_o, rays_d, jitter)
+    else:
+        workspace.state_key = None
 
 
 def render_bwd_into(spec: GridSpec, params: RenderParams, densities, features, rays_o, rays_d, jitter,
                     colour, depth, acc, g_colour, g_depth, g_acc, d_densities, d_features,
-                    workspace: Workspace, rng=(0, 0), accumulate: bool = False) -> None:
-    """voxe_render_bwd into caller-provided gradient tensors (either may be None to skip it)."""
+                    workspace: Workspace, rng=(0, 0), accumulate: bool = False, source=None) -> None:
+    """voxe_render_bwd into caller-provided gradient tensors (either may be None to skip it).  `source`: as in render_fwd_into."""
     device = densities.device
     L = lib()
     R = rays_o.shape[0]
-    key = _pack_key(spec, densities, features)
-    g, c = _descs(spec, params, densities, features, rng[0], rng[1], workspace.key == key)
+    src_d, src_f = source if source is not None else (densities, features)
+    key = _pack_key(spec, src_d, src_f)
+    g, c = _descs(spec, params, densities, features, rng[0], rng[1], False)
     with torch.cuda.device(device):
         ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
-        c.reuse_packed_grid = int(workspace.key == key)
-        c.ray_state_valid = int(workspace.state_key == _state_key(key, params, rays_o, rays_d, jitter, rng, _route(g, c, R)))
+        c.reuse_packed_grid = int(workspace.holds(spec, src_d, src_f))
+        c.ray_state_valid = int(workspace.holds_states(_state_key(key, params, rays_o, rays_d, jitter, rng, _route(g, c, R))))
         check(L.voxe_render_bwd(C.byref(g), C.byref(c), ptr(rays_o), ptr(rays_d), R, ptr(jitter), ptr(colour),
                                 ptr(depth), ptr(acc), ptr(g_colour), ptr(g_depth), ptr(g_acc),
                                 ptr(d_densities), ptr(d_features), int(accumulate), ptr(ws), ws.numel(),
                                 stream_ptr(device)), "voxe_render_bwd")
-    workspace.key = key
+    workspace.remember(spec, src_d, src_f)
 
 
 class _RenderFn(torch.autograd.Function):
@@ -247,7 +310,7 @@ class _RenderFn(torch.autograd.Function):
             workspace = workspace.for_differentiable_forward(version)
             workspace.pending, workspace.pending_version = True, version
         render_fwd_into(spec, params, dens, feat, ro, rd, jit, colour, depth, acc, disp, workspace, rng,
-                        keep_for_backward=bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
+                        keep_for_backward=bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1]), source=(densities, features))
         ctx.spec, ctx.params, ctx.workspace, ctx.rng = spec, params, workspace, rng
         ctx.save_for_backward(densities, features, ro, rd, jit, colour, depth, acc)
         return colour, depth, acc, disp
@@ -304,7 +367,7 @@ class _RenderFn(torch.autograd.Function):
                                     want_densities=bool(need_d and deferred.want_densities),
                                     want_features=bool(need_f and deferred.want_features),
                                     grad_workspace=(main if workspace is not main else None),
-                                    expect_layout=deferred.layout if deferred.dirty else abi.GRAD_ANY)
+                                    expect_layout=deferred.layout if deferred.dirty else abi.GRAD_ANY, source=(densities, features))
             if layout is not None:
                 deferred.clean_ptr = main.buf.data_ptr()
                 if layout != abi.GRAD_ANY:
@@ -322,7 +385,7 @@ class _RenderFn(torch.autograd.Function):
         d_dens = torch.empty_like(dens) if need_d else None
         d_feat = torch.empty_like(feat) if need_f else None
         render_bwd_into(spec, params, dens, feat, ro, rd, jit, colour, depth, acc, g_colour, g_depth, g_acc,
-                        d_dens, d_feat, workspace, ctx.rng)
+                        d_dens, d_feat, workspace, ctx.rng, source=(densities, features))
         workspace.pending = False
         return d_dens, d_feat
 
@@ -379,14 +442,14 @@ class _QueryFn(torch.autograd.Function):
         L = lib()
         dens, feat, pts = f32c(densities.detach()), f32c(features.detach()), f32c(points.detach())
         N, F = pts.shape[0], feat.shape[-1]
-        key = _pack_key(spec, dens, feat)
         g, _ = _descs(spec, RenderParams(1, 0.0, 1.0), dens, feat, 0, 0, False)
         with torch.cuda.device(device):
             ws = workspace.ensure(L.voxe_workspace_bytes(C.byref(g), None, 0), device)
             out = torch.empty((N, F + 1), dtype=torch.float32, device=device)
-            check(L.voxe_query_fwd(C.byref(g), ptr(pts), N, ptr(out), int(workspace.key == key), ptr(ws), ws.numel(),
-                                   stream_ptr(device)), "voxe_query_fwd")
-        workspace.key = key
+            # (keyed on the caller's tensors: `dens` / `feat` may be temporaries of the conversion above)
+            check(L.voxe_query_fwd(C.byref(g), ptr(pts), N, ptr(out), int(workspace.holds(spec, densities, features)), ptr(ws),
+                                   ws.numel(), stream_ptr(device)), "voxe_query_fwd")
+        workspace.remember(spec, densities, features)
         ctx.spec, ctx.workspace = spec, workspace
         ctx.save_for_backward(densities, features, pts)
         return out
@@ -400,16 +463,15 @@ class _QueryFn(torch.autograd.Function):
         device = densities.device
         L = lib()
         dens, feat = f32c(densities.detach()), f32c(features.detach())
-        key = _pack_key(ctx.spec, dens, feat)
         g, _ = _descs(ctx.spec, RenderParams(1, 0.0, 1.0), dens, feat, 0, 0, False)
         with torch.cuda.device(device):
             ws = ctx.workspace.ensure(L.voxe_workspace_bytes(C.byref(g), None, 0), device)
             d_dens = torch.empty_like(dens) if need_d else None
             d_feat = torch.empty_like(feat) if need_f else None
             check(L.voxe_query_bwd(C.byref(g), ptr(pts), pts.shape[0], ptr(f32c(g_out)), ptr(d_dens), ptr(d_feat), 0,
-                                   int(ctx.workspace.key == key), ptr(ws), ws.numel(), stream_ptr(device)),
-                  "voxe_query_bwd")
-        ctx.workspace.key = key
+                                   int(ctx.workspace.holds(ctx.spec, densities, features)), ptr(ws), ws.numel(),
+                                   stream_ptr(device)), "voxe_query_bwd")
+        ctx.workspace.remember(ctx.spec, densities, features)
         ctx.workspace.state_key = None  # the gradient region of the workspace was reused
         return d_dens, d_feat, None, None, None
 
@@ -653,30 +715,32 @@ def adam_step_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, e
 def render_bwd_acc(spec: GridSpec, params: RenderParams, densities, features, rays_o, rays_d, jitter,
                    colour, depth, acc, g_colour, g_depth, g_acc, workspace: Workspace, rng=(0, 0),
                    zero_first: bool = True, want_densities: bool = True, want_features: bool = True,
-                   grad_workspace: Optional[Workspace] = None, expect_layout: int = abi.GRAD_ANY) -> Optional[int]:
+                   grad_workspace: Optional[Workspace] = None, expect_layout: int = abi.GRAD_ANY, source=None) -> Optional[int]:
     """voxe_render_bwd_acc(_into): the backward of one render, its gradient LEFT in the workspace (kernel layout) for
     `grid_adam_step_` -- in `grad_workspace`'s gradient region when given (a second render of the same step that ran in
     its own workspace).  Returns the layout (abi.GRAD_*); renders accumulated into one step must agree on it:
-    with `expect_layout` set, a render whose kernel writes the other layout is NOT run and None is returned."""
+    with `expect_layout` set, a render whose kernel writes the other layout is NOT run and None is returned.
+    `source`: as in render_fwd_into."""
     device = densities.device
     L = lib()
     R = rays_o.shape[0]
-    key = _pack_key(spec, densities, features)
-    g, c = _descs(spec, params, densities, features, rng[0], rng[1], workspace.key == key)
+    src_d, src_f = source if source is not None else (densities, features)
+    key = _pack_key(spec, src_d, src_f)
+    g, c = _descs(spec, params, densities, features, rng[0], rng[1], False)
     layout = C.c_int32(abi.GRAD_ANY)
     if expect_layout != abi.GRAD_ANY and R > 0 and expect_layout != predicted_grad_layout(spec, params, densities, features, R):
         return None
     with torch.cuda.device(device):
         ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
-        c.reuse_packed_grid = int(workspace.key == key)
-        c.ray_state_valid = int(workspace.state_key == _state_key(key, params, rays_o, rays_d, jitter, rng, _route(g, c, R)))
+        c.reuse_packed_grid = int(workspace.holds(spec, src_d, src_f))
+        c.ray_state_valid = int(workspace.holds_states(_state_key(key, params, rays_o, rays_d, jitter, rng, _route(g, c, R))))
         gws = None if grad_workspace is None else grad_workspace.buf
         check(L.voxe_render_bwd_acc_into(C.byref(g), C.byref(c), ptr(rays_o), ptr(rays_d), R, ptr(jitter), ptr(colour),
                                          ptr(depth), ptr(acc), ptr(g_colour), ptr(g_depth), ptr(g_acc),
                                          int(want_densities), int(want_features), int(zero_first), C.byref(layout),
                                          ptr(ws), ws.numel(), ptr(gws), 0 if gws is None else gws.numel(),
                                          stream_ptr(device)), "voxe_render_bwd_acc_into")
-    workspace.key = key
+    workspace.remember(spec, src_d, src_f)
     return int(layout.value)
 
 
@@ -773,7 +837,7 @@ def grid_adam_step_(spec: GridSpec, densities, features, grad_layout: int, works
     for t in (densities if m_d is not None else None, features if m_f is not None else None, m_d, v_d, m_f, v_f):
         if t is not None:
             torch.autograd.graph.increment_version(t)
-    workspace.key = _pack_key(spec, densities, features)   # the workspace holds the updated grid packed
+    workspace.remember(spec, densities, features)          # the workspace holds the updated grid packed
     workspace.state_key = None
 
 
@@ -822,8 +886,16 @@ def attn_refine_step_(spec: GridSpec, params: RenderParams, densities, attn, ray
             raise VoxeError(f"attn_refine_step_: {nm} must be contiguous float32 with {n} elements on the device")
     ensure_gfx950(device)      # (behind the tensor checks: CPU tensors are refused with a VoxeError, GPU or not)
     L = lib()
-    key = _pack_key(spec, densities, attn)
-    g, c = _descs(spec, params, densities, attn, rng[0], rng[1], workspace.key == key)
+    if losses is None and tv_weight != 0.0:
+        # the TV pass writes its loss value wherever it runs, and it runs for the gradient whenever tv_weight != 0: the library
+        # is never handed NULL there (a null store on the device otherwise); the values go to a scratch pair nobody reads
+        losses = workspace.recon_scratch.get("refine_losses")
+        if losses is None or losses.device != device:
+            losses = workspace.recon_scratch["refine_losses"] = torch.empty(2, dtype=torch.float32, device=device)
+        # (`tv_loss_always` asks for the TV VALUE when tv_weight == 0; nobody reads the value here, and tv_weight != 0 runs the
+        #  pass anyway: off, so that the flag never becomes the reason for a launch)
+        tv_loss_always = False
+    g, c = _descs(spec, params, densities, attn, rng[0], rng[1], False)
     rs = abi.VoxeAttnRefineStep()
     rs.attn_map, rs.tv_weight, rs.tv_loss_always = ptr(attn_map), float(tv_weight), int(bool(tv_loss_always))
     rs.lr, rs.beta1, rs.beta2, rs.eps, rs.step = float(lr), float(beta1), float(beta2), float(eps), int(step)
@@ -834,7 +906,7 @@ def attn_refine_step_(spec: GridSpec, params: RenderParams, densities, attn, ray
         ws = workspace.ensure(_render_ws_bytes(L, g, c, R), device)
         # (a buffer this call allocated holds whatever torch.empty returned in its gradient region)
         rs.zero_gradient_first = int(bool(zero_gradient_first) or ws is not had)
-        c.reuse_packed_grid = int(workspace.key == key)
+        c.reuse_packed_grid = int(workspace.holds(spec, densities, attn))
         need = L.voxe_attn_refine_scratch_bytes(C.byref(g), R)
         sc = workspace.recon_scratch.get("refine")
         if sc is None or sc.numel() < need or sc.device != ws.device:
@@ -843,7 +915,7 @@ def attn_refine_step_(spec: GridSpec, params: RenderParams, densities, attn, ray
                                       ptr(sc), sc.numel(), stream_ptr(device)), "voxe_attn_refine_step")
     for t in (attn, state[0], state[1]):
         torch.autograd.graph.increment_version(t)
-    workspace.key = _pack_key(spec, densities, attn)       # the workspace holds the updated grid packed
+    workspace.remember(spec, densities, attn)              # the workspace holds the updated grid packed
     workspace.state_key = None
 
 
@@ -868,9 +940,8 @@ def _recon_call(entry: str, spec: GridSpec, params: RenderParams, densities, fea
     if image_rows is not None and (image_rows.dtype != torch.int64 or image_rows.numel() != poses.shape[0] or not image_rows.is_cuda):
         raise VoxeError(f"{entry}: image_rows must be int64 [K] on the device")
     L = lib()
-    key = _pack_key(spec, densities, features)
     p = dataclasses.replace(params, linear_grad=True, image_width=0, image_height=0)
-    g, c = _descs(spec, p, densities, features, rng[0], rng[1], workspace.key == key)
+    g, c = _descs(spec, p, densities, features, rng[0], rng[1], False)
     rs = abi.VoxeReconStep()
     rs.H, rs.W, rs.focal = int(height), int(width), float(focal)
     rs.poses, rs.images, rs.image_rows = ptr(poses), ptr(images), ptr(image_rows)
@@ -893,7 +964,7 @@ def _recon_call(entry: str, spec: GridSpec, params: RenderParams, densities, fea
         ws = workspace.ensure(nbytes, device)
         # (a buffer this call allocated holds whatever torch.empty returned in its gradient region)
         rs.zero_gradient_first = int(bool(zero_gradient_first) or ws is not had)
-        c.reuse_packed_grid = int(workspace.key == key)
+        c.reuse_packed_grid = int(workspace.holds(spec, densities, features))
         ws2 = None
         if diffuse_regularisation:
             # the second workspace runs the DIFFUSE render: for view-dependent grids that render may take another route (and
@@ -948,7 +1019,7 @@ def recon_step_(spec: GridSpec, params: RenderParams, densities, features, works
         c = type(c0).from_buffer_copy(c0)
         rs = type(rs0).from_buffer_copy(rs0)
         c.seed, c.rng_offset = int(rng[0]) & 0xFFFFFFFFFFFFFFFF, int(rng[1]) & 0xFFFFFFFFFFFFFFFF
-        c.reuse_packed_grid = int(workspace.key == _pack_key(spec, densities, features))
+        c.reuse_packed_grid = int(workspace.holds(spec, densities, features))
         rs.poses, rs.image_rows = ptr(poses), ptr(image_rows)
         rs.lr, rs.beta1, rs.beta2, rs.eps = float(lr), float(beta1), float(beta2), float(eps)
         rs.step_densities, rs.step_features = int(step_densities), int(step_features)
@@ -974,7 +1045,7 @@ def recon_step_(spec: GridSpec, params: RenderParams, densities, features, works
     for t in (densities, features, m_d, v_d, m_f, v_f):
         if t is not None:
             torch.autograd.graph.increment_version(t)
-    workspace.key = _pack_key(spec, densities, features)   # the workspace holds the updated grid packed
+    workspace.remember(spec, densities, features)          # the workspace holds the updated grid packed
     workspace.state_key = None
     workspace2.key = None                                  # (its packed grid is the previous iteration's)
     workspace2.state_key = None
@@ -1409,6 +1480,11 @@ def grid_resample(src_densities: Optional[torch.Tensor], src_features: Optional[
         taken = torch.empty(dims2, dtype=torch.uint8, device=device) if want_taken else None
         check(lib().voxe_grid_resample(ptr(sd), ptr(sf), X, Y, Z, Cn, ptr(dd), ptr(df), *dims2, C.byref(xf), ptr(taken),
                                        stream_ptr(device)), "voxe_grid_resample")
+    if union:
+        # the library wrote the destination through raw pointers: tell autograd and the packed-grid caches
+        for t in (dd, df):
+            if t is not None:
+                torch.autograd.graph.increment_version(t)
     return dd, df, taken
 
 
