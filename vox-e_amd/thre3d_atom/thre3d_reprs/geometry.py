@@ -48,7 +48,7 @@ def render_geometry(vol_mod, camera_pose: CameraPose, camera_intrinsics: CameraI
     rays = flatten_rays(cast_rays(camera_intrinsics, camera_pose, device=vol_mod.device))
     params = _render_params(grid, rays, config, attn=False)
     spec = grid.voxe_grid_spec(attn=False)
-    rng = _ops._next_rng() if params.perturb else (0, 0)
+    rng = _ops.resolve_rng(params, None, None)
     with torch.no_grad():
         colour, _, _, _ = _ops.render(spec, params, grid.densities, grid.features, rays.origins, rays.directions,
                                       workspace=grid.voxe_workspace("sh"), rng=rng)

@@ -1,0 +1,182 @@
+"""Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss on rays) and Adam
+on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+
+from . import abi
+from .args import GridSpec, RenderParams, _check_rays, _require_buffer, resolve_rng
+from .gridops import _check_densities, _sampling_inputs
+from .runtime import VoxeError, check, ensure_gfx950, f32c, lib, ptr, require_device, stream_ptr
+from .workspace import _scratch_for, wrote
+
+
+class _ScalarLossFn(torch.autograd.Function):
+    """loss = entry(x[, other]) by one library call that writes the value and -- for an upstream gradient of 1.0, scaled in the
+    backward -- the gradient w.r.t. `x` in one launch sequence.  `plan(x, other)` (both dense float32) checks the shapes and
+    returns ((scratch-size query, its arguments), the call's leading arguments)."""
+
+    @staticmethod
+    def forward(ctx, x, other, entry, symbol, plan):
+        require_device(x, entry)
+        a = f32c(x.detach())
+        b = None if other is None else f32c(other.detach())
+        (scratch_query, scratch_args), lead = plan(a, b)
+        device = a.device
+        ensure_gfx950(device)
+        L = lib()
+        with torch.cuda.device(device):
+            sc = _scratch_for(device, getattr(L, scratch_query)(*scratch_args))
+            loss = torch.empty((), dtype=torch.float32, device=device)
+            d_a = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+            check(getattr(L, symbol)(*lead, 1.0, ptr(loss), ptr(d_a), 0, ptr(sc), sc.numel(), stream_ptr(device)), symbol)
+        ctx.save_for_backward(d_a)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (d_a,) = ctx.saved_tensors
+        return (None if d_a is None else d_a * g), None, None, None, None
+
+
+def density_correlation_loss(sds_density: torch.Tensor, regular_density: torch.Tensor) -> torch.Tensor:
+    """1 - corr(sds, regular)  (thre3d_atom/modules/sds_trainer.py:507-524); differentiable w.r.t. sds."""
+    def plan(a, b):
+        if a.numel() != b.numel():
+            raise VoxeError("density_correlation_loss: shape mismatch")
+        return ("voxe_dcl_scratch_bytes", (a.numel(),)), (ptr(a), ptr(b), a.numel())
+    return _ScalarLossFn.apply(sds_density, regular_density, "density_correlation_loss", "voxe_dcl_fwd_bwd", plan)
+
+
+def density_diff_loss(sds_density: torch.Tensor, regular_density: torch.Tensor, l2_mode: bool) -> torch.Tensor:
+    """mse_loss (l2_mode) / l1_loss of the two density grids (thre3d_atom/modules/sds_trainer.py:494-503); differentiable w.r.t. sds."""
+    kind = abi.DREG_L2 if l2_mode else abi.DREG_L1
+
+    def plan(a, b):
+        if a.numel() != b.numel():
+            raise VoxeError("density_diff_loss: shape mismatch")
+        return ("voxe_dcl_scratch_bytes", (a.numel(),)), (ptr(a), ptr(b), a.numel(), int(kind))
+    return _ScalarLossFn.apply(sds_density, regular_density, "density_diff_loss", "voxe_density_diff_fwd_bwd", plan)
+
+
+def feature_correlation_loss(sds_features: torch.Tensor, regular_features: torch.Tensor) -> torch.Tensor:
+    """sum_v (sum_c sigmoid(f_vc) - sigmoid(r_vc))^2 (thre3d_atom/modules/sds_trainer.py:526-534); differentiable w.r.t. sds."""
+    def plan(f, r):
+        if f.shape != r.shape or f.dim() < 1:
+            raise VoxeError("feature_correlation_loss: shape mismatch")
+        F = int(f.shape[-1])
+        nvox = f.numel() // F
+        return ("voxe_dcl_scratch_bytes", (nvox,)), (ptr(f), ptr(r), nvox, F)
+    return _ScalarLossFn.apply(sds_features, regular_features, "feature_correlation_loss", "voxe_feature_correlation_fwd_bwd", plan)
+
+
+def tv_loss_on_grid(grid: torch.Tensor) -> torch.Tensor:
+    """(mean|dx| + mean|dy| + mean|dz|)/3  (thre3d_atom/modules/sds_trainer.py:563-567)."""
+    def plan(gr, _):
+        if gr.dim() != 4:
+            raise VoxeError("tv_loss_on_grid expects [X,Y,Z,C]")
+        return ("voxe_tv_scratch_bytes", tuple(gr.shape)), (ptr(gr), *gr.shape)
+    return _ScalarLossFn.apply(grid, None, "tv_loss_on_grid", "voxe_tv_fwd_bwd", plan)
+
+
+@torch.no_grad()
+def adam_step_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+               step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
+    """In-place torch.optim.Adam update of one tensor (weight_decay=0, amsgrad=False)."""
+    for name, t in (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        _require_buffer("adam_step_", name, t, numel=param.numel())
+    device = param.device
+    ensure_gfx950(device)
+    with torch.cuda.device(device):
+        check(lib().voxe_adam_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(),
+                                   float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                   stream_ptr(device)), "voxe_adam_step")
+    wrote(param, exp_avg, exp_avg_sq)
+
+
+@torch.no_grad()
+def attn_masked_l1(render: torch.Tensor, attn_map: torch.Tensor):
+    """voxe_attn_masked_l1: calc_loss_on_attn_grid (modules/refinement_functions.py:42-77) and its gradient w.r.t. the render.
+    Returns (loss [scalar tensor], d_render like `render`)."""
+    require_device(render, "attn_masked_l1 (render)")
+    require_device(attn_map, "attn_masked_l1 (attn_map)")
+    r, m = f32c(render.detach()).reshape(-1), f32c(attn_map.detach()).reshape(-1)
+    if r.numel() != m.numel():
+        raise VoxeError(f"attn_masked_l1: render ({r.numel()}) and map ({m.numel()}) differ in size")
+    device = r.device
+    ensure_gfx950(device)
+    L = lib()
+    d_r = torch.empty_like(r)
+    loss = torch.zeros((), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        sc = _scratch_for(device, L.voxe_attn_masked_l1_scratch_bytes())
+        check(L.voxe_attn_masked_l1(ptr(r), ptr(m), r.numel(), ptr(d_r), ptr(loss), ptr(sc), sc.numel(), stream_ptr(device)),
+              "voxe_attn_masked_l1")
+    return loss, d_r.reshape(render.shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# distortion loss on rays (DESIGN.md section 4 "Distortion"): reads the raw densities only, no workspace; differentiable w.r.t.
+# the densities
+# ------------------------------------------------------------------------------------------------
+def distortion_fwd_bwd(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                       jitter: Optional[torch.Tensor] = None, rng: Tuple[int, int] = (0, 0), grad_scale: float = 1.0,
+                       want_loss: bool = True, want_ray_loss: bool = False, d_densities: Optional[torch.Tensor] = None,
+                       accumulate: bool = False, lanes: int = 0):
+    """voxe_distortion_fwd_bwd as it stands: (loss [] or None, ray_loss [R] or None); `d_densities` (contiguous float32 of the
+    densities' shape, or None) receives grad_scale * dloss/draw, added to its contents when `accumulate`.  `lanes` (test aid):
+    1 / 2 / 4 / 8 pins the kernel's lanes per ray for this call, 0 = chosen by R."""
+    _check_densities(densities, "distortion_loss")
+    _check_rays("distortion_loss", rays_o, rays_d, jitter, params.num_samples)
+    device = densities.device
+    if d_densities is not None:
+        _require_buffer("distortion_loss", "d_densities", d_densities, shape=densities.shape, device=device)
+    g, c, dens, ro, rd, jit = _sampling_inputs(spec, params, densities, rays_o, rays_d, jitter, rng)
+    R = ro.shape[0]
+    L = lib()
+    with torch.cuda.device(device):
+        loss = torch.zeros((), dtype=torch.float32, device=device) if want_loss else None
+        ray_loss = torch.empty((R,), dtype=torch.float32, device=device) if want_ray_loss else None
+        sc = _scratch_for(device, L.voxe_distortion_scratch_bytes(R)) if want_loss else None
+        if lanes:
+            check(L.voxe_distortion_debug_lanes(int(lanes)), "voxe_distortion_debug_lanes")
+        try:
+            check(L.voxe_distortion_fwd_bwd(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), float(grad_scale), ptr(loss),
+                                            ptr(ray_loss), ptr(d_densities), 1 if accumulate else 0, ptr(sc),
+                                            sc.numel() if sc is not None else 0, stream_ptr(device)), "voxe_distortion_fwd_bwd")
+        finally:
+            if lanes:
+                L.voxe_distortion_debug_lanes(0)
+    wrote(d_densities)
+    return loss, ray_loss
+
+
+class _DistortionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, densities, spec, params, rays_o, rays_d, jitter, rng, return_ray_loss, lanes):
+        d_d = torch.empty_like(f32c(densities.detach())) if ctx.needs_input_grad[0] else None
+        loss, ray_loss = distortion_fwd_bwd(spec, params, densities, rays_o, rays_d, jitter, rng, want_ray_loss=return_ray_loss,
+                                            d_densities=d_d, lanes=lanes)
+        ctx.save_for_backward(d_d)
+        if return_ray_loss:
+            ctx.mark_non_differentiable(ray_loss)
+            return loss, ray_loss
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (d_d,) = ctx.saved_tensors
+        return (None if d_d is None else d_d * g,) + (None,) * 8
+
+
+def distortion_loss(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                    jitter: Optional[torch.Tensor] = None, rng: Optional[Tuple[int, int]] = None, return_ray_loss: bool = False,
+                    _lanes: int = 0):
+    """Distortion loss of flat rays (mip-NeRF 360; DVGOv2's O(S) evaluation): the mean over rays of
+    L_r = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i on depths normalised by params.near / params.far, with the samples
+    and weights `render` uses for the same params, jitter and rng (`rng` follows render's rule: None = a fresh stream when
+    params.perturb and no jitter is given).  A scalar tensor, differentiable w.r.t. `densities` (the gradient is computed in the
+    forward, only when it is needed); return_ray_loss=True: (loss, L_r [R], not differentiable)."""
+    rng = resolve_rng(params, jitter, rng)
+    return _DistortionFn.apply(densities, spec, params, rays_o, rays_d, jitter, rng, bool(return_ray_loss), int(_lanes))
