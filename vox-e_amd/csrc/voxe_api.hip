@@ -93,14 +93,9 @@ int validate_grid_only(const VoxeGridDesc* g) {
   return grid_acts_status(g);
 }
 
-// voxe_recon_step's paired render (two renders of the same batch with independent jitter streams in ONE launch of 2 B rays):
-// set around its calls of the render entry points; the space-binned kernels read DevCfg::pair_R
-struct PairSpec { int64_t rays; uint64_t rng_offset; };
-thread_local const PairSpec* tl_pair = nullptr;
-struct PairScope {
-  explicit PairScope(const PairSpec* p) { tl_pair = p; }
-  ~PairScope() { tl_pair = nullptr; }
-};
+// voxe_recon_step's paired render (two renders of the same batch with independent jitter streams in ONE launch of 2 B rays): an
+// argument of plan_render(), kept by the plan; the space-binned kernels read DevCfg::pair_R.  rays = 0: an ordinary render
+struct PairSpec { int64_t rays = 0; uint64_t rng_offset = 0; };
 
 void grid_to_dev(const VoxeGridDesc* g, DevGrid* dg) {
   dg->X = g->X; dg->Y = g->Y; dg->Z = g->Z;
@@ -112,14 +107,14 @@ void grid_to_dev(const VoxeGridDesc* g, DevGrid* dg) {
   dg->pre_act = g->density_pre_act; dg->post_act = g->density_post_act;
 }
 
-void make_dev(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const Variant& v, DevGrid* dg,
+void make_dev(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const Variant& v, const PairSpec& pair, DevGrid* dg,
               HostCfg* dc) {
   dc->disp = disp_of(c);
   dc->pair_R = 0; dc->key0b = dc->key1b = 0;
-  if (tl_pair) {
-    dc->pair_R = tl_pair->rays;
-    dc->key0b = (uint32_t)c->seed ^ ((uint32_t)tl_pair->rng_offset * 0x9E3779B1u);
-    dc->key1b = (uint32_t)(c->seed >> 32) ^ (uint32_t)(tl_pair->rng_offset >> 32) ^ 0x7F4A7C15u;
+  if (pair.rays) {
+    dc->pair_R = pair.rays;
+    dc->key0b = (uint32_t)c->seed ^ ((uint32_t)pair.rng_offset * 0x9E3779B1u);
+    dc->key1b = (uint32_t)(c->seed >> 32) ^ (uint32_t)(pair.rng_offset >> 32) ^ 0x7F4A7C15u;
   }
   grid_to_dev(g, dg);
   dc->S = c->num_samples;
@@ -207,7 +202,12 @@ WsLayout ws_layout(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, boo
 // the part every call on a grid shares (grid step, point queries): packed grid + gradient region
 WsLayout grid_layout(const VoxeGridDesc* g) { return ws_layout(g, nullptr, 0, false); }
 
-int finish() { return hipGetLastError() == hipSuccess ? VOXE_OK : VOXE_ERR_LAUNCH; }
+// Every launching entry point ends here, and touches a thread-local of this library on the way.  glibc before 2.39 (BZ 19924) brings a
+// thread's TLS table up to date only when the thread reads a thread-local of the NEWEST module loaded; until then every thread-local
+// access of a dlopen()ed HIP runtime takes the slow path: measured 40 ns per HIP call, 1 - 2 us per entry point of this library, in a
+// Python process (profiles/recon_args_host_time.txt).  The thread-local arguments this file used to read per call hid that.
+thread_local volatile int tl_tls_current = 0;
+int finish() { tl_tls_current = 1; return hipGetLastError() == hipSuccess ? VOXE_OK : VOXE_ERR_LAUNCH; }
 
 // ---- the plan of one render call -----------------------------------------------------------------------------------------------
 // Everything the entry points decide about a call -- which route it takes, how the workspace is carved, which optional buffers
@@ -219,6 +219,7 @@ int finish() { return hipGetLastError() == hipSuccess ? VOXE_OK : VOXE_ERR_LAUNC
 // partials need `total`, the region route, the two-phase buffers and the deterministic scratch need `total_with_src`.
 struct RenderPlan {
   Variant v; DevGrid dg; HostCfg dc; WsLayout l;
+  PairSpec pair;                 // the paired render of voxe_recon_step, or rays = 0
   int route = VOXE_ROUTE_NONE;   // nominal VOXE_ROUTE_*
   int nseg = 1;                  // depth segments of a march
   bool det = false, region = false, tiled = false, packed_bwd = false;   // deterministic | space-binned | LDS-window | line-dense scatter backward
@@ -250,13 +251,14 @@ struct RenderPlan {
 };
 
 // Status of validate(); on VOXE_OK the whole plan is filled, otherwise only the layout (voxe_workspace_bytes answers for
-// descriptors a render call would refuse).  Reads tl_pair: call it inside the PairScope of the
-// launches it plans.  `jitter`: the caller's jitter array (the lean forward, hence the precise sums, exist only without one).
-int plan_render(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const float* jitter, RenderPlan* p) {
+// descriptors a render call would refuse).  `jitter`: the caller's jitter array (the lean forward, hence the precise sums, exist
+// only without one).  `pair` (nullable): the paired render of voxe_recon_step.
+int plan_render(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const float* jitter, const PairSpec* pair, RenderPlan* p) {
   *p = RenderPlan();   // (zeroes dg / dc: a plan that was refused has R = 0)
+  if (pair) p->pair = *pair;
   const int st = validate(g, c, R, &p->v);
   if (st == VOXE_OK) {
-    make_dev(g, c, R, p->v, &p->dg, &p->dc);
+    make_dev(g, c, R, p->v, p->pair, &p->dg, &p->dc);
     const VoxeDispatch& d = p->dc.disp;
     p->nseg = num_segments(c->num_samples, p->dc.seg_len);
     p->det = c->deterministic != 0;
@@ -283,12 +285,23 @@ int plan_render(const VoxeGridDesc* g, const VoxeRenderCfg* c, int64_t R, const 
 // keeps the workspace for a backward of these rays) or a re-march of the backward (`out` = null: no outputs, everything a backward
 // reads is rebuilt).  One function, so that the two cannot disagree about sample_fwd, segsum_d, sched, ray_state or segbuf.
 struct FwdOutputs { float *colour, *depth, *acc, *disparity; };
-FwdArgs fwd_args(const RenderPlan& p, const RenderPlan::Tier& t, void* workspace, const float* rays_o, const float* rays_d,
-                 const float* jitter, const FwdOutputs* out, bool keep) {
+// what every function that runs a planned render is given, besides the plan
+struct RenderCall {
+  const VoxeGridDesc* grid; const VoxeRenderCfg* cfg;
+  const float *rays_o, *rays_d; int64_t R; const float* jitter;
+  void* workspace; size_t workspace_bytes; hipStream_t s;
+  // voxe_recon_step on the space-binned route: where the segment tables live (null: in the workspace's own region scratch) and
+  // whether voxe_recon_prefetch already filled them for these rays
+  void* region_tables = nullptr; bool prebinned = false;
+  bool drop_hint = false;   // a public render entry's call: once it is known to run, a hint pending on the workspace is dropped
+};
+FwdArgs fwd_args(const RenderPlan& p, const RenderPlan::Tier& t, const RenderCall& c, const FwdOutputs* out, bool keep) {
   const WsLayout& l = p.l;
+  void* const workspace = c.workspace;
   const FwdOutputs o = out ? *out : FwdOutputs{};
-  FwdArgs a{at<float>(workspace, l.packed_off), rays_o, rays_d, jitter, o.colour, o.depth, o.acc, o.disparity, nullptr, nullptr};
+  FwdArgs a{at<float>(workspace, l.packed_off), c.rays_o, c.rays_d, c.jitter, o.colour, o.depth, o.acc, o.disparity, nullptr, nullptr};
   a.keep_samples = keep;
+  a.region_tables = c.region_tables; a.prebinned = c.prebinned;
   if (t.region) return a;   // (the region kernels keep their states and tables in their own scratch)
   // depth-segment states for the segmented backward, when that backward applies (a re-march runs only for a backward that reads them)
   if (t.full && (p.tiled || p.packed_bwd || !out)) a.ray_state = at<float>(workspace, l.state_off);
@@ -320,13 +333,11 @@ struct FwdStamp {
   float d_fit_m, d_fit_lat, d_ffit_lat, d_ffit_m, d_zdom, d_max_adv, d_image_ratio;
 };
 FwdStamp make_stamp(const VoxeGridDesc* g, const VoxeRenderCfg* c, const float* rays_o, const float* rays_d, int64_t R,
-                    const float* jitter, size_t wsbytes) {
+                    const float* jitter, size_t wsbytes, const PairSpec& pair) {
   FwdStamp k;
   memset(&k, 0, sizeof(k));   // (padding included: stamps are compared with memcmp)
-  const int64_t pair_rays = tl_pair ? tl_pair->rays : 0;
-  const uint64_t pair_offset = tl_pair ? tl_pair->rng_offset : 0;
   k.densities = g->densities; k.features = g->features; k.rays_o = rays_o; k.rays_d = rays_d; k.jitter = jitter;
-  k.R = R; k.pair_rays = pair_rays; k.seed = c->seed; k.rng_offset = c->rng_offset; k.pair_offset = pair_offset; k.wsbytes = wsbytes;
+  k.R = R; k.pair_rays = pair.rays; k.seed = c->seed; k.rng_offset = c->rng_offset; k.pair_offset = pair.rng_offset; k.wsbytes = wsbytes;
   k.X = g->X; k.Y = g->Y; k.Z = g->Z; k.F = g->F; k.feature_kind = g->feature_kind; k.pre_act = g->density_pre_act;
   k.post_act = g->density_post_act; k.S = c->num_samples; k.perturb = c->perturb; k.lindisp = c->linear_disparity;
   k.clip = c->aabb_clip; k.white = c->white_bkgd; k.deg = c->sh_degree; k.diffuse = c->render_diffuse; k.width = c->image_width;
@@ -340,6 +351,9 @@ FwdStamp make_stamp(const VoxeGridDesc* g, const VoxeRenderCfg* c, const float* 
   k.d_fit_m = d.tile_fit_m; k.d_fit_lat = d.tile_fit_lat; k.d_ffit_lat = d.fwd_fit_lat; k.d_ffit_m = d.fwd_fit_m; k.d_zdom = d.fwd_zdom;
   k.d_max_adv = d.fwd_max_adv; k.d_image_ratio = d.region_image_ratio;
   return k;
+}
+FwdStamp make_stamp(const RenderPlan& p, const RenderCall& c) {
+  return make_stamp(c.grid, c.cfg, c.rays_o, c.rays_d, c.R, c.jitter, c.workspace_bytes, p.pair);
 }
 constexpr size_t kMaxStamps = 256;
 std::mutex g_stamp_mu;
@@ -367,6 +381,116 @@ bool stamp_matches(const void* workspace, FwdStamp k) {
   const auto it = g_stamps.find(workspace);
   return it != g_stamps.end() && memcmp(&it->second, &k, sizeof(k)) == 0;
 }
+
+// ---- voxe_recon_prefetch: the batch and the segment tables of the NEXT iteration, assembled on a side stream ---------------------
+// Batch assembly and binning read the cameras, the images and the jitter streams -- never the grid -- so iteration i + 1's can run
+// while iteration i's backward and grid step occupy the memory system (binning is index arithmetic; the grid step is a pure
+// HBM stream).  Two sets of tables / batch buffers alternate: set 0 = (region scratch of `workspace`, front of `scratch`), set 1 =
+// (the same offsets of `workspace2`, ReconLayout::batch2).  A prefetch is a HINT recorded per workspace: the step that follows
+// uses it iff the arguments that decide the batch and the tables are the ones it was made for (ReconKey, compared field by
+// field); otherwise it waits for the side stream and assembles its own, exactly as without the hint.
+struct ReconKey {
+  FwdStamp fwd;                  // grid geometry, cfg, dispatch, jitter streams, ray buffers of the paired render
+  const void *poses, *image_rows, *images, *workspace2, *scratch;
+  uint64_t subset_offset, ws2bytes, scbytes;
+  int64_t batch;
+  int32_t H, W, K, num_images;
+  float focal;
+};
+// The hints on record -- one per workspace, with the side stream it is assembled on -- and their protocol.  Each method is one step
+// of it and takes the lock once.  Each finds its record by workspace: a record that another thread's issue() recycled between two
+// steps of one call is simply absent (or fresh) for the later step, which then has nothing to do.
+class ReconHints {
+ public:
+  // voxe_recon_prefetch: `enqueue(slot, side)` puts the work of a hint for table set `slot` on the side stream and returns what the
+  // hint was made for.  The side work starts behind the forward of the last step on this workspace: launched in front of the
+  // backward, the segment pass would take a quarter of its slots; behind it, it shares the machine with the grid step, an HBM stream
+  // that leaves the CUs idle (profiles/r06_recon_prefetch.txt; the schedules that lost are in DESIGN.md's table).
+  template <class Enqueue>
+  int issue(const void* workspace, hipStream_t s, Enqueue enqueue) {
+    std::lock_guard<std::mutex> lock(mu_);
+    if (recs_.size() >= kMaxRecords && recs_.find(workspace) == recs_.end()) {
+      // (workspaces come and go with their trainers: records without a hint in flight give their stream and events back)
+      for (auto it = recs_.begin(); it != recs_.end();) {
+        Record& o = it->second;
+        if (o.hint.valid) { ++it; continue; }          // (a hint in flight: its events are still waited for)
+        if (o.side) { (void)hipStreamSynchronize(o.side); (void)hipStreamDestroy(o.side); }
+        if (o.fork) (void)hipEventDestroy(o.fork);
+        if (o.done) (void)hipEventDestroy(o.done);
+        it = recs_.erase(it);
+      }
+    }
+    Record& r = recs_[workspace];
+    if (!r.side) {
+      // (lowest priority: the side stream's kernels fill what the iteration's own kernels leave idle, they do not queue in front of them)
+      int prio_lo = 0, prio_hi = 0;
+      (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+      if (hipStreamCreateWithPriority(&r.side, hipStreamNonBlocking, prio_lo) != hipSuccess) return VOXE_ERR_LAUNCH;
+      if (hipEventCreateWithFlags(&r.fork, hipEventDisableTiming) != hipSuccess) return VOXE_ERR_LAUNCH;
+      if (hipEventCreateWithFlags(&r.done, hipEventDisableTiming) != hipSuccess) return VOXE_ERR_LAUNCH;
+    }
+    const int slot = 1 - r.last_slot;   // (a hint never consumed: its tables are overwritten -- in stream order on the side stream)
+    if (!r.forked) (void)hipEventRecord(r.fork, s);   // no step has run on this workspace yet (or the last one took another route): behind whatever is on `s`
+    (void)hipStreamWaitEvent(r.side, r.fork, 0);
+    r.hint = Pending{true, slot, enqueue(slot, r.side)};
+    (void)hipEventRecord(r.done, r.side);
+    ++stats_[0];
+    return VOXE_OK;
+  }
+  // voxe_recon_step begins: `s` waits for a hint pending on the workspace whether or not the step takes its tables (it may be about
+  // to write that set); the hint is handed over.  Until forward_enqueued() a new hint is ordered behind everything on the stream.
+  struct Pending { bool valid = false; int slot = 0; ReconKey key{}; };
+  Pending begin_step(const void* workspace, hipStream_t s) {
+    std::lock_guard<std::mutex> lock(mu_);
+    const auto it = recs_.find(workspace);
+    if (it == recs_.end()) return Pending();
+    Record& r = it->second;
+    const Pending p = r.hint;
+    if (p.valid) (void)hipStreamWaitEvent(s, r.done, 0);
+    r.hint.valid = false;
+    r.last_slot = 0;
+    r.forked = false;
+    return p;
+  }
+  // the forward of a step that rendered from table set `slot` is on `s`: from here on the other set may be rewritten
+  void forward_enqueued(const void* workspace, int slot, hipStream_t s) {
+    std::lock_guard<std::mutex> lock(mu_);
+    const auto it = recs_.find(workspace);
+    if (it == recs_.end() || !it->second.side) return;
+    it->second.last_slot = slot;
+    (void)hipEventRecord(it->second.fork, s);
+    it->second.forked = true;
+  }
+  // a step took the hint it was handed / assembled its own batch and tables instead
+  void count(bool taken) { std::lock_guard<std::mutex> lock(mu_); ++stats_[taken ? 1 : 2]; }
+  // a call other than the step is about to write `ptr` beyond the gradient region on `s`: a hint whose tables may live there (its workspace
+  // or workspace2) is dropped, `s` waits for the side stream, and the next hint there is ordered behind everything on its stream
+  void workspace_written(const void* ptr, hipStream_t s) {
+    std::lock_guard<std::mutex> lock(mu_);
+    for (auto& rec : recs_) {
+      Record& r = rec.second;
+      if (rec.first != ptr && r.hint.key.workspace2 != ptr) continue;   // (the key of the last hint issued, pending or not)
+      r.forked = false;
+      if (!r.hint.valid) continue;
+      (void)hipStreamWaitEvent(s, r.done, 0);
+      r.hint.valid = false; ++stats_[2];
+    }
+  }
+  void stats(int64_t out[3]) { std::lock_guard<std::mutex> lock(mu_); for (int i = 0; i < 3; ++i) out[i] = stats_[i]; }
+ private:
+  struct Record {
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr;     // on the caller's stream, behind a step's forward (fold pass): from here on the side work of a hint may run
+    hipEvent_t done = nullptr;     // on the side stream, behind the pending hint's work
+    bool forked = false; int last_slot = 0;   // set the last step of this workspace rendered from
+    Pending hint;                  // awaits the next step on this workspace
+  };
+  static constexpr size_t kMaxRecords = 16;
+  std::mutex mu_;
+  std::unordered_map<const void*, Record> recs_;     // by workspace
+  int64_t stats_[3] = {0, 0, 0};                     // hints issued | taken by the following step | dropped (voxe_recon_prefetch_stats)
+};
+ReconHints g_hints;
 
 // ---- per-phase timing (voxe_profile_*) ----------------------------------------------------------
 enum Phase { PH_PACK = 0, PH_FWD, PH_MEMSET, PH_BWD, PH_UNPACK, PH_COUNT };
@@ -485,7 +609,7 @@ int voxe_random_subset(int64_t n, int64_t count, uint64_t seed, uint64_t rng_off
 // out = (1 when launches of this configuration build one, byte offset, blocks of a launch, tile slots of a launch)
 int voxe_tile_sched_debug_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, int64_t out[4]) {
   RenderPlan p;
-  const int st = plan_render(grid, cfg, R, nullptr, &p);
+  const int st = plan_render(grid, cfg, R, nullptr, nullptr, &p);
   if (st) return st;
   if (!out) return VOXE_ERR_NULL_POINTER;
   const HostCfg& dc = p.dc;
@@ -502,7 +626,7 @@ int voxe_tile_sched_debug_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* 
 // forward / backward kernels this process has made so far
 int voxe_tile_plan_debug_offset(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, int64_t* out) {
   RenderPlan p;
-  const int st = plan_render(grid, cfg, R, nullptr, &p);
+  const int st = plan_render(grid, cfg, R, nullptr, nullptr, &p);
   if (st) return st;
   if (!out) return VOXE_ERR_NULL_POINTER;
   *out = p.l.plan_bytes > 0 ? (int64_t)p.l.plan_off : -1;
@@ -516,85 +640,82 @@ int voxe_tile_plan_debug_launches(int64_t out[2]) {
 
 size_t voxe_tile_plan_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
   RenderPlan p;
-  if (plan_render(grid, cfg, R, nullptr, &p) != VOXE_OK || !cfg || cfg->ray_state_valid < 0) return 0;
+  if (plan_render(grid, cfg, R, nullptr, nullptr, &p) != VOXE_OK || !cfg || cfg->ray_state_valid < 0) return 0;
   return p.l.plan_bytes;
 }
 
 size_t voxe_workspace_bytes(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
   RenderPlan p;
-  (void)plan_render(grid, cfg, R, nullptr, &p);   // (sizes are answered for descriptors a render call would refuse, too)
+  (void)plan_render(grid, cfg, R, nullptr, nullptr, &p);   // (sizes are answered for descriptors a render call would refuse, too)
   // ray_state_valid = -1 (inference: no backward of these rays follows): the packed grid and the segmented forward's states /
   // partials -- none of the backward's per-sample sources, staging gradient or binning scratch (gigabytes at large R)
   return (cfg && cfg->ray_state_valid < 0) ? p.l.total : p.l.total_with_src;
 }
 
-int voxe_render_fwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o,
-                    const float* rays_d, int64_t R, const float* jitter, float* colour, float* depth,
-                    float* acc, float* disparity, void* workspace, size_t workspace_bytes,
-                    void* stream) {
-  RenderPlan p;
-  const int st = plan_render(grid, cfg, R, jitter, &p);
-  if (st) return st;
-  if (R > 0 && (!rays_o || !rays_d || !colour)) return VOXE_ERR_NULL_POINTER;
-  if (!workspace || workspace_bytes < p.l.fwd_total) return VOXE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  if (!cfg->reuse_packed_grid) { PhaseTimer t(PH_PACK, s); launch_pack_any(grid, at<float>(workspace, p.l.packed_off), s); }
-  if (R == 0) return finish();
-  {
-    // what this workspace holds from now on (a backward's ray_state_valid = 1 is checked against it)
-    FwdStamp k = make_stamp(grid, cfg, rays_o, rays_d, R, jitter, workspace_bytes);
-    k.kept = cfg->ray_state_valid >= 0 ? 1 : 0;
-    record_stamp(workspace, k);
-  }
-  const RenderPlan::Tier tier = p.tier(workspace_bytes);
-  const FwdOutputs out{colour, depth, acc, disparity};
-  const FwdArgs a = fwd_args(p, tier, workspace, rays_o, rays_d, jitter, &out, cfg->ray_state_valid >= 0);
-  if (tier.region) {
-    // space-binned path (unordered / sparse rays): forward through the region kernels; the segment tables and per-segment
-    // states stay in the workspace for the backward of the same call (cfg->ray_state_valid)
-    PhaseTimer t(PH_FWD, s);
-    launch_fwd_region(p.dg, p.dc, cfg->sh_degree, cfg->render_diffuse, a, at<char>(workspace, p.l.region_off), s);
-    return finish();
-  }
-  { PhaseTimer t(PH_FWD, s); launch_fwd(p.dg, p.dc, cfg->sh_degree, cfg->render_diffuse, a, s); }
-  return finish();
-}
-
 }  // extern "C" (reopened below)
 
 namespace {
+// ---- running a planned render ------------------------------------------------------------------------------------------------------
+// The public render entries plan their call and hand the plan to the functions below with RenderCall::drop_hint set: behind the
+// checks that can refuse the call, in front of its first launch, a prefetch hint pending on the workspace is dropped
+// (ReconHints::workspace_written).  voxe_recon_step and voxe_attn_refine_step plan each of their renders once and run its forward
+// and backward from that plan (which reads neither cfg->ray_state_valid nor cfg->reuse_packed_grid: the steps change both in
+// between); voxe_recon_step leaves drop_hint off, so a step never drops its own hint.
+int render_fwd(const RenderPlan& p, const RenderCall& c, const FwdOutputs& out) {
+  const VoxeRenderCfg* cfg = c.cfg; void* const workspace = c.workspace; hipStream_t s = c.s;
+  if (c.R > 0 && (!c.rays_o || !c.rays_d || !out.colour)) return VOXE_ERR_NULL_POINTER;
+  if (!workspace || c.workspace_bytes < p.l.fwd_total) return VOXE_ERR_WORKSPACE;
+  if (c.drop_hint) g_hints.workspace_written(workspace, s);
+  if (!cfg->reuse_packed_grid) { PhaseTimer t(PH_PACK, s); launch_pack_any(c.grid, at<float>(workspace, p.l.packed_off), s); }
+  if (c.R == 0) return finish();
+  {
+    // what this workspace holds from now on (a backward's ray_state_valid = 1 is checked against it)
+    FwdStamp k = make_stamp(p, c);
+    k.kept = cfg->ray_state_valid >= 0 ? 1 : 0;
+    record_stamp(workspace, k);
+  }
+  const RenderPlan::Tier tier = p.tier(c.workspace_bytes);
+  const FwdArgs a = fwd_args(p, tier, c, &out, cfg->ray_state_valid >= 0);
+  PhaseTimer t(PH_FWD, s);
+  // space-binned path (unordered / sparse rays): forward through the region kernels; the segment tables and per-segment
+  // states stay in the workspace for the backward of the same call (cfg->ray_state_valid)
+  if (tier.region) launch_fwd_region(p.dg, p.dc, cfg->sh_degree, cfg->render_diffuse, a, at<char>(workspace, p.l.region_off), s);
+  else launch_fwd(p.dg, p.dc, cfg->sh_degree, cfg->render_diffuse, a, s);
+  return finish();
+}
+
 // what the three backward entry points check before anything else; on VOXE_OK *p is the plan of the call
 int plan_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, const float* jitter, const float* rays_o,
              const float* rays_d, const float* colour, const float* depth, const float* acc, const float* d_colour, RenderPlan* p) {
-  const int st = plan_render(grid, cfg, R, jitter, p);
+  const int st = plan_render(grid, cfg, R, jitter, nullptr, p);
   if (st) return st;
   if (R > 0 && (!rays_o || !rays_d || !colour || !depth || !acc || !d_colour)) return VOXE_ERR_NULL_POINTER;
   return VOXE_OK;
 }
 
-// memset (optional) + backward kernel into the workspace's packed gradient region; *bricked = layout of that region
-int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const RenderPlan& p, const float* rays_o,
-                      const float* rays_d, int64_t R, const float* jitter, const float* colour, const float* depth,
-                      const float* acc, const float* d_colour, const float* d_depth, const float* d_acc, bool want_d,
-                      bool want_f, bool zero_first, bool* bricked, void* workspace, size_t workspace_bytes,
-                      hipStream_t s, void* grad_workspace, size_t grad_workspace_bytes) {
+// memset (optional) + backward kernel into the packed gradient region of the workspace (or `grad_workspace`'s); *grad_layout = its layout
+int render_bwd(const RenderPlan& p, const RenderCall& c, const float* colour, const float* depth, const float* acc,
+               const float* d_colour, const float* d_depth, const float* d_acc, bool want_d, bool want_f, bool zero_first,
+               int32_t* grad_layout, void* grad_workspace, size_t grad_workspace_bytes) {
+  const VoxeRenderCfg* cfg = c.cfg; void* const workspace = c.workspace; hipStream_t s = c.s;
   const WsLayout& l = p.l;
-  if (!workspace || workspace_bytes < l.total) return VOXE_ERR_WORKSPACE;
+  if (!workspace || c.workspace_bytes < l.total) return VOXE_ERR_WORKSPACE;
   if (grad_workspace && grad_workspace_bytes < l.state_off) return VOXE_ERR_WORKSPACE;   // (packed grid + gradient region)
+  if (c.drop_hint) g_hints.workspace_written(workspace, s);
   float* packed = at<float>(workspace, l.packed_off);
   float* gpacked = at<float>(grad_workspace ? grad_workspace : workspace, l.grad_off);
-  if (!cfg->reuse_packed_grid) { PhaseTimer t(PH_PACK, s); launch_pack_any(grid, packed, s); }
+  if (!cfg->reuse_packed_grid) { PhaseTimer t(PH_PACK, s); launch_pack_any(c.grid, packed, s); }
   if (zero_first) {
     PhaseTimer t(PH_MEMSET, s);
     if (hipMemsetAsync(gpacked, 0, l.grad_bytes(), s) != hipSuccess) return VOXE_ERR_LAUNCH;
   }
-  *bricked = false;
-  if (R == 0) return VOXE_OK;
+  if (c.R == 0) { *grad_layout = VOXE_GRAD_ANY; return finish(); }
   const DevGrid& dg = p.dg; const HostCfg& dc = p.dc;
-  const RenderPlan::Tier tier = p.tier(workspace_bytes);
+  const RenderPlan::Tier tier = p.tier(c.workspace_bytes);
   float* state = at<float>(workspace, l.state_off);
-  BwdArgs a{packed, rays_o, rays_d, jitter, colour, depth, acc, d_colour, d_depth, d_acc, gpacked,
+  BwdArgs a{packed, c.rays_o, c.rays_d, c.jitter, colour, depth, acc, d_colour, d_depth, d_acc, gpacked,
             want_d, want_f, (p.tiled || p.packed_bwd) ? state : nullptr};
+  a.region_tables = c.region_tables;
   // (the forward of these rays -- voxe_render_fwd with this workspace or the re-march below -- wrote the sums, the list and its
   // per-sample values under the same plan: fwd_args())
   if (p.precise_sums_apply) a.segsum_d = at<const double>(workspace, l.prec_off);
@@ -613,7 +734,7 @@ int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
     a.ray_state = state;
   }
   // the caller's claim that the workspace holds this render's forward is only believed when the forward's record says so
-  const FwdStamp stamp = make_stamp(grid, cfg, rays_o, rays_d, R, jitter, workspace_bytes);
+  const FwdStamp stamp = make_stamp(p, c);
   const bool states_valid = cfg->ray_state_valid > 0 && stamp_matches(workspace, stamp);
   if (!states_valid) {
     // (the re-march below writes everything a backward reads: from here on the workspace holds THIS render)
@@ -624,10 +745,11 @@ int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
   if (!states_valid && tier.route != VOXE_ROUTE_SCATTER) {
     // the caller's workspace does not hold this call's forward states (region route: segment tables too): re-march, no outputs
     PhaseTimer t(PH_FWD, s);
-    const FwdArgs f = fwd_args(p, tier, workspace, rays_o, rays_d, jitter, nullptr, true);
+    const FwdArgs f = fwd_args(p, tier, c, nullptr, true);
     if (tier.region) launch_fwd_region(dg, dc, cfg->sh_degree, cfg->render_diffuse, f, at<char>(workspace, l.region_off), s);
     else launch_fwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, f, s);
   }
+  bool bricked = false;
   PhaseTimer t(PH_BWD, s);
   if (tier.route == VOXE_ROUTE_DETERMINISTIC) {
     // (the fixed-point region must start cleared: the finalize pass leaves it so, the first use clears it here)
@@ -639,15 +761,27 @@ int render_bwd_common(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
     launch_bwd_tile(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
   } else if (tier.route == VOXE_ROUTE_PACKED_SCATTER) {
     launch_bwd_packed_scatter(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
-    *bricked = !cfg->linear_grad;  // that kernel accumulates into the bricked layout unless asked otherwise
+    bricked = !cfg->linear_grad;  // that kernel accumulates into the bricked layout unless asked otherwise
   } else {
     launch_bwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, a, s);
   }
-  return VOXE_OK;
+  *grad_layout = bricked ? VOXE_GRAD_BRICKED : VOXE_GRAD_LINEAR;
+  return finish();
 }
 }  // namespace
 
 extern "C" {
+
+int voxe_render_fwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o,
+                    const float* rays_d, int64_t R, const float* jitter, float* colour, float* depth,
+                    float* acc, float* disparity, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  RenderPlan p;
+  const int st = plan_render(grid, cfg, R, jitter, nullptr, &p);
+  if (st) return st;
+  return render_fwd(p, RenderCall{grid, cfg, rays_o, rays_d, R, jitter, workspace, workspace_bytes, (hipStream_t)stream, nullptr, false, /*drop_hint=*/true},
+                    FwdOutputs{colour, depth, acc, disparity});
+}
 
 int voxe_render_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o,
                     const float* rays_d, int64_t R, const float* jitter, const float* colour,
@@ -659,12 +793,11 @@ int voxe_render_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const fl
   if (st) return st;
   if (!d_densities && !d_features) return VOXE_OK;
   hipStream_t s = (hipStream_t)stream;
-  bool bricked = false;
-  const int rc = render_bwd_common(grid, cfg, p, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc,
-                                   d_densities != nullptr, d_features != nullptr, true, &bricked, workspace,
-                                   workspace_bytes, s, nullptr, 0);
+  int32_t layout = VOXE_GRAD_ANY;
+  const int rc = render_bwd(p, RenderCall{grid, cfg, rays_o, rays_d, R, jitter, workspace, workspace_bytes, s, nullptr, false, /*drop_hint=*/true}, colour, depth, acc,
+                            d_colour, d_depth, d_acc, d_densities != nullptr, d_features != nullptr, true, &layout, nullptr, 0);
   if (rc) return rc;
-  { PhaseTimer t(PH_UNPACK, s); launch_unpack_any(grid, at<const float>(workspace, p.l.grad_off), d_densities, d_features, accumulate, bricked ? 1 : 0, s); }
+  { PhaseTimer t(PH_UNPACK, s); launch_unpack_any(grid, at<const float>(workspace, p.l.grad_off), d_densities, d_features, accumulate, layout == VOXE_GRAD_BRICKED ? 1 : 0, s); }
   return finish();
 }
 
@@ -686,26 +819,22 @@ int voxe_render_bwd_acc_into(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
   const int st = plan_bwd(grid, cfg, R, jitter, rays_o, rays_d, colour, depth, acc, d_colour, &p);
   if (st) return st;
   if (!grad_layout) return VOXE_ERR_NULL_POINTER;
-  bool bricked = false;
-  const int rc = render_bwd_common(grid, cfg, p, rays_o, rays_d, R, jitter, colour, depth, acc, d_colour, d_depth, d_acc,
-                                   want_densities != 0, want_features != 0, zero_first != 0, &bricked, workspace,
-                                   workspace_bytes, (hipStream_t)stream, grad_workspace, grad_workspace_bytes);
-  if (rc) return rc;
-  *grad_layout = R > 0 ? (bricked ? VOXE_GRAD_BRICKED : VOXE_GRAD_LINEAR) : VOXE_GRAD_ANY;
-  return finish();
+  return render_bwd(p, RenderCall{grid, cfg, rays_o, rays_d, R, jitter, workspace, workspace_bytes, (hipStream_t)stream, nullptr, false, /*drop_hint=*/true}, colour, depth,
+                    acc, d_colour, d_depth, d_acc, want_densities != 0, want_features != 0, zero_first != 0, grad_layout, grad_workspace,
+                    grad_workspace_bytes);
 }
 
 // the two answers below are nominal: given the workspace voxe_workspace_bytes asks for
 int voxe_render_bwd_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
   RenderPlan p;
-  const int st = plan_render(grid, cfg, R, nullptr, &p);
+  const int st = plan_render(grid, cfg, R, nullptr, nullptr, &p);
   if (st) return st < -1 ? st : VOXE_ERR_BAD_SHAPE;
   return p.grad_layout();
 }
 
 int voxe_render_route(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
   RenderPlan p;
-  const int st = plan_render(grid, cfg, R, nullptr, &p);
+  const int st = plan_render(grid, cfg, R, nullptr, nullptr, &p);
   if (st) return st < -1 ? st : VOXE_ERR_BAD_SHAPE;
   return p.route;
 }
@@ -719,9 +848,6 @@ int voxe_disparity_bwd(const float* depth, const float* acc, const float* d_disp
 }
 
 namespace {
-#ifndef VOXE_RECON_PAIRED
-#define VOXE_RECON_PAIRED 1
-#endif
 struct ReconLayout { size_t subset, rays_o, rays_d, target, out[2], d_colour[2], partial, out2, d_colour2, batch2, total; };
 ReconLayout recon_layout(int64_t B) {
   ReconLayout l;
@@ -744,55 +870,12 @@ ReconLayout recon_layout(int64_t B) {
   return l;
 }
 
-// ---- voxe_recon_prefetch: the batch and the segment tables of the NEXT iteration, assembled on a side stream ---------------------
-// Batch assembly and binning read the cameras, the images and the jitter streams -- never the grid -- so iteration i + 1's can run
-// while iteration i's backward and grid step occupy the memory system (binning is index arithmetic; the grid step is a pure
-// HBM stream).  Two sets of tables / batch buffers alternate: set 0 = (region scratch of `workspace`, front of `scratch`), set 1 =
-// (the same offsets of `workspace2`, ReconLayout::batch2).  A prefetch is a HINT recorded per workspace: the step that follows
-// uses it iff the arguments that decide the batch and the tables are the ones it was made for (ReconKey, compared field by
-// field); otherwise it waits for the side stream and assembles its own, exactly as without the hint.
-struct ReconKey {
-  FwdStamp fwd;                  // grid geometry, cfg, dispatch, jitter streams, ray buffers of the paired render
-  const void *poses, *image_rows, *images, *workspace2, *scratch;
-  uint64_t subset_offset, ws2bytes, scbytes;
-  int64_t batch;
-  int32_t H, W, K, num_images;
-  float focal;
-};
-struct ReconPending { bool valid = false; int slot = 0; ReconKey key; hipEvent_t done = nullptr; };
-struct ReconSide {
-  hipStream_t side = nullptr;
-  hipEvent_t fork0 = nullptr;    // on the caller's stream, at the start of a step: from here on the idle set of tables / batch buffers may be rewritten
-  hipEvent_t fork = nullptr;     // ... behind the step's forward (fold pass): from here on the segment pass of the hint may run
-  bool forked = false;
-  int last_slot = 0;             // set the last step of this workspace rendered from
-  ReconPending pend;
-};
-std::mutex g_recon_mu;
-std::unordered_map<const void*, ReconSide> g_recon;     // by workspace
-constexpr size_t kMaxReconSides = 16;
-int64_t g_recon_stats[3] = {0, 0, 0};                   // hints issued | taken by the following step | dropped by it (voxe_recon_prefetch_stats)
-#ifndef VOXE_RECON_SIDE_LOW
-#define VOXE_RECON_SIDE_LOW 1
-#endif
-#ifndef VOXE_RECON_FORK
-#define VOXE_RECON_FORK 1        // where a step lets the prefetch of its successor start: 0 at its own start | 1 behind its forward (fold) |
-                                 // 2 batch assembly + clearing of the counters at its start, the segment pass behind its forward |
-                                 // 3 like 2, the segment pass already behind the region forward (beside the fold pass).
-                                 // Measured (160^3, 2 x 32768 rays, ms per iteration of the trainer's loop, which the host paced at the
-                                 // time; profiles/r06_recon_prefetch.txt): no hint 0.805, 1 -> 0.725, 0 -> 0.79, 2 -> 0.78, 3 -> 0.79.
-                                 // (A device-paced loop gains ~1 % from schedule 1 and loses with the others: device work is conserved.)  The backward's blocks hold every SIMD's registers and 144 of 160 KB
-                                 // of LDS: launched behind it (1) the segment pass (1024-thread blocks, 72 KB) waits until the backward
-                                 // drains and then shares the machine with the grid step -- an HBM stream that leaves the CUs idle;
-                                 // launched in front of it (2) the segment pass runs at once but the column scan behind it starves and the
-                                 // backward loses a quarter of its slots for as long.  Stream priority moves nothing (hi / lo equal).
-#endif
-ReconKey recon_key(const VoxeGridDesc* grid, const VoxeRenderCfg* pc, const VoxeRenderCfg* cfg, const VoxeReconStep* rs, const float* rays_o,
-                   const float* rays_d, size_t workspace_bytes, const void* workspace2, size_t workspace2_bytes, const void* scratch,
-                   size_t scratch_bytes) {
+ReconKey recon_key(const VoxeGridDesc* grid, const VoxeRenderCfg* pc, const PairSpec& pair, const VoxeRenderCfg* cfg, const VoxeReconStep* rs,
+                   const float* rays_o, const float* rays_d, size_t workspace_bytes, const void* workspace2, size_t workspace2_bytes,
+                   const void* scratch, size_t scratch_bytes) {
   ReconKey k;
   memset(&k, 0, sizeof(k));
-  k.fwd = make_stamp(grid, pc, rays_o, rays_d, 2 * rs->batch, nullptr, workspace_bytes);
+  k.fwd = make_stamp(grid, pc, rays_o, rays_d, 2 * rs->batch, nullptr, workspace_bytes, pair);
   k.poses = rs->poses; k.image_rows = rs->image_rows; k.images = rs->images; k.workspace2 = workspace2; k.scratch = scratch;
   k.subset_offset = cfg->rng_offset; k.ws2bytes = workspace2_bytes; k.scbytes = scratch_bytes;
   k.batch = rs->batch; k.H = rs->H; k.W = rs->W; k.K = rs->K; k.num_images = rs->num_images; k.focal = rs->focal;
@@ -812,6 +895,12 @@ struct ReconBatchPtrs { int64_t* subset; float *rays_o, *rays_d, *target; };
 ReconBatchPtrs recon_batch_ptrs(const ReconLayout& l, void* scratch, int slot) {
   void* sc = at<char>(scratch, slot ? l.batch2 : 0);
   return ReconBatchPtrs{at<int64_t>(sc, l.subset), at<float>(sc, l.rays_o), at<float>(sc, l.rays_d), at<float>(sc, l.target)};
+}
+// batch assembly: keyed subset of the K * H * W pixels -> rays + target pixels (one launch; same streams as voxe_random_subset,
+// voxe_cast_rays_indexed and the pixel gather)
+void assemble_recon_batch(const VoxeRenderCfg* cfg, const VoxeReconStep* rs, const ReconBatchPtrs& bp, hipStream_t st) {
+  launch_recon_batch(rs->batch, cfg->seed, cfg->rng_offset, rs->H, rs->W, rs->focal, rs->K, rs->poses, rs->images,
+                     (const long long*)rs->image_rows, rs->num_images, (long long*)bp.subset, bp.rays_o, bp.rays_d, bp.target, st);
 }
 int recon_check(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const VoxeReconStep* rs) {
   if (!grid || !cfg || !rs || !rs->poses || !rs->images || !rs->losses) return VOXE_ERR_NULL_POINTER;
@@ -833,67 +922,27 @@ int voxe_recon_prefetch(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, cons
   const int chk = recon_check(grid, cfg, rs);
   if (chk) return chk;
   // only the paired render of SH-0 grids has tables worth assembling ahead; everything else: the hint is dropped
-  if (!(rs->diffuse_regularisation && cfg->sh_degree == 0 && VOXE_RECON_PAIRED) || !workspace || !workspace2 || !scratch) return VOXE_OK;
+  if (!(rs->diffuse_regularisation && cfg->sh_degree == 0) || !workspace || !workspace2 || !scratch) return VOXE_OK;
   const int64_t B = rs->batch;
   const ReconLayout l = recon_layout(B);
   if (scratch_bytes < l.total) return VOXE_ERR_WORKSPACE;
   const VoxeRenderCfg pc = recon_pair_cfg(cfg);
   const PairSpec pair{B, cfg->rng_offset + 2};
-  PairScope scope(&pair);
   RenderPlan plan;
-  (void)plan_render(grid, &pc, 2 * B, nullptr, &plan);   // (a render the plan refuses takes no region route: the hint is dropped)
+  (void)plan_render(grid, &pc, 2 * B, nullptr, &pair, &plan);   // (a render the plan refuses takes no region route: the hint is dropped)
   if (!plan.tier(workspace_bytes).region || !plan.tier(workspace2_bytes).region) return VOXE_OK;
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(g_recon_mu);
-  if (g_recon.size() >= kMaxReconSides && g_recon.find(workspace) == g_recon.end()) {
-    // (workspaces come and go with their trainers: records without a hint in flight give their stream and events back)
-    for (auto it = g_recon.begin(); it != g_recon.end();) {
-      ReconSide& o = it->second;
-      if (o.pend.valid) { ++it; continue; }          // (a hint in flight: its events are still waited for)
-      if (o.side) { (void)hipStreamSynchronize(o.side); (void)hipStreamDestroy(o.side); }
-      if (o.fork) (void)hipEventDestroy(o.fork);
-      if (o.fork0) (void)hipEventDestroy(o.fork0);
-      if (o.pend.done) (void)hipEventDestroy(o.pend.done);
-      it = g_recon.erase(it);
-    }
-  }
-  ReconSide& rsd = g_recon[workspace];
-  if (!rsd.side) {
-    // (lowest priority: the side stream's kernels fill what the iteration's own kernels leave idle, they do not queue in front of them)
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (hipStreamCreateWithPriority(&rsd.side, hipStreamNonBlocking, VOXE_RECON_SIDE_LOW ? prio_lo : prio_hi) != hipSuccess) return VOXE_ERR_LAUNCH;
-    if (hipEventCreateWithFlags(&rsd.fork, hipEventDisableTiming) != hipSuccess) return VOXE_ERR_LAUNCH;
-    if (hipEventCreateWithFlags(&rsd.fork0, hipEventDisableTiming) != hipSuccess) return VOXE_ERR_LAUNCH;
-    if (hipEventCreateWithFlags(&rsd.pend.done, hipEventDisableTiming) != hipSuccess) return VOXE_ERR_LAUNCH;
-  }
-  // (a hint that was never consumed: its tables are overwritten below -- in stream order on the side stream)
-  const int slot = 1 - rsd.last_slot;
-  if (!rsd.forked) {     // no step has run on this workspace yet (or the last one took another route): behind whatever is on `stream`
-    (void)hipEventRecord(rsd.fork0, s);
-    (void)hipEventRecord(rsd.fork, s);
-  }
-  const bool early = VOXE_RECON_FORK == 2 || VOXE_RECON_FORK == 3 || VOXE_RECON_FORK == 0;
-  (void)hipStreamWaitEvent(rsd.side, early ? rsd.fork0 : rsd.fork, 0);
-  const ReconBatchPtrs bp = recon_batch_ptrs(l, scratch, slot);
-  launch_recon_batch(B, cfg->seed, cfg->rng_offset, rs->H, rs->W, rs->focal, rs->K, rs->poses, rs->images,
-                     (const long long*)rs->image_rows, rs->num_images, (long long*)bp.subset, bp.rays_o, bp.rays_d, bp.target, rsd.side);
-  void* const tables = at<char>(slot ? workspace2 : workspace, plan.l.region_off);
-  launch_bin_region(plan.dg, plan.dc, bp.rays_o, bp.rays_d, nullptr, tables, rsd.side, /*phase=*/1);      // counters cleared
-  if (VOXE_RECON_FORK == 2 || VOXE_RECON_FORK == 3) (void)hipStreamWaitEvent(rsd.side, rsd.fork, 0);
-  launch_bin_region(plan.dg, plan.dc, bp.rays_o, bp.rays_d, nullptr, tables, rsd.side, /*phase=*/2);      // segments -> sorted tables
-  (void)hipEventRecord(rsd.pend.done, rsd.side);
-  rsd.pend.valid = true;
-  rsd.pend.slot = slot;
-  ++g_recon_stats[0];
-  rsd.pend.key = recon_key(grid, &pc, cfg, rs, bp.rays_o, bp.rays_d, workspace_bytes, workspace2, workspace2_bytes, scratch, scratch_bytes);
-  return finish();
+  const int st = g_hints.issue(workspace, (hipStream_t)stream, [&](int slot, hipStream_t side) {
+    const ReconBatchPtrs bp = recon_batch_ptrs(l, scratch, slot);
+    assemble_recon_batch(cfg, rs, bp, side);
+    launch_bin_region(plan.dg, plan.dc, bp.rays_o, bp.rays_d, nullptr, at<char>(slot ? workspace2 : workspace, plan.l.region_off), side);
+    return recon_key(grid, &pc, pair, cfg, rs, bp.rays_o, bp.rays_d, workspace_bytes, workspace2, workspace2_bytes, scratch, scratch_bytes);
+  });
+  return st ? st : finish();
 }
 
 int voxe_recon_prefetch_stats(int64_t* out) {
   if (!out) return VOXE_ERR_NULL_POINTER;
-  std::lock_guard<std::mutex> lock(g_recon_mu);
-  for (int i = 0; i < 3; ++i) out[i] = g_recon_stats[i];
+  g_hints.stats(out);
   return VOXE_OK;
 }
 
@@ -909,109 +958,57 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
   hipStream_t s = (hipStream_t)stream;
   const int64_t B = rs->batch;
   int st = VOXE_OK;
-  // a prefetch pending on this workspace: the step waits for the side stream whether or not it takes the tables (they may be
-  // the set this call is about to write), and takes them iff they were made for exactly this call
-  bool have_side = false, pending = false;
-  int pend_slot = 0;
-  ReconKey pend_key;
-  {
-    std::lock_guard<std::mutex> lock(g_recon_mu);
-    const auto it = g_recon.find(workspace);
-    if (it != g_recon.end()) {
-      have_side = true;
-      if (it->second.pend.valid) {
-        pending = true; pend_slot = it->second.pend.slot; pend_key = it->second.pend.key;
-        (void)hipStreamWaitEvent(s, it->second.pend.done, 0);
-        it->second.pend.valid = false;
-      }
-      it->second.last_slot = 0;
-      it->second.forked = false;    // (until the paired route below says from where on the idle tables may be rewritten: a hint given
-                                    //  behind a step that took another route is ordered behind everything on the stream)
-    }
-  }
+  const auto adam_step = [&]() {
+    return voxe_grid_adam_step(grid, VOXE_GRAD_LINEAR, 0, grid->X, nullptr, nullptr, rs->exp_avg_densities,
+                               rs->exp_avg_sq_densities, rs->exp_avg_features, rs->exp_avg_sq_features, rs->lr, rs->beta1,
+                               rs->beta2, rs->eps, rs->step_densities, rs->step_features, nullptr, workspace, workspace_bytes, stream);
+  };
+  // a prefetch pending on this workspace: taken iff it was made for exactly this call
+  const ReconHints::Pending pend = g_hints.begin_step(workspace, s);
   // SH-0 grids: the diffuse render is the specular kernel with another jitter stream -- both renders as ONE launch of 2 B
   // rays on the space-binned route (one binning pass, one forward, one backward; no second packed grid).  32 768-ray
   // batches leave the chip half empty and the binning / scan / fold passes are launch-latency sized: r04, 160^3,
   // 1.15 -> see profiles/r04_recon_bench.txt.  Needs `workspace` sized for 2 B rays (voxe_workspace_bytes(grid, cfg, 2 B)).
-  if (nrender == 2 && cfg->sh_degree == 0 && VOXE_RECON_PAIRED) {
+  if (nrender == 2 && cfg->sh_degree == 0) {
     VoxeRenderCfg pc = recon_pair_cfg(cfg);
     pc.reuse_packed_grid = cfg->reuse_packed_grid;
     const PairSpec pair{B, cfg->rng_offset + 2};
-    PairScope scope(&pair);
     RenderPlan plan;
-    (void)plan_render(grid, &pc, 2 * B, nullptr, &plan);
+    (void)plan_render(grid, &pc, 2 * B, nullptr, &pair, &plan);   // (refused: no region route, the general route below reports it)
     if (plan.tier(workspace_bytes).region) {
-      int slot = 0;
-      if (pending) {
-        const ReconBatchPtrs pp = recon_batch_ptrs(l, scratch, pend_slot);
-        const ReconKey k = recon_key(grid, &pc, cfg, rs, pp.rays_o, pp.rays_d, workspace_bytes, workspace2, workspace2_bytes, scratch, scratch_bytes);
-        if (memcmp(&k, &pend_key, sizeof(k)) == 0) slot = pend_slot; else pending = false;
-        std::lock_guard<std::mutex> lock(g_recon_mu);
-        ++g_recon_stats[pending ? 1 : 2];
+      bool prebinned = false;
+      if (pend.valid) {
+        const ReconBatchPtrs pp = recon_batch_ptrs(l, scratch, pend.slot);
+        const ReconKey k = recon_key(grid, &pc, pair, cfg, rs, pp.rays_o, pp.rays_d, workspace_bytes, workspace2, workspace2_bytes, scratch, scratch_bytes);
+        prebinned = memcmp(&k, &pend.key, sizeof(k)) == 0;
+        g_hints.count(prebinned);
       }
-      const bool prebinned = pending;
+      const int slot = prebinned ? pend.slot : 0;
       const ReconBatchPtrs bp = recon_batch_ptrs(l, scratch, slot);
-      if (have_side) {
-        std::lock_guard<std::mutex> lock(g_recon_mu);
-        const auto it = g_recon.find(workspace);      // (another thread's voxe_recon_prefetch may have recycled the record since)
-        if (it == g_recon.end() || !it->second.side) have_side = false;
-        else {
-          (void)hipEventRecord(it->second.fork0, s);
-          if (VOXE_RECON_FORK == 0) { (void)hipEventRecord(it->second.fork, s); it->second.forked = true; }
-        }
-      }
-      // batch assembly: keyed subset of the K * H * W pixels -> rays + target pixels (one launch; same streams as
-      // voxe_random_subset, voxe_cast_rays_indexed and the pixel gather)
-      if (!prebinned)
-        launch_recon_batch(B, cfg->seed, cfg->rng_offset, rs->H, rs->W, rs->focal, rs->K, rs->poses, rs->images,
-                           (const long long*)rs->image_rows, rs->num_images, (long long*)bp.subset, bp.rays_o, bp.rays_d, bp.target, s);
-      hipEvent_t mid = nullptr;
-      if (have_side && VOXE_RECON_FORK == 3) {
-        std::lock_guard<std::mutex> lock(g_recon_mu);
-        const auto it = g_recon.find(workspace);
-        if (it != g_recon.end()) mid = it->second.fork;
-      }
-      const RegionBins bins{slot ? at<void>(workspace2, plan.l.region_off) : nullptr, prebinned ? 1 : 0, mid};
-      struct BinsScope { explicit BinsScope(const RegionBins* b) { tl_region_bins = b; } ~BinsScope() { tl_region_bins = nullptr; } } bscope(&bins);
+      if (!prebinned) assemble_recon_batch(cfg, rs, bp, s);
       float* colour = at<float>(scratch, l.out2);
       float *depth = colour + 6 * B, *acc = depth + 2 * B;
       float* d_colour = at<float>(scratch, l.d_colour2);
-      st = voxe_render_fwd(grid, &pc, bp.rays_o, bp.rays_d, 2 * B, nullptr, colour, depth, acc, nullptr, workspace, workspace_bytes, stream);
+      const RenderCall call{grid, &pc, bp.rays_o, bp.rays_d, 2 * B, nullptr, workspace, workspace_bytes, s,
+                            /*region_tables=*/slot ? at<void>(workspace2, plan.l.region_off) : nullptr, prebinned};
+      st = render_fwd(plan, call, FwdOutputs{colour, depth, acc, nullptr});
       if (st) return st;
-      if (have_side) {
-        std::lock_guard<std::mutex> lock(g_recon_mu);
-        const auto it = g_recon.find(workspace);
-        if (it != g_recon.end() && it->second.side) {
-          ReconSide& rsd = it->second;
-          rsd.last_slot = slot;
-          if (VOXE_RECON_FORK == 3) rsd.forked = true;      // (recorded between the region forward and the fold pass: RegionBins::after_fwd)
-          else if (VOXE_RECON_FORK != 0) { (void)hipEventRecord(rsd.fork, s); rsd.forked = true; }
-        }
-      }
+      g_hints.forward_enqueued(workspace, slot, s);
       launch_l1_loss_grad_n(colour, bp.target, 3 * B, 2, d_colour, rs->losses, at<char>(scratch, l.partial), s);   // both renders, one launch pair
       pc.ray_state_valid = 1;
       pc.reuse_packed_grid = 1;
       int32_t layout = VOXE_GRAD_ANY;
-      st = voxe_render_bwd_acc_into(grid, &pc, bp.rays_o, bp.rays_d, 2 * B, nullptr, colour, depth, acc, d_colour, nullptr, nullptr,
-                                    rs->exp_avg_densities != nullptr, rs->exp_avg_features != nullptr,
-                                    rs->zero_gradient_first ? 1 : 0, &layout, workspace, workspace_bytes, nullptr, 0, stream);
+      st = render_bwd(plan, call, colour, depth, acc, d_colour, nullptr, nullptr, rs->exp_avg_densities != nullptr,
+                      rs->exp_avg_features != nullptr, rs->zero_gradient_first != 0, &layout, nullptr, 0);
       if (st) return st;
       if (layout != VOXE_GRAD_LINEAR) return VOXE_ERR_UNSUPPORTED;
-      return voxe_grid_adam_step(grid, VOXE_GRAD_LINEAR, 0, grid->X, nullptr, nullptr, rs->exp_avg_densities,
-                                 rs->exp_avg_sq_densities, rs->exp_avg_features, rs->exp_avg_sq_features, rs->lr, rs->beta1,
-                                 rs->beta2, rs->eps, rs->step_densities, rs->step_features, nullptr, workspace, workspace_bytes,
-                                 stream);
+      return adam_step();
     }
   }
-  int64_t* subset = at<int64_t>(scratch, l.subset);
-  float* rays_o = at<float>(scratch, l.rays_o);
-  float* rays_d = at<float>(scratch, l.rays_d);
-  float* target = at<float>(scratch, l.target);
-  launch_recon_batch(B, cfg->seed, cfg->rng_offset, rs->H, rs->W, rs->focal, rs->K, rs->poses, rs->images,
-                     (const long long*)rs->image_rows, rs->num_images, (long long*)subset, rays_o, rays_d, target, s);
+  const ReconBatchPtrs bp = recon_batch_ptrs(l, scratch, 0);
+  assemble_recon_batch(cfg, rs, bp, s);
   VoxeRenderCfg rc[2] = {*cfg, *cfg};
-  void* ws[2] = {workspace, workspace2};
-  size_t wsb[2] = {workspace_bytes, workspace2_bytes};
+  RenderPlan plan[2]; RenderCall call[2];
   for (int i = 0; i < nrender; ++i) {
     rc[i].rng_offset = cfg->rng_offset + 1 + (uint64_t)i;
     rc[i].ray_state_valid = 0;
@@ -1020,26 +1017,26 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
     if (i == 1) rc[i].reuse_packed_grid = 0;       // the second workspace still holds the previous iteration's grid
     float* colour = at<float>(scratch, l.out[i]);
     float *depth = colour + 3 * B, *acc = depth + B;
-    st = voxe_render_fwd(grid, &rc[i], rays_o, rays_d, B, nullptr, colour, depth, acc, nullptr, ws[i], wsb[i], stream);
+    st = plan_render(grid, &rc[i], B, nullptr, nullptr, &plan[i]);
     if (st) return st;
-    launch_l1_loss_grad(colour, target, 3 * B, at<float>(scratch, l.d_colour[i]), rs->losses + 2 * i, at<char>(scratch, l.partial), s);
+    call[i] = RenderCall{grid, &rc[i], bp.rays_o, bp.rays_d, B, nullptr, i == 0 ? workspace : workspace2, i == 0 ? workspace_bytes : workspace2_bytes, s};
+    st = render_fwd(plan[i], call[i], FwdOutputs{colour, depth, acc, nullptr});
+    if (st) return st;
+    launch_l1_loss_grad(colour, bp.target, 3 * B, at<float>(scratch, l.d_colour[i]), rs->losses + 2 * i, at<char>(scratch, l.partial), s);
   }
   for (int i = 0; i < nrender; ++i) {
     float* colour = at<float>(scratch, l.out[i]);
     float *depth = colour + 3 * B, *acc = depth + B;
-    rc[i].ray_state_valid = 1;                     // the forward above left this render's states in ws[i]
+    rc[i].ray_state_valid = 1;                     // the forward above left this render's states in its workspace
     rc[i].reuse_packed_grid = 1;
     int32_t layout = VOXE_GRAD_ANY;
-    st = voxe_render_bwd_acc_into(grid, &rc[i], rays_o, rays_d, B, nullptr, colour, depth, acc, at<const float>(scratch, l.d_colour[i]),
-                                  nullptr, nullptr, rs->exp_avg_densities != nullptr, rs->exp_avg_features != nullptr,
-                                  /*zero_first=*/(i == 0 && rs->zero_gradient_first) ? 1 : 0, &layout, ws[i], wsb[i], i == 0 ? nullptr : workspace,
-                                  i == 0 ? 0 : workspace_bytes, stream);
+    st = render_bwd(plan[i], call[i], colour, depth, acc, at<const float>(scratch, l.d_colour[i]), nullptr, nullptr,
+                    rs->exp_avg_densities != nullptr, rs->exp_avg_features != nullptr,
+                    /*zero_first=*/i == 0 && rs->zero_gradient_first, &layout, i == 0 ? nullptr : workspace, i == 0 ? 0 : workspace_bytes);
     if (st) return st;
     if (layout != VOXE_GRAD_LINEAR) return VOXE_ERR_UNSUPPORTED;
   }
-  return voxe_grid_adam_step(grid, VOXE_GRAD_LINEAR, 0, grid->X, nullptr, nullptr, rs->exp_avg_densities,
-                             rs->exp_avg_sq_densities, rs->exp_avg_features, rs->exp_avg_sq_features, rs->lr, rs->beta1,
-                             rs->beta2, rs->eps, rs->step_densities, rs->step_features, nullptr, workspace, workspace_bytes, stream);
+  return adam_step();
 }
 
 namespace {
@@ -1091,15 +1088,18 @@ int voxe_attn_refine_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, co
   float* tv_grad = at<float>(scratch, l.tv_grad);
   VoxeRenderCfg rc = *cfg;
   rc.ray_state_valid = 0;
-  int st = voxe_render_fwd(grid, &rc, rays_o, rays_d, R, nullptr, attn, depth, acc, nullptr, workspace, workspace_bytes, stream);
+  RenderPlan plan;
+  int st = plan_render(grid, &rc, R, nullptr, nullptr, &plan);
+  if (st) return st;
+  const RenderCall call{grid, &rc, rays_o, rays_d, R, nullptr, workspace, workspace_bytes, s, nullptr, false, /*drop_hint=*/true};
+  st = render_fwd(plan, call, FwdOutputs{attn, depth, acc, nullptr});
   if (st) return st;
   launch_attn_masked_l1(attn, rs->attn_map, R, d_render, rs->losses, at<char>(scratch, l.l1_scratch), s);
   rc.ray_state_valid = 1;
   rc.reuse_packed_grid = 1;
   int32_t layout = VOXE_GRAD_ANY;
-  st = voxe_render_bwd_acc_into(grid, &rc, rays_o, rays_d, R, nullptr, attn, depth, acc, d_render, nullptr, nullptr,
-                                /*want_densities=*/0, /*want_features=*/1, rs->zero_gradient_first ? 1 : 0, &layout, workspace,
-                                workspace_bytes, nullptr, 0, stream);
+  st = render_bwd(plan, call, attn, depth, acc, d_render, nullptr, nullptr, /*want_d=*/false, /*want_f=*/true,
+                  rs->zero_gradient_first != 0, &layout, nullptr, 0);
   if (st) return st;
   // the TV stencil reads the parameters BEFORE the step overwrites them: its gradient goes through the step's extra-gradient input
   const float* extra = nullptr;
@@ -1121,7 +1121,7 @@ int voxe_clock_probe(int32_t spin, double* shader_hz, void* stream) {
 int voxe_region_debug_layout(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, int64_t out[17]) {
   if (!out) return VOXE_ERR_NULL_POINTER;
   RenderPlan p;
-  const int st = plan_render(grid, cfg, R, nullptr, &p);
+  const int st = plan_render(grid, cfg, R, nullptr, nullptr, &p);
   if (st) return st;
   if (!p.region) return VOXE_ERR_UNSUPPORTED;   // (grid, cfg, R) does not take the space-binned route
   long long t[16];
@@ -1212,7 +1212,7 @@ int voxe_sample_probe(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const 
                       uint8_t* inside, float* zvals, float* sigma, float* rad, void* workspace,
                       size_t workspace_bytes, void* stream) {
   RenderPlan p;
-  const int st = plan_render(grid, cfg, R, jitter, &p);
+  const int st = plan_render(grid, cfg, R, jitter, nullptr, &p);
   if (st) return st;
   if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
   if (!workspace || workspace_bytes < p.l.fwd_total) return VOXE_ERR_WORKSPACE;

@@ -26,6 +26,10 @@ struct FwdArgs {
   int* sched = nullptr;
   // per-tile plan of the launches that build a list (tile_plan_bytes(); nullable: without it the kernels read the list alone)
   int2* plan = nullptr;
+  // space-binned route, voxe_recon_step: the segment tables live at `region_tables` (null: in the route's own scratch) and,
+  // `prebinned`, voxe_recon_prefetch already filled them with these rays' segments
+  void* region_tables = nullptr;
+  bool prebinned = false;
 };
 struct BwdArgs {
   const float *packed, *rays_o, *rays_d, *jitter, *colour, *depth, *acc, *d_colour, *d_depth, *d_acc;
@@ -42,6 +46,7 @@ struct BwdArgs {
   const double* segsum_d = nullptr;   // FwdArgs::segsum_d of the forward of the SAME rays (VoxeDispatch::precise_grad), or null
   const int* sched = nullptr;         // FwdArgs::sched of the forward of the SAME rays, or null
   const int2* plan = nullptr;         // FwdArgs::plan of the forward of the SAME rays, or null
+  void* region_tables = nullptr;      // FwdArgs::region_tables of the forward of the SAME rays
 };
 // Launch-constant device config + the dispatch decisions of THIS call (VoxeRenderCfg::dispatch, NULL = all defaults): kernels
 // take the DevCfg base by value, host-side predicates and launchers read `disp` through the accessors below (0 = default).
@@ -153,12 +158,9 @@ void launch_fwd_region(const DevGrid& g, const HostCfg& c, int deg, int diffuse,
                        hipStream_t st);   // segment tables + forward; leaves the per-segment states in `scratch`
 void launch_bwd_region(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const BwdArgs& a, void* scratch,
                        hipStream_t st);   // needs the tables / states of launch_fwd_region for the same rays
-// r06: the binning passes of launch_fwd_region on their own, into the tables at `tables` (a buffer of region_scratch_bytes), and
-// the override the region launches read while it is set: tables elsewhere than in `scratch` / already filled for these rays
-struct RegionBins { void* tables; int prebinned; hipEvent_t after_fwd; };   // after_fwd (or null): recorded between the region forward and the fold pass
-extern thread_local const RegionBins* tl_region_bins;
+// r06: the binning passes of launch_fwd_region on their own, into the tables at `tables` (a buffer of region_scratch_bytes)
 void launch_bin_region(const DevGrid& g, const HostCfg& c, const float* rays_o, const float* rays_d, const float* jitter, void* tables,
-                       hipStream_t st, int phase = 3);   // phase 1: clear the counters | 2: the passes behind that | 3: both
+                       hipStream_t st);
 // byte offsets of the segment tables inside the region scratch + their dimensions (test aid: voxe_region_debug_layout)
 void region_debug_layout(int X, int Y, int Z, long long R, int S, long long out[16]);
 

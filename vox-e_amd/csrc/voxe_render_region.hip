@@ -1264,11 +1264,10 @@ size_t region_scratch_bytes(int X, int Y, int Z, long long R, int S, bool full_s
 }
 // The segment TABLES (everything the binning passes write: slots, sorted list, counters, block tables) may live in another
 // buffer than the per-segment partials / states: voxe_recon_prefetch bins the NEXT iteration's batch into a second set of tables
-// while this iteration's backward still reads the first (tl_region_bins, set by voxe_recon_step around its render calls).
-thread_local const RegionBins* tl_region_bins = nullptr;
-static BinScratch bin_scratch(const RegionLayout& l, void* scratch, void* tables = nullptr) {
+// while this iteration's backward still reads the first (FwdArgs / BwdArgs::region_tables).  `tables` null: they live in `scratch`.
+static BinScratch bin_scratch(const RegionLayout& l, void* scratch, void* tables) {
   char* base = (char*)scratch;
-  char* tb = tables ? (char*)tables : ((tl_region_bins && tl_region_bins->tables) ? (char*)tl_region_bins->tables : base);
+  char* tb = tables ? (char*)tables : base;
   BinScratch bs;
   bs.slot_region = (unsigned*)(tb + l.slot_region);
   bs.slot_pos = (unsigned*)(tb + l.slot_pos);
@@ -1304,10 +1303,8 @@ static size_t full_tex_lds(K kernel, int cm) {
 // the binning passes (index math only: they read the rays and the jitter streams, never the grid): segments -> counting sort by
 // (region, length class).  Writes the TABLES of `bs` only.
 static void launch_bin_region_passes(const DevGrid& g, const DevCfg& c, const float* rays_o, const float* rays_d, const float* jitter,
-                                     const RegionLayout& l, const BinScratch& bs, hipStream_t st, bool lds_ok, int phase = 3) {
-  // phase: 1 = clear the counters | 2 = everything behind that | 3 = both
-  if (phase & 1) (void)hipMemsetAsync(bs.count, 0, 2 * up256(((size_t)(l.nreg + 1) * kLenClasses + 4) * sizeof(unsigned)), st);
-  if (!(phase & 2)) return;
+                                     const RegionLayout& l, const BinScratch& bs, hipStream_t st, bool lds_ok) {
+  (void)hipMemsetAsync(bs.count, 0, 2 * up256(((size_t)(l.nreg + 1) * kLenClasses + 4) * sizeof(unsigned)), st);
   const int nseg = num_segments(c.S, c.seg_len);
   const int nb = (c.image_width > 0 ? blocks_for_tiles(c.map_mode, (c.image_width + 7) / 8, tile_rows_total(c, 8))
                                     : blocks_for_tiles(c.map_mode, 1, (c.R + 63) / 64)) * nseg;
@@ -1330,17 +1327,17 @@ static void launch_bin_region_passes(const DevGrid& g, const DevCfg& c, const fl
 // ... on their own, into the tables at `tables` (a region scratch, or a buffer of the same size): what launch_fwd_region would do
 // first for these rays (voxe_recon_prefetch; the table offsets do not depend on the grid's SH degree)
 void launch_bin_region(const DevGrid& g, const HostCfg& c, const float* rays_o, const float* rays_d, const float* jitter, void* tables,
-                       hipStream_t st, int phase) {
+                       hipStream_t st) {
   const RegionLayout l = region_layout(g.X, g.Y, g.Z, c.R, c.S, false);
   const BinScratch bs = bin_scratch(l, tables, tables);
-  launch_bin_region_passes(g, c, rays_o, rays_d, jitter, l, bs, st, disp_region_lds_ranks(c.disp), phase);
+  launch_bin_region_passes(g, c, rays_o, rays_d, jitter, l, bs, st, disp_region_lds_ranks(c.disp));
 }
 
 template <int COUT, int NCM, int NCU>
 static void launch_fwd_region_t(const DevGrid& g, const DevCfg& c, const FwdArgs& a, void* scratch, hipStream_t st, bool lds_ok) {
   const RegionLayout l = region_layout(g.X, g.Y, g.Z, c.R, c.S, NCU > 1);
-  const BinScratch bs = bin_scratch(l, scratch);
-  if (!(tl_region_bins && tl_region_bins->prebinned))     // (the tables already hold these rays' segments)
+  const BinScratch bs = bin_scratch(l, scratch, a.region_tables);
+  if (!a.prebinned)     // (otherwise the tables already hold these rays' segments)
     launch_bin_region_passes(g, c, a.rays_o, a.rays_d, a.jitter, l, bs, st, lds_ok);
   const int nseg = num_segments(c.S, c.seg_len);
   // degree 3: staging the 151.6 KB of a region's texels leaves one block (4 waves) per CU
@@ -1348,7 +1345,6 @@ static void launch_fwd_region_t(const DevGrid& g, const DevCfg& c, const FwdArgs
   const size_t lds = (NCU > 1 && stage) ? full_tex_lds(region_fwd_kernel<COUT, NCM, NCU>, COUT * NCM + 1) : 0;
   float4* fwdval = (NCU > 1 && a.keep_samples && VOXE_REGION_FWDVAL) ? (float4*)((char*)scratch + l.fwdval) : nullptr;
   region_fwd_kernel<COUT, NCM, NCU><<<l.nreg + kGenericBlocks, VOXE_REGION_BLOCK, lds, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.jitter, bs, l.nreg, stage, fwdval);
-  if (tl_region_bins && tl_region_bins->after_fwd) (void)hipEventRecord(tl_region_bins->after_fwd, st);
   const int rays_per_block = 256 / nseg;        // (nseg <= 256: region_bwd_supported)
   region_fold_kernel<COUT><<<(int)((c.R + rays_per_block - 1) / rays_per_block), 256, 0, st>>>(
       c, bs, a.colour, a.depth, a.acc, a.disparity, rays_per_block);
@@ -1357,7 +1353,7 @@ static void launch_fwd_region_t(const DevGrid& g, const DevCfg& c, const FwdArgs
 template <int COUT, int NCM, int NCU>
 static void launch_bwd_region_t(const DevGrid& g, const DevCfg& c, const BwdArgs& a, void* scratch, hipStream_t st) {
   const RegionLayout l = region_layout(g.X, g.Y, g.Z, c.R, c.S, NCU > 1);
-  const BinScratch bs = bin_scratch(l, scratch);
+  const BinScratch bs = bin_scratch(l, scratch, a.region_tables);
   if constexpr (NCU == 1) {
     // The parity-class banked window (conflict free, +75 VALU per sample, 32 KB instead of 23.5: 3 blocks per CU instead of 4)
     // pays when the regions are FULL: 160 000 unordered rays 0.79 -> 0.51 ms, 80 000 (8 cameras of 100x100) 0.373 -> 0.357,
