@@ -87,7 +87,7 @@ def test_dead_source_ends_both_keys_and_invalidate_reaches_the_sibling():
     assert not _holds(ws, o) and ws.key is None
     # invalidate(): the sibling a second differentiable forward ran in is a cache of the same grid
     _remember(ws, o)
-    ws.pending, ws.pending_version = True, (0, 0)
+    ws.forward_pending((0, 0))
     sib = ws.for_differentiable_forward((0, 0))
     assert sib is ws.sibling and sib is not ws
     _remember(sib, o)

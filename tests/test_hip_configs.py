@@ -675,7 +675,7 @@ def test_a_false_ray_state_valid_claim_is_served_by_a_re_march(order):
         claim = ops._state_key(ops._pack_key(spec, td, tf), params, to, tdir, None, (4, 6), ops._route(g_, c_, o.shape[0]))
         if mode == "other_rays_in_between":
             ops.render_fwd_into(spec, params, td, tf, to2, tdir2, None, *junk, ws, (4, 6))
-        ws.state_key = claim                            # what a careless C caller passes: ray_state_valid = 1
+        ws.remember_states(claim, to, tdir, None)       # what a careless C caller passes: ray_state_valid = 1
         d_d, d_f = torch.zeros_like(td), torch.zeros_like(tf)
         ops.render_bwd_into(spec, params, td, tf, to, tdir, None, outs[0], outs[1], outs[2], tg, None, None, d_d, d_f, ws, (4, 6))
         got[mode] = (gh.n(d_d), gh.n(d_f))
@@ -717,7 +717,7 @@ def test_a_grid_step_between_forward_and_backward_invalidates_the_claim(tile_alw
     ops.render_bwd_into(spec, params, td, tf, to, tdir, None, fresh[0], fresh[1], fresh[2], gc, None, None, want_d, want_f, ws2, (2, 3))
     assert claim is not None and ws.state_key is None                # (the binding itself drops its claim with the step)
     g_, c_ = ops._descs(spec, params, td, tf, 2, 3, False)
-    ws.state_key = ops._state_key(ops._pack_key(spec, td, tf), params, to, tdir, None, (2, 3), ops._route(g_, c_, o.shape[0]))
+    ws.remember_states(ops._state_key(ops._pack_key(spec, td, tf), params, to, tdir, None, (2, 3), ops._route(g_, c_, o.shape[0])), to, tdir, None)
     got_d, got_f = torch.zeros_like(td), torch.zeros_like(tf)
     ops.render_bwd_into(spec, params, td, tf, to, tdir, None, fresh[0], fresh[1], fresh[2], gc, None, None, got_d, got_f, ws, (2, 3))
     assert rel_l2(gh.n(got_d), gh.n(want_d)) < 2e-6 and rel_l2(gh.n(got_f), gh.n(want_f)) < 2e-6

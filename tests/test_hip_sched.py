@@ -226,7 +226,7 @@ def test_a_block_list_never_outlives_its_forward(case):
             params = on_b
             # a careless caller's claim: "the workspace holds the forward of exactly this backward"
             g_, c_ = ops._descs(spec, params, td, tf, 4, 6, False)
-            ws.state_key = ops._state_key(ops._pack_key(spec, td, tf), params, tob, tdb, None, (4, 6), ops._route(g_, c_, ob.shape[0]))
+            ws.remember_states(ops._state_key(ops._pack_key(spec, td, tf), params, tob, tdb, None, (4, 6), ops._route(g_, c_, ob.shape[0])), tob, tdb, None)
         else:
             params = _params(cfg, hw_b, tile_map=1, tile_qsplit=1)
             outs = _forward(spec, params, td, tf, tob, tdb, ws, (4, 6))

@@ -247,7 +247,7 @@ def test_a_re_march_gives_the_same_truncated_gradient(name, deg, disp):
         ops.render_fwd_into(spec, params, td, tf, to, tdir, None, *outs, ws, c.rng, keep_for_backward=(mode == "honest"))
         if mode == "inference_forward":
             assert ws.state_key is None
-            ws.state_key = ops._state_key(ops._pack_key(spec, td, tf), params, to, tdir, None, c.rng, ops._route(g_, c_, R))
+            ws.remember_states(ops._state_key(ops._pack_key(spec, td, tf), params, to, tdir, None, c.rng, ops._route(g_, c_, R)), to, tdir, None)
         elif mode == "backward_alone":
             ws.invalidate()
         d_d, d_f = torch.zeros_like(td), torch.zeros_like(tf)

@@ -355,7 +355,7 @@ def test_a_plan_never_outlives_its_forward():
             params = on
             # a careless caller's claim: "the workspace holds the forward of exactly this backward"
             g_, c_ = ops._descs(spec, params, td, tf, RNG[0], RNG[1], False)
-            ws.state_key = ops._state_key(ops._pack_key(spec, td, tf), params, tob, tdb, None, RNG, ops._route(g_, c_, ob.shape[0]))
+            ws.remember_states(ops._state_key(ops._pack_key(spec, td, tf), params, tob, tdb, None, RNG, ops._route(g_, c_, ob.shape[0])), tob, tdb, None)
         else:
             params = _params(cfg, width, 0, tile_map=1)
             outs = _forward(spec, params, td, tf, tob, tdb, ws)

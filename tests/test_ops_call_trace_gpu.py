@@ -112,10 +112,10 @@ def test_recon_steps_with_hints(spy):
     wa, wb = ops.Workspace(), ops.Workspace()
     common = (o.spec, p, d, f, wa, wb, h, w, focal_for(w), poses, None, images, batch, True)
     for n in (1, 2, 3):
-        cached = wa.recon_cache
+        cached = wa.recon.last
         ops.recon_step_(*common, st_d, st_f, n, n, 1e-2, losses, (11, 10 * n), zero_gradient_first=(n == 1))
         if n > 1:     # (the shortcut hands the library copies of the cached descriptors and keeps the buffers)
-            assert cached is not None and wa.recon_cache[4] is cached[4] and wa.recon_cache[1] is cached[1]
+            assert cached is not None and wa.recon.last.ws is cached.ws and wa.recon.last.grid is cached.grid
         if n < 3:
             ops.recon_prefetch_(*common, losses, (11, 10 * (n + 1)))
     _check(spy, "recon")

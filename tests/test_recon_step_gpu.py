@@ -222,9 +222,70 @@ def test_recon_step_bounds_its_image_rows_and_a_failed_call_leaves_the_optimiser
         with pytest.raises(VoxeError):           # fewer images than cameras: rejected inside the library call
             opt.reconstruction_step(rp, hw, hw, focal_for(hw), poses, None, images[: K - 1].contiguous(), 4096, True, losses, (5, 1))
         assert opt.state[grid.densities]["step"] == 1 and opt.state[grid.features]["step"] == 1
-        assert ws.deferred.clean_ptr == 0 and ws.key is None      # the next call clears the gradient region and re-packs
+        assert ws.deferred.must_clear(ws.buf) and ws.key is None  # the next call clears the gradient region and re-packs
         opt.reconstruction_step(rp, hw, hw, focal_for(hw), poses, None, images, 4096, True, losses, (5, 2))
         assert opt.state[grid.densities]["step"] == 2 and bool(torch.isfinite(losses).all())
+
+
+class _NoReconStep:
+    """voxe_hip.ops.lib() with a voxe_recon_step that must not be reached; every other entry is the library's"""
+
+    def __init__(self, real):
+        self._real = real
+
+    def __getattr__(self, name):
+        return getattr(self._real, name)
+
+    def voxe_recon_step(self, *args):
+        raise AssertionError("reached the library")
+
+
+def test_recon_step_refuses_malformed_optimiser_state_on_both_paths(monkeypatch):
+    """the grid step writes one value per parameter through the raw pointer of every moment tensor, so
+    recon_step_ checks them -- float32, contiguous, on the grid's device, as many elements as their parameter -- on the
+    cached-descriptor path as on the full marshalling.  While malformed state is tried, voxe_recon_step is replaced by a stub: no
+    such call reaches the device.  Shapes of tests/test_ops_call_trace_gpu.py: the 20 x 24 x 28 SH-0 grid, 4 views of 24 x 32
+    pixels, a batch of 512, diffuse regularisation on."""
+    import cache_cases as cc
+    from voxe_hip.runtime import VoxeError
+
+    o = cc.make_owner("sh0", "f32", DEV)
+    K, h, w, batch = 4, 24, 32, 512
+    poses = torch.stack([torch.cat([p.rotation, p.translation], dim=-1) for p in
+                         (pose_spherical(*synth_pose_angles(i, 100), RADIUS) for i in (3, 38, 12, 58))]).float().to(DEV)
+    images = torch.rand(K, 3, h, w, generator=torch.Generator().manual_seed(1)).to(DEV)
+    d, f = o.densities.detach(), o.features.detach()
+    st_d, st_f = (torch.zeros_like(d), torch.zeros_like(d)), (torch.zeros_like(f), torch.zeros_like(f))
+    losses = torch.zeros(4, device=DEV)
+    p = ops.RenderParams(num_samples=48, near=NEAR, far=FAR, perturb=True, white_bkgd=True)
+    bad_states = {
+        "exp_avg_sq of the densities one element short": ((st_d[0], torch.zeros(d.numel() - 1, device=DEV)), st_f),
+        "float64 exp_avg of the densities": ((st_d[0].double(), st_d[1]), st_f),
+        "state of the features on the CPU": (st_d, (st_f[0].cpu(), st_f[1].cpu())),
+    }
+
+    def step(wa, wb, sd, sf, n):
+        ops.recon_step_(o.spec, p, d, f, wa, wb, h, w, focal_for(w), poses, None, images, batch, True, sd, sf, n, n, 1e-2, losses,
+                        (11, 10 * n), zero_gradient_first=(n == 1))
+
+    wa, wb = ops.Workspace(), ops.Workspace()
+    step(wa, wb, st_d, st_f, 1)
+    record = wa.recon.last
+    assert record is not None and record.ws is wa.buf
+    real = ops.lib()
+    with monkeypatch.context() as m:
+        m.setattr(ops, "lib", lambda: _NoReconStep(real))
+        for pair in ((wa, wb), (ops.Workspace(), ops.Workspace())):     # the cached-descriptor path, the full marshalling
+            for what, (sd, sf) in bad_states.items():
+                with pytest.raises(VoxeError, match="state_"):
+                    step(*pair, sd, sf, 2)
+            assert pair[0] is wa or pair[0].recon.last is None, "a refused call left descriptors behind"
+    # the refused calls cost the loop nothing: the valid state still takes the cached path, on the same descriptors and buffers
+    assert wa.recon.last is record
+    step(wa, wb, st_d, st_f, 2)
+    torch.cuda.synchronize()
+    assert wa.recon.last is not record and wa.recon.last.ws is record.ws and wa.recon.last.grid is record.grid
+    assert bool(torch.isfinite(losses).all())
 
 
 def _prefetch_stats():

@@ -2,11 +2,13 @@
 decide reuse_packed_grid and ray_state_valid) and `Workspace.after_call` (what the buffer holds now) -- with `forget_states`,
 `forget_grid` and the announcement of tensors the library wrote.  Driven directly with CPU tensors, as
 tests/test_cache_keys_host.py drives the pieces underneath; the grids are those of tests/cache_cases.py."""
+import pytest
 import torch
 
 import cache_cases as cc
-from voxe_hip import ops
-from voxe_hip.workspace import DROPPED, UNTOUCHED, DeferredGrad, wrote
+from voxe_hip import abi, ops
+from voxe_hip.runtime import VoxeError
+from voxe_hip.workspace import DROPPED, UNTOUCHED, ReconRecord, wrote
 
 PARAMS = ops.RenderParams(num_samples=6, near=1.0, far=4.0, perturb=True)
 NBYTES = 4096
@@ -79,7 +81,7 @@ def test_forget_states_ends_only_the_state_claim_and_forget_grid_both():
     assert _before(ws, o, r)[1:] == (0, 0, False)
     # forget_grid is this workspace's alone; invalidate() reaches the sibling
     _after(ws, o, r)
-    ws.pending, ws.pending_version = True, (0, 0)
+    ws.forward_pending((0, 0))
     sib = ws.for_differentiable_forward((0, 0))
     _before(sib, o)
     _after(sib, o, r)
@@ -93,11 +95,12 @@ def test_regrow_reports_a_new_buffer_and_drops_both_keys():
     o, r, ws = cc.make_owner("sh0"), _rays(), ops.Workspace()
     old = _before(ws, o)[0]
     _after(ws, o, r)
-    ws.recon_cache = ("descriptors into the old buffer",)
+    ws.recon.step_enqueued(ws, ops.Workspace(), ReconRecord("descriptors into the old buffer", None, None, None, old, None, None))
+    assert ws.recon.last.ws is old
     buf, reuse, valid, fresh = _before(ws, o, r, nbytes=2 * NBYTES)
     assert buf is not old and buf is ws.buf and buf.numel() >= 2 * NBYTES
     assert (reuse, valid, fresh) == (0, 0, True)
-    assert ws.key is None and ws.state_key is None and ws.recon_cache is None
+    assert ws.key is None and ws.state_key is None and ws.recon.last is None
     # a smaller request keeps the buffer
     _after(ws, o, r)
     assert _before(ws, o, r, nbytes=NBYTES) == (buf, 1, 1, False)
@@ -105,19 +108,72 @@ def test_regrow_reports_a_new_buffer_and_drops_both_keys():
 
 def test_regrow_with_a_deferred_gradient_keeps_the_grid_key():
     """deferred-gradient mode with an accumulated gradient: the packed grid and the gradient are copied into the new buffer (on the
-    device; here the key logic alone), so the grid is still held -- the ray states are not -- and `clean_ptr` follows the buffer"""
+    device; here the key logic alone), so the grid is still held -- the ray states are not -- and the known region follows the buffer"""
     o, r, ws = cc.make_owner("sh0"), _rays(), ops.Workspace()
     old = _before(ws, o)[0]
     _after(ws, o, r)
-    ws.deferred = DeferredGrad(dirty=True, clean_ptr=old.data_ptr())
+    ws.attach_deferred(True, True).accumulated(old, abi.GRAD_LINEAR)
     key = ws.key
     buf, reuse, valid, fresh = _before(ws, o, r, nbytes=2 * NBYTES)
     assert buf is not old and fresh
     assert (reuse, valid) == (1, 0) and ws.key == key and ws.state_key is None
-    assert ws.deferred.clean_ptr == buf.data_ptr()
+    assert not ws.deferred.must_clear(buf) and ws.deferred.dirty
     # not dirty: nothing to keep
-    ws.deferred.dirty = False
+    ws.deferred.consumed(buf)
     assert _before(ws, o, nbytes=4 * NBYTES)[1:] == (0, 0, True) and ws.key is None
+
+
+def test_deferred_gradient_state_machine_through_every_transition():
+    """attach -> accumulate -> step -> failed call -> overwritten region -> second attach -> release: after each transition the
+    three questions the entry points ask (clear first? which layout must the next render write? is a gradient waiting?)"""
+    o, ws = cc.make_owner("sh0"), ops.Workspace()
+    buf = _before(ws, o)[0]
+    _after(ws, o)
+    d = ws.attach_deferred(True, False)
+
+    def state(b=buf):
+        return d.must_clear(b), d.expected_layout(), d.dirty
+
+    assert ws.deferred is d and (d.want_densities, d.want_features) == (True, False)
+    assert state(None) == (True, abi.GRAD_ANY, False) and state() == (True, abi.GRAD_ANY, False)
+    d.accumulated(buf, abi.GRAD_LINEAR)
+    assert state() == (False, abi.GRAD_LINEAR, True) and state(None) == (False, abi.GRAD_LINEAR, True)
+    d.consumed(buf)
+    assert state() == (False, abi.GRAD_ANY, False) and state(None)[0] and state(torch.empty_like(buf))[0]
+    ws.call_failed()                                       # ... the region holds a partial gradient, the packed grid may be stale
+    assert state() == (True, abi.GRAD_ANY, False) and ws.key is None and ws.state_key is None
+    d.accumulated(buf, abi.GRAD_ANY)                       # a backward without rays: cleared, nothing accumulated
+    assert state() == (False, abi.GRAD_ANY, False)
+    d.overwritten()                                        # clean: allowed, and the region is no longer known
+    assert state() == (True, abi.GRAD_ANY, False)
+    d.accumulated(buf, abi.GRAD_LINEAR)
+    with pytest.raises(VoxeError, match="would overwrite the accumulated gradient"):
+        d.overwritten()
+    assert state() == (False, abi.GRAD_LINEAR, True)
+    with pytest.raises(RuntimeError, match="already in deferred-gradient mode"):
+        ws.attach_deferred(True, True)
+    assert ws.deferred is d
+    # the finalizer's release: of its own mode only; a dirty region is unknown to whoever attaches next, the grid is re-packed
+    _after(ws, o)
+    assert not ws.detach_deferred(mine=ops.DeferredGrad()) and ws.deferred is d and ws.key is not None
+    assert ws.detach_deferred(mine=d) and ws.deferred is None and ws.key is None
+    nxt = ws.attach_deferred(True, True)
+    assert nxt is not d and nxt.must_clear(buf) and nxt.expected_layout() == abi.GRAD_ANY and not nxt.dirty
+    nxt.consumed(buf)
+    assert not ws.detach_deferred() and ws.deferred is None          # nothing accumulated: nothing left behind
+
+
+def test_recon_scratch_grows_on_demand_and_names_do_not_alias():
+    recon, cpu = ops.Workspace().recon, torch.device("cpu")
+    a = recon.scratch("step", 100, torch.uint8, cpu)
+    assert a.numel() >= 100 and a.dtype == torch.uint8
+    assert recon.scratch("step", 100, torch.uint8, cpu) is a and recon.scratch("step", 40, torch.uint8, cpu) is a
+    b = recon.scratch("step", 101, torch.uint8, cpu)
+    assert b is not a and b.numel() >= 101 and recon.scratch("step", 100, torch.uint8, cpu) is b
+    c = recon.scratch("refine", 101, torch.uint8, cpu)
+    assert c is not b and c.data_ptr() != b.data_ptr() and recon.scratch("step", 101, torch.uint8, cpu) is b
+    f = recon.scratch("refine_losses", 2, torch.float32, cpu)
+    assert f.dtype == torch.float32 and f.numel() == 2 and recon.scratch("refine", 101, torch.uint8, cpu) is c
 
 
 def test_wrote_bumps_exactly_the_tensors_given():

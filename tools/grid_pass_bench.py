@@ -79,7 +79,7 @@ def main():
     dd, ff = dens.clone(), feat.clone()
     st_d, st_f = (torch.zeros_like(dd), torch.zeros_like(dd)), (torch.zeros_like(ff), torch.zeros_like(ff))
     ws = ops.Workspace()
-    ws.buf = torch.zeros(L.voxe_workspace_bytes(C.byref(gdesc), None, 0), dtype=torch.uint8, device=dev)
+    ws.ensure(L.voxe_workspace_bytes(C.byref(gdesc), None, 0), dev).zero_()
     cnt = [0]
 
     def sds_r03():

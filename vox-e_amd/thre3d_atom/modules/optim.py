@@ -80,15 +80,10 @@ class FusedGridAdam(torch.optim.Optimizer):
         self.workspace = voxel_grid.voxe_workspace(kind)
         train_d = any(p is self._dens for p in params)
         train_f = any(p is self._feat for p in params)
-        live = self.workspace.deferred
-        if live is not None:
-            raise RuntimeError("FusedGridAdam: this grid is already in deferred-gradient mode (another FusedGridAdam is "
-                               "attached to it); detach() that optimiser first")
-        mine = _ops.DeferredGrad(want_densities=train_d, want_features=train_f)
-        self.workspace.deferred = mine
+        mine = self.workspace.attach_deferred(train_d, train_f)    # (raises while another FusedGridAdam is attached to the grid)
         self._train = (train_d, train_f)
         # dropped without detach() (an exception unwound the training loop, the caller forgot): leave the mode anyway
-        self._finalizer = weakref.finalize(self, FusedGridAdam._release, self.workspace, mine)
+        self._finalizer = weakref.finalize(self, self.workspace.detach_deferred, mine)
         self._dcl = None          # (reference densities, weight, kind): density regulariser evaluated inside step()
         self.dcl_loss = None      # device scalar: its unweighted value at the last step()
         self._featcorr = None     # (reference features, weight): feature-correlation regulariser evaluated inside step()
@@ -135,14 +130,6 @@ class FusedGridAdam(torch.optim.Optimizer):
         self._featcorr = (ref, float(weight))
         self.featcorr_loss = torch.zeros((), dtype=torch.float32, device=self._feat.device)
 
-    @staticmethod
-    def _release(workspace, mine) -> None:
-        if workspace.deferred is mine:
-            if mine.dirty:
-                workspace.invalidate()
-                mine.clean_ptr = 0     # (the region holds an unconsumed gradient: whoever attaches next clears it first)
-            workspace.deferred = None
-
     def __enter__(self):
         return self
 
@@ -153,17 +140,15 @@ class FusedGridAdam(torch.optim.Optimizer):
     def detach(self) -> None:
         """leave the deferred-gradient mode (renders return ordinary .grad tensors again)"""
         self._finalizer.detach()
-        if self.workspace.deferred is not None and self.workspace.deferred.dirty:
-            self.workspace.invalidate()   # (an unconsumed gradient would otherwise leak into a later fused step)
+        if self.workspace.detach_deferred():
             _ops.workspace_grad_view(self.spec, self._dens, self._feat, self.workspace).zero_()
-        self.workspace.deferred = None
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         super().zero_grad(set_to_none=True)
         d = self.workspace.deferred
         if d is not None and d.dirty:          # a gradient nobody stepped on: clear the region
             _ops.workspace_grad_view(self.spec, self._dens, self._feat, self.workspace).zero_()
-            d.dirty, d.layout = False, _ops.abi.GRAD_ANY
+            d.consumed(self.workspace.buf)
 
     def _state_of(self, p):
         state = self.state[p]
@@ -197,20 +182,14 @@ class FusedGridAdam(torch.optim.Optimizer):
         step_d = (st_d["step"] if st_d is not None else st_f["step"]) + 1
         step_f = (st_f["step"] if st_f is not None else step_d - 1) + 1
         ws = self.workspace
-        if ws.sibling is None:
-            ws.sibling = _ops.Workspace()
-        fresh = ws.buf is None or d.clean_ptr != ws.buf.data_ptr()
         try:
-            _ops.recon_step_(self.spec, render_params, self._dens, self._feat, ws, ws.sibling, height, width, focal, poses,
+            _ops.recon_step_(self.spec, render_params, self._dens, self._feat, ws, ws.partner(), height, width, focal, poses,
                              image_rows, images, batch, diffuse_regularisation,
                              None if st_d is None else (st_d["exp_avg"], st_d["exp_avg_sq"]),
                              None if st_f is None else (st_f["exp_avg"], st_f["exp_avg_sq"]), step_d, step_f, group["lr"],
-                             losses, rng, beta1=beta1, beta2=beta2, eps=group["eps"], zero_gradient_first=fresh)
+                             losses, rng, beta1=beta1, beta2=beta2, eps=group["eps"], zero_gradient_first=d.must_clear(ws.buf))
         except Exception:
-            # the call may have failed BEHIND its first backward (e.g. the diffuse pass was rejected): the gradient region
-            # then holds a partial gradient and the packed grid may be stale -- the next call must clear / re-pack first
-            d.clean_ptr = 0
-            ws.invalidate()
+            ws.call_failed()   # (e.g. the diffuse pass was rejected, behind the specular backward)
             raise
         # This path does not go through Optimizer.step(): registered step pre / post hooks are NOT invoked; the scheduler's
         # "optimizer.step() before lr_scheduler.step()" check is told that a step happened.
@@ -218,8 +197,7 @@ class FusedGridAdam(torch.optim.Optimizer):
         for st in (st_d, st_f):
             if st is not None:
                 st["step"] += 1
-        d.clean_ptr = ws.buf.data_ptr()
-        d.dirty, d.layout = False, _ops.abi.GRAD_ANY
+        d.consumed(ws.buf)
 
     @torch.no_grad()
     def reconstruction_prefetch(self, render_params, height: int, width: int, focal: float, poses, image_rows, images,
@@ -229,9 +207,9 @@ class FusedGridAdam(torch.optim.Optimizer):
         iteration's backward and Adam step run.  A hint -- results never depend on it; call it right after
         reconstruction_step, with `poses` / `image_rows` that were COMPUTED before that step was enqueued (the side stream
         is ordered behind that step's forward, not behind this call)."""
-        if self.kind != "sh" or self.workspace.deferred is None or self.workspace.sibling is None:
+        if self.kind != "sh" or self.workspace.deferred is None:
             return
-        _ops.recon_prefetch_(self.spec, render_params, self._dens, self._feat, self.workspace, self.workspace.sibling, height,
+        _ops.recon_prefetch_(self.spec, render_params, self._dens, self._feat, self.workspace, self.workspace.partner(), height,
                              width, focal, poses, image_rows, images, batch, diffuse_regularisation, losses, rng)
 
     @torch.no_grad()
@@ -261,20 +239,17 @@ class FusedGridAdam(torch.optim.Optimizer):
         beta1, beta2 = group["betas"]
         st = self._state_of(self._feat)
         ws = self.workspace
-        fresh = ws.buf is None or d.clean_ptr != ws.buf.data_ptr()
         try:
             _ops.attn_refine_step_(self.spec, render_params, self._dens.detach(), self._feat.detach(), rays_o, rays_d,
                                    attn_map.detach().to(torch.float32).contiguous(), ws, st["step"] + 1, group["lr"],
                                    (st["exp_avg"], st["exp_avg_sq"]), tv_weight, losses, rng, beta1=beta1, beta2=beta2,
-                                   eps=group["eps"], attn_render=attn_render, zero_gradient_first=fresh)
+                                   eps=group["eps"], attn_render=attn_render, zero_gradient_first=d.must_clear(ws.buf))
         except Exception:
-            d.clean_ptr = 0
-            ws.invalidate()
+            ws.call_failed()
             raise
         self._opt_called = True      # (not through Optimizer.step(): see reconstruction_step)
         st["step"] += 1          # (the binding bumped the tensor versions: the detached views share their counters)
-        d.clean_ptr = ws.buf.data_ptr()
-        d.dirty, d.layout = False, _ops.abi.GRAD_ANY
+        d.consumed(ws.buf)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -332,5 +307,5 @@ class FusedGridAdam(torch.optim.Optimizer):
         for st in (st_d, st_f):
             if st is not None:
                 st["step"] += 1
-        d.dirty, d.layout = False, _ops.abi.GRAD_ANY
+        d.consumed(self.workspace.buf)
         return loss

@@ -18,7 +18,7 @@ from .gridops import (cc_largest_k, extract_mesh, graph_build, graphcut, grid_re
 from .losses import (adam_step_, attn_masked_l1, density_correlation_loss, density_diff_loss, distortion_fwd_bwd,  # noqa: F401
                      distortion_loss, feature_correlation_loss, tv_loss_on_grid)
 from .runtime import VoxeError, check, ensure_gfx950, f32c, lib, ptr, require_device, stream_ptr
-from .workspace import DROPPED, DeferredGrad, Workspace, wrote, _pack_key, _scratch_for, _state_key  # noqa: F401
+from .workspace import DROPPED, DeferredGrad, ReconRecord, Workspace, wrote, _pack_key, _scratch_for, _state_key  # noqa: F401
 
 
 def _render_ws_bytes(L, g, c, R) -> int:
@@ -115,7 +115,7 @@ class _RenderFn(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:  # (grad mode itself is off inside Function.forward)
             version = (densities._version, features._version)
             workspace = workspace.for_differentiable_forward(version)
-            workspace.pending, workspace.pending_version = True, version
+            workspace.forward_pending(version)
         render_fwd_into(spec, params, dens, feat, ro, rd, jit, colour, depth, acc, disp, workspace, rng,
                         keep_for_backward=bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1]), source=(densities, features))
         ctx.spec, ctx.params, ctx.workspace, ctx.rng = spec, params, workspace, rng
@@ -158,35 +158,27 @@ class _RenderFn(torch.autograd.Function):
                 and feat.data_ptr() == features.data_ptr():
             # deferred-gradient mode: the gradient stays in the MAIN workspace's gradient region (kernel layout) for the
             # fused grid step; autograd sees no gradient for the two grid tensors
-            # (the region of a buffer this mode has not written yet holds whatever torch.empty returned)
-            fresh = (not deferred.dirty) and deferred.clean_ptr != main.buf.data_ptr()
             if not params.linear_grad:   # every render of the step writes the SAME (linear) gradient layout
                 params = dataclasses.replace(params, linear_grad=True)
             layout = render_bwd_acc(spec, params, dens, feat, ro, rd, jit, colour, depth, acc, g_colour, g_depth, g_acc,
-                                    workspace, ctx.rng, zero_first=fresh,
+                                    workspace, ctx.rng, zero_first=deferred.must_clear(main.buf),
                                     want_densities=bool(need_d and deferred.want_densities),
                                     want_features=bool(need_f and deferred.want_features),
                                     grad_workspace=(main if workspace is not main else None),
-                                    expect_layout=deferred.layout if deferred.dirty else abi.GRAD_ANY, source=(densities, features))
+                                    expect_layout=deferred.expected_layout(), source=(densities, features))
             if layout is not None:
-                deferred.clean_ptr = main.buf.data_ptr()
-                if layout != abi.GRAD_ANY:
-                    deferred.layout = layout
-                    deferred.dirty = True
-                workspace.pending = False
+                deferred.accumulated(main.buf, layout)
+                workspace.backward_ran()
                 return None, None
             # (the kernel that fits this render writes another gradient layout than what the region holds -- cannot happen
             #  with linear_grad -- : ordinary path; its un-pack leaves a gradient in ITS workspace's region)
             if workspace is main:
-                if deferred.dirty:
-                    raise VoxeError("deferred-gradient mode: a render with another gradient layout would overwrite the "
-                                    "accumulated gradient")
-                deferred.clean_ptr = 0
+                deferred.overwritten()
         d_dens = torch.empty_like(dens) if need_d else None
         d_feat = torch.empty_like(feat) if need_f else None
         render_bwd_into(spec, params, dens, feat, ro, rd, jit, colour, depth, acc, g_colour, g_depth, g_acc,
                         d_dens, d_feat, workspace, ctx.rng, source=(densities, features))
-        workspace.pending = False
+        workspace.backward_ran()
         return d_dens, d_feat
 
 
@@ -433,9 +425,7 @@ def attn_refine_step_(spec: GridSpec, params: RenderParams, densities, attn, ray
     if losses is None and tv_weight != 0.0:
         # the TV pass writes its loss value wherever it runs, and it runs for the gradient whenever tv_weight != 0: the library
         # is never handed NULL there (a null store on the device otherwise); the values go to a scratch pair nobody reads
-        losses = workspace.recon_scratch.get("refine_losses")
-        if losses is None or losses.device != device:
-            losses = workspace.recon_scratch["refine_losses"] = torch.empty(2, dtype=torch.float32, device=device)
+        losses = workspace.recon.scratch("refine_losses", 2, torch.float32, device)
         # (`tv_loss_always` asks for the TV VALUE when tv_weight == 0; nobody reads the value here, and tv_weight != 0 runs the
         #  pass anyway: off, so that the flag never becomes the reason for a launch)
         tv_loss_always = False
@@ -449,10 +439,7 @@ def attn_refine_step_(spec: GridSpec, params: RenderParams, densities, attn, ray
         ws, c.reuse_packed_grid, fresh, _ = workspace.before_call(spec, densities, attn, _render_ws_bytes(L, g, c, R), device)
         # (a buffer this call allocated holds whatever torch.empty returned in its gradient region)
         rs.zero_gradient_first = int(bool(zero_gradient_first) or fresh)
-        need = L.voxe_attn_refine_scratch_bytes(C.byref(g), R)
-        sc = workspace.recon_scratch.get("refine")
-        if sc is None or sc.numel() < need or sc.device != ws.device:
-            sc = workspace.recon_scratch["refine"] = torch.empty(need, dtype=torch.uint8, device=device)
+        sc = workspace.recon.scratch("refine", L.voxe_attn_refine_scratch_bytes(C.byref(g), R), torch.uint8, device)
         check(L.voxe_attn_refine_step(C.byref(g), C.byref(c), C.byref(rs), ptr(rays_o), ptr(rays_d), R, ptr(ws), ws.numel(),
                                       ptr(sc), sc.numel(), stream_ptr(device)), "voxe_attn_refine_step")
     wrote(attn, state[0], state[1])
@@ -464,7 +451,7 @@ def _recon_call(entry: str, spec: GridSpec, params: RenderParams, densities, fea
                 height: int, width: int, focal: float, poses: torch.Tensor, image_rows: Optional[torch.Tensor],
                 images: torch.Tensor, batch: int, diffuse_regularisation: bool, state_densities, state_features,
                 step_densities: int, step_features: int, lr: float, losses: torch.Tensor, rng: Tuple[int, int],
-                beta1: float, beta2: float, eps: float, zero_gradient_first: bool, scratch_holder: Optional[dict]):
+                beta1: float, beta2: float, eps: float, zero_gradient_first: bool):
     """argument marshalling shared by voxe_recon_step and voxe_recon_prefetch (the hint must announce EXACTLY what the step
     will pass: same descriptors, same buffers, same sizes)"""
     device = densities.device
@@ -485,9 +472,9 @@ def _recon_call(entry: str, spec: GridSpec, params: RenderParams, densities, fea
     rs.poses, rs.images, rs.image_rows = ptr(poses), ptr(images), ptr(image_rows)
     rs.num_images = int(images.shape[0])
     rs.K, rs.batch, rs.diffuse_regularisation = int(poses.shape[0]), int(batch), int(bool(diffuse_regularisation))
-    moments = _recon_optimiser(rs, state_densities, state_features, step_densities, step_features, lr, beta1, beta2, eps)
+    moments = _recon_optimiser(rs, densities, features, state_densities, state_features, step_densities, step_features, lr, beta1,
+                               beta2, eps)
     rs.losses = ptr(losses)
-    holder = scratch_holder if scratch_holder is not None else workspace.recon_scratch
     with torch.cuda.device(device):
         nbytes = L.voxe_workspace_bytes(C.byref(g), C.byref(c), int(batch))
         if diffuse_regularisation and p.sh_degree == 0:
@@ -503,19 +490,18 @@ def _recon_call(entry: str, spec: GridSpec, params: RenderParams, densities, fea
             # (SH-0: it holds the second set of segment tables, the one voxe_recon_prefetch fills ahead)
             _, c2 = _descs(spec, dataclasses.replace(p, render_diffuse=True), densities, features, rng[0], rng[1], False)
             ws2 = workspace2.ensure(max(nbytes, L.voxe_workspace_bytes(C.byref(g), C.byref(c2), int(batch))), device)
-        need = L.voxe_recon_scratch_bytes(int(batch))
-        sc = holder.get("buf")
-        if sc is None or sc.numel() < need or sc.device != ws.device:
-            if sc is not None and workspace.prefetch_inflight:
-                torch.cuda.synchronize(device)     # (the library's side stream may still be writing the old buffer)
-                workspace.prefetch_inflight = False
-            sc = holder["buf"] = torch.empty(need, dtype=torch.uint8, device=device)
+        sc = workspace.recon.scratch("step", L.voxe_recon_scratch_bytes(int(batch)), torch.uint8, device, hinted=workspace)
     return L, g, c, rs, ws, ws2, sc, moments
 
 
-def _recon_optimiser(rs, state_densities, state_features, step_densities, step_features, lr, beta1, beta2, eps):
-    """fill in the optimiser's share of a VoxeReconStep; -> (exp_avg, exp_avg_sq) of the densities and of the features"""
+def _recon_optimiser(rs, densities, features, state_densities, state_features, step_densities, step_features, lr, beta1, beta2, eps):
+    """fill in the optimiser's share of a VoxeReconStep; -> (exp_avg, exp_avg_sq) of the densities and of the features.  The grid
+    step writes every moment tensor through its raw pointer, one value per parameter: checked on every call, cached path or not"""
     (m_d, v_d), (m_f, v_f) = _moments(state_densities), _moments(state_features)
+    for nm, t, p in (("state_densities", m_d, densities), ("state_densities", v_d, densities), ("state_features", m_f, features),
+                     ("state_features", v_f, features)):
+        if t is not None:
+            _require_buffer("recon_step_", nm, t, numel=p.numel(), device=p.device)
     rs.lr, rs.beta1, rs.beta2, rs.eps = float(lr), float(beta1), float(beta2), float(eps)
     rs.step_densities, rs.step_features = int(step_densities), int(step_features)
     rs.exp_avg_densities, rs.exp_avg_sq_densities = ptr(m_d), ptr(v_d)
@@ -532,32 +518,11 @@ def _recon_key(spec, params, densities, features, height, width, focal, images, 
             images.is_contiguous(), int(batch), bool(diffuse_regularisation), losses.data_ptr(), losses.dtype, losses.numel())
 
 
-def _recon_cached_descs(key, workspace: Workspace, workspace2: Workspace, poses, image_rows, rng, scratch_holder):
-    """(g, c, rs, ws, ws2, sc) of the last recon_step_ of `workspace` -- copies of its descriptors with this call's cameras and
-    streams, its buffers -- when that step ran the same loop (`key`: grid, images, batch; the cameras' shape; the buffers still in
-    place), else None: the full marshalling (_recon_call) is then the step's business, and a hint announces nothing"""
-    cache = workspace.recon_cache
-    if not (cache is not None and scratch_holder is None and cache[0] == key and cache[4] is workspace.buf
-            and cache[5] is workspace2.buf):
-        return None
-    K = cache[3].K      # (the cameras: another K, dtype or layout than the descriptors were built for)
-    if not (poses.is_cuda and poses.dtype == torch.float32 and poses.is_contiguous() and tuple(poses.shape) == (K, 3, 4)
-            and (image_rows is None or (image_rows.is_cuda and image_rows.dtype == torch.int64 and image_rows.numel() == K))):
-        return None
-    _, g, c0, rs0, ws, ws2, sc = cache
-    c = type(c0).from_buffer_copy(c0)
-    rs = type(rs0).from_buffer_copy(rs0)
-    c.seed, c.rng_offset = int(rng[0]) & 0xFFFFFFFFFFFFFFFF, int(rng[1]) & 0xFFFFFFFFFFFFFFFF
-    rs.poses, rs.image_rows = ptr(poses), ptr(image_rows)
-    return g, c, rs, ws, ws2, sc
-
-
 def recon_step_(spec: GridSpec, params: RenderParams, densities, features, workspace: Workspace, workspace2: Workspace,
                 height: int, width: int, focal: float, poses: torch.Tensor, image_rows: Optional[torch.Tensor],
                 images: torch.Tensor, batch: int, diffuse_regularisation: bool, state_densities, state_features,
                 step_densities: int, step_features: int, lr: float, losses: torch.Tensor, rng: Tuple[int, int],
-                beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, zero_gradient_first: bool = True,
-                scratch_holder: Optional[dict] = None) -> None:
+                beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, zero_gradient_first: bool = True) -> None:
     """voxe_recon_step: one reconstruction iteration (random pixel batch over the K cameras `poses` -> specular
     [+ diffuse] render -> L1 loss(es) against `images` -> backward -> Adam on both grid tensors) in ONE library call.
     `losses` [4] float32 on the device receives (L1 specular, MSE specular, L1 diffuse, MSE diffuse).  The jitter /
@@ -565,29 +530,27 @@ def recon_step_(spec: GridSpec, params: RenderParams, densities, features, works
     `workspace` holds the updated grid packed and a cleared gradient region."""
     device = densities.device
     key = _recon_key(spec, params, densities, features, height, width, focal, images, batch, diffuse_regularisation, losses)
-    cached = _recon_cached_descs(key, workspace, workspace2, poses, image_rows, rng, scratch_holder)
+    cached = workspace.recon.descriptors(key, workspace.buf, workspace2.buf, poses, image_rows, rng)
     if cached is not None:
         # the same loop as the last call: only the optimiser's state and the flags are filled in -- the trainer's loop is paced by
         # this function's host time
         L = lib()
         g, c, rs, ws, ws2, sc = cached
         c.reuse_packed_grid = int(workspace.holds(spec, densities, features))
-        moments = _recon_optimiser(rs, state_densities, state_features, step_densities, step_features, lr, beta1, beta2, eps)
+        moments = _recon_optimiser(rs, densities, features, state_densities, state_features, step_densities, step_features, lr,
+                                   beta1, beta2, eps)
         rs.zero_gradient_first = int(bool(zero_gradient_first))
     else:
         L, g, c, rs, ws, ws2, sc, moments = _recon_call(
             "recon_step_", spec, params, densities, features, workspace, workspace2, height, width, focal, poses, image_rows, images,
             batch, diffuse_regularisation, state_densities, state_features, step_densities, step_features, lr, losses, rng, beta1,
-            beta2, eps, zero_gradient_first, scratch_holder)
+            beta2, eps, zero_gradient_first)
     with torch.cuda.device(device):
         check(L.voxe_recon_step(C.byref(g), C.byref(c), C.byref(rs), ptr(ws), ws.numel(), ptr(ws2),
                                 0 if ws2 is None else ws2.numel(), ptr(sc), sc.numel(), stream_ptr(device)), "voxe_recon_step")
-    workspace.prefetch_inflight = False                    # (the step waited for the side stream, hint taken or not)
-    workspace2.prefetch_inflight = False
     # what a hint for the NEXT iteration has to repeat (recon_prefetch_ copies these descriptors instead of building them again:
     # the hint's host time is on the iteration's critical path once the device work is hidden)
-    workspace.recon_cache = (key, g, c, rs, ws, ws2, sc)
-    workspace.prefetch_keepalive = None
+    workspace.recon.step_enqueued(workspace, workspace2, ReconRecord(key, g, c, rs, ws, ws2, sc))
     wrote(densities, features, *moments)
     workspace.after_call(spec, densities, features, DROPPED)          # the workspace holds the updated grid packed
     workspace2.forget_grid()                               # (its packed grid is the previous iteration's)
@@ -595,19 +558,19 @@ def recon_step_(spec: GridSpec, params: RenderParams, densities, features, works
 
 def recon_prefetch_(spec: GridSpec, params: RenderParams, densities, features, workspace: Workspace, workspace2: Workspace,
                     height: int, width: int, focal: float, poses: torch.Tensor, image_rows: Optional[torch.Tensor],
-                    images: torch.Tensor, batch: int, diffuse_regularisation: bool, losses: torch.Tensor, rng: Tuple[int, int],
-                    scratch_holder: Optional[dict] = None) -> None:
+                    images: torch.Tensor, batch: int, diffuse_regularisation: bool, losses: torch.Tensor, rng: Tuple[int, int]) -> None:
     """voxe_recon_prefetch: announce the NEXT recon_step_ (same arguments; `poses`, `image_rows` and `rng` are the next
     iteration's; everything else must equal the last recon_step_ of this workspace, otherwise nothing is announced).  The library
     assembles that iteration's batch and segment tables on a stream of its own while the current iteration's backward and grid
     step run; the next recon_step_ takes them iff its arguments are the announced ones.  A hint: results never depend on it, and
     no buffer is ever allocated, grown or moved by it.  Call it right after recon_step_ (both workspaces and the scratch exist by then and keep
-    their addresses); `poses` / `image_rows` are kept alive until the next recon_step_ of this workspace."""
+    their addresses); `poses` / `image_rows` are kept alive until the next recon_step_ of this workspace, and the caller must not
+    modify them in between: the step recognises its hint by their addresses, not by their values."""
     device = densities.device
     if workspace.buf is None:
         return                                             # (no step has sized the buffers yet: nothing to announce against)
     key = _recon_key(spec, params, densities, features, height, width, focal, images, batch, diffuse_regularisation, losses)
-    cached = _recon_cached_descs(key, workspace, workspace2, poses, image_rows, rng, scratch_holder)
+    cached = workspace.recon.descriptors(key, workspace.buf, workspace2.buf, poses, image_rows, rng)
     if cached is None:
         # Anything else (another batch size, grid, image stack, ... than the last step's) is not announced: marshalling it afresh
         # could regrow a workspace, and a hint must never move a buffer -- the caller's knowledge of what its workspace holds
@@ -618,10 +581,7 @@ def recon_prefetch_(spec: GridSpec, params: RenderParams, densities, features, w
     with torch.cuda.device(device):
         check(L.voxe_recon_prefetch(C.byref(g), C.byref(c), C.byref(rs), ptr(ws), ws.numel(), ptr(ws2),
                                     0 if ws2 is None else ws2.numel(), ptr(sc), sc.numel(), stream_ptr(device)), "voxe_recon_prefetch")
-    workspace.prefetch_inflight = True
-    if workspace2 is not None:
-        workspace2.prefetch_inflight = True
-    workspace.prefetch_keepalive = (poses, image_rows, images)
+    workspace.recon.hint_issued(workspace, workspace2, (poses, image_rows, images))
 
 
 @torch.no_grad()

@@ -1,8 +1,13 @@
-"""The caller-owned workspace of the render, query and fused-step entry points and the protocol of its two caches: "the buffer still
-holds this grid packed" (VoxeRenderCfg::reuse_packed_grid) and "it still holds this forward's ray states" (::ray_state_valid).
-Plain Python over tensors: no library call is made here.  An entry point of voxe_hip.ops prepares its arguments, asks
-`Workspace.before_call`, calls the library and tells `Workspace.after_call`."""
+"""The caller-owned workspace of the render, query and fused-step entry points and the protocols that live on it.  Plain Python
+over tensors: no library call is made here, and nothing outside this module assigns an attribute of its classes.
+* the two caches, "the buffer still holds this grid packed" (VoxeRenderCfg::reuse_packed_grid) and "it still holds this forward's ray
+  states" (::ray_state_valid): an entry point of voxe_hip.ops asks `Workspace.before_call`, calls the library, tells `after_call`;
+* the deferred-gradient mode (`DeferredGrad`, `Workspace.attach_deferred` / `detach_deferred` / `call_failed`): must the gradient
+  region be cleared before a backward accumulates into it;
+* the reconstruction loop (`ReconLoop` = `Workspace.recon`): the last step's descriptors, named scratch, a hint in flight;
+* a differentiable forward waiting for its backward (`forward_pending`, `backward_ran`, `partner`)."""
 import weakref
+from collections import namedtuple
 from dataclasses import dataclass
 from operator import attrgetter
 from typing import Optional
@@ -11,6 +16,7 @@ import torch
 
 from . import abi
 from . import dispatch as _dispatch
+from .runtime import VoxeError, ptr
 
 # what a library call did to the ray states (Workspace.after_call; a tuple names the forward whose states it left)
 UNTOUCHED, DROPPED = "untouched", "dropped"
@@ -25,6 +31,80 @@ class DeferredGrad:
     want_densities: bool = True
     want_features: bool = True
     clean_ptr: int = 0        # data_ptr of the workspace buffer whose gradient region is known to be cleared / in use
+
+    def must_clear(self, buf) -> bool:
+        """THE question "clear the region first" (a buffer this mode has not written holds whatever torch.empty returned)"""
+        return not self.dirty and (buf is None or self.clean_ptr != buf.data_ptr())
+
+    def expected_layout(self) -> int:
+        return self.layout if self.dirty else abi.GRAD_ANY
+
+    def accumulated(self, buf, layout: int) -> None:
+        """a backward left a gradient of `layout` in the region of `buf` (GRAD_ANY: no rays, nothing but the clearing)"""
+        self.clean_ptr = buf.data_ptr()
+        if layout != abi.GRAD_ANY:
+            self.layout, self.dirty = layout, True
+
+    def consumed(self, buf) -> None:
+        """an optimiser step (or zero_grad) took the gradient and left the region of `buf` cleared"""
+        self.clean_ptr = buf.data_ptr()
+        self.dirty, self.layout = False, abi.GRAD_ANY
+
+    def overwritten(self) -> None:
+        """a backward of the ordinary path is about to un-pack ANOTHER gradient layout through the region"""
+        if self.dirty:
+            raise VoxeError("deferred-gradient mode: a render with another gradient layout would overwrite the "
+                            "accumulated gradient")
+        self.clean_ptr = 0
+
+
+# what the last recon_step_ handed the library: its descriptors (the next call of the same loop copies them) and its buffers
+ReconRecord = namedtuple("ReconRecord", "key grid cfg step ws ws2 scratch")
+
+
+class ReconLoop:
+    """Python state of the fused iterations (recon_step_ / recon_prefetch_, attn_refine_step_) that run in one workspace"""
+
+    def __init__(self):
+        self.last: Optional[ReconRecord] = None   # of the last recon_step_ (what a hint for the next one repeats)
+        self.buffers = {}                         # name -> device scratch of the fused iterations
+        self.keepalive = None                     # what the library's side stream reads until the next step is enqueued
+
+    def scratch(self, name: str, numel: int, dtype, device, hinted: Optional["Workspace"] = None) -> torch.Tensor:
+        """the scratch tensor `name`, at least `numel` x `dtype` on `device`, grown on demand (`hinted`: a workspace whose hint uses it)"""
+        buf = self.buffers.get(name)
+        if buf is None or buf.numel() < numel or buf.dtype != dtype or buf.device != torch.device(device):
+            if buf is not None and hinted is not None and hinted.hint_inflight:
+                torch.cuda.synchronize(buf.device)     # (the side stream of `hinted`'s hint may still be writing the old buffer)
+                hinted.hint_inflight = False
+            buf = self.buffers[name] = torch.empty(numel, dtype=dtype, device=device)
+        return buf
+
+    def descriptors(self, key, buf, buf2, poses, image_rows, rng):
+        """(g, c, rs, ws, ws2, sc) of the last recon_step_ -- copies of its descriptors with this call's cameras and streams, its
+        buffers -- when that step ran the same loop (`key`: grid, images, batch; the cameras' shape; the two workspaces' buffers
+        `buf` / `buf2` still in place), else None: the full marshalling is then the step's business, and a hint announces nothing"""
+        last = self.last
+        if not (last is not None and last.key == key and last.ws is buf and last.ws2 is buf2):
+            return None
+        K = last.step.K      # (the cameras: another K, dtype or layout than the descriptors were built for)
+        if not (poses.is_cuda and poses.dtype == torch.float32 and poses.is_contiguous() and tuple(poses.shape) == (K, 3, 4)
+                and (image_rows is None or (image_rows.is_cuda and image_rows.dtype == torch.int64 and image_rows.numel() == K))):
+            return None
+        c, rs = type(last.cfg).from_buffer_copy(last.cfg), type(last.step).from_buffer_copy(last.step)
+        c.seed, c.rng_offset = int(rng[0]) & 0xFFFFFFFFFFFFFFFF, int(rng[1]) & 0xFFFFFFFFFFFFFFFF
+        rs.poses, rs.image_rows = ptr(poses), ptr(image_rows)
+        return last.grid, c, rs, last.ws, last.ws2, last.scratch
+
+    def hint_issued(self, workspace: "Workspace", workspace2: "Workspace", keepalive) -> None:
+        """until the next step is enqueued the library's side stream may be writing both buffers and reading `keepalive`"""
+        workspace.hint_inflight = workspace2.hint_inflight = True
+        self.keepalive = keepalive
+
+    def step_enqueued(self, workspace: "Workspace", workspace2: "Workspace", record: ReconRecord) -> None:
+        """(the step waited for the side stream, hint taken or not)"""
+        workspace.hint_inflight = workspace2.hint_inflight = False
+        self.last, self.keepalive = record, None
 
 
 class Workspace:
@@ -49,17 +129,13 @@ class Workspace:
         # deferred-gradient mode (FusedGridAdam): backward passes of renders through this workspace (or its sibling)
         # LEAVE the grid gradient in this workspace's gradient region instead of returning .grad tensors
         self.deferred: Optional["DeferredGrad"] = None
-        self.recon_scratch: dict = {}   # device scratch of recon_step_ (rays, targets, outputs of one fused iteration)
-        # recon_prefetch_: the library's side stream may be writing into this buffer (and reading `prefetch_keepalive`) until the
-        # next recon_step_ of the owning workspace has been enqueued
-        self.prefetch_inflight = False
-        self.prefetch_keepalive = None
-        self.recon_cache = None         # descriptors of the last recon_step_ (what a hint for the next one repeats)
+        self.recon = ReconLoop()
+        self.hint_inflight = False      # set and cleared by ReconLoop.hint_issued / step_enqueued on both workspaces of the pair
 
     def __del__(self):
         # a hint in flight (recon_prefetch_) writes this buffer from a stream torch's caching allocator knows nothing about
         try:
-            if self.prefetch_inflight and self.buf is not None:
+            if self.hint_inflight and self.buf is not None:
                 torch.cuda.synchronize(self.buf.device)
         except Exception:
             pass
@@ -71,11 +147,49 @@ class Workspace:
             self.pending = False
         if not self.pending:
             return self
+        sibling = self.partner()
+        if sibling.pending and version is not None and sibling.pending_version != version:
+            sibling.pending = False
+        return sibling if not sibling.pending else self
+
+    def partner(self) -> "Workspace":
+        """the second workspace of this one (own buffers), created on first use"""
         if self.sibling is None:
             self.sibling = Workspace()
-        if self.sibling.pending and version is not None and self.sibling.pending_version != version:
-            self.sibling.pending = False
-        return self.sibling if not self.sibling.pending else self
+        return self.sibling
+
+    def forward_pending(self, version) -> None:
+        """a differentiable forward of the parameters at `version` left its ray states here for its backward"""
+        self.pending, self.pending_version = True, version
+
+    def backward_ran(self) -> None:
+        self.pending = False
+
+    def attach_deferred(self, want_densities: bool, want_features: bool) -> DeferredGrad:
+        if self.deferred is not None:
+            raise RuntimeError("FusedGridAdam: this grid is already in deferred-gradient mode (another FusedGridAdam is "
+                               "attached to it); detach() that optimiser first")
+        self.deferred = DeferredGrad(want_densities=want_densities, want_features=want_features)
+        return self.deferred
+
+    def detach_deferred(self, mine: Optional[DeferredGrad] = None) -> bool:
+        """leave the deferred-gradient mode (`mine`, the finalizer: only while it is still that optimiser's) -> an unconsumed gradient
+        stays behind.  It must not leak into a later fused step: its region is unknown to whoever attaches next, and detach(), which
+        unlike the finalizer may run a kernel, zeroes it as well"""
+        d = self.deferred
+        if d is None or (mine is not None and d is not mine):
+            return False
+        if d.dirty:
+            self.call_failed()
+        self.deferred = None
+        return d.dirty
+
+    def call_failed(self) -> None:
+        """a fused call may have failed BEHIND its first backward: the gradient region then holds a partial gradient and the
+        packed grid may be stale -- the next call must clear / re-pack first"""
+        if self.deferred is not None:
+            self.deferred.clean_ptr = 0
+        self.invalidate()
 
     def before_call(self, spec, densities, features, nbytes: int, device):
         """THE question before a library call on the grid `densities` / `features` (the caller's SOURCE tensors, see `holds`):
@@ -117,10 +231,10 @@ class Workspace:
     def ensure(self, nbytes: int, device) -> torch.Tensor:
         if self.buf is None or self.buf.numel() < nbytes or self.buf.device != torch.device(device):
             old = self.buf
-            if old is not None and self.prefetch_inflight:
+            if old is not None and self.hint_inflight:
                 torch.cuda.synchronize(old.device)   # (a stream torch's allocator knows nothing about is still using the old buffer)
-                self.prefetch_inflight = False
-            self.recon_cache = None                  # (its descriptors point into the old buffer -- and would keep it alive)
+                self.hint_inflight = False
+            self.recon.last = None                   # (its descriptors point into the old buffer -- and would keep it alive)
             self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
             keep = (old is not None and self.deferred is not None and self.deferred.dirty
                     and old.device == self.buf.device)
