@@ -912,6 +912,54 @@ int voxe_cast_rays_camera_bwd(const VoxeCamera* cam, const float* poses, int32_t
                               float* d_distortion /* device float[5] k1 k2 p1 p2 k3, or NULL */,
                               int32_t accumulate, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- learned environment-map background behind the grid (not in the reference) -----------------------------------
+ * An added symbol is backward compatible: VOXE_ABI_VERSION stays 13.  No voxe_cpu_ twin; the float64 restatement is
+ * tests/background_ref.py.  No render entry point changes: the background is composited behind a finished render with the
+ * ray's leftover transmittance 1 - acc, and its d_acc goes into voxe_render_bwd / voxe_render_bwd_rays as their upstream d_acc.
+ *
+ * VoxeEnvMap: texels [height, width, 3], float32, contiguous, LOGITS; height >= 2, width >= 2.  For a ray direction
+ * d = (dx, dy, dz), which need not be unit length:
+ *       r = sqrt(dx^2 + dy^2),  phi = atan2(dy, dx) (0 where r == 0),  theta = atan2(r, dz)
+ *       u = (phi / 2 pi + 0.5) width - 0.5,              v = (theta / pi) height - 0.5
+ *       x0 = floor(u), fx = u - x0, columns x0 mod width, (x0 + 1) mod width               (the longitude wraps)
+ *       y0 = floor(v), fy = v - y0, rows clamp(y0, 0, height - 1), clamp(y0 + 1, 0, height - 1)     (the poles clamp)
+ *       t_c = bilinear(E[..., c]),  b_c = sigmoid(t_c),  colour_out_c = colour_in_c + (1 - acc) b_c
+ *   A direction with a non-finite component, or of zero length, has b = 0 and no gradient anywhere.  The angles and (u, v) are
+ *   evaluated in double, everything else in float.
+ *
+ * voxe_background_fwd: colour_out [R,3] from colour_in [R,3], acc [R] and rays_d [R,3]; colour_out may be colour_in.
+ *
+ * voxe_background_bwd: with g = d_colour_out [R,3] (d_colour_in = g needs no call):
+ *       d_acc = - sum_c g_c b_c
+ *       s_c = (1 - acc) g_c b_c (1 - b_c),   d_texels[tap] += w_tap s_c for the four taps (taps that coincide through the clamp
+ *         receive both weights)
+ *       d_rays_d = d_u du/dd + d_v dv/dd,  d_u = (width / 2 pi) sum_c s_c ((1 - fy)(E01 - E00) + fy (E11 - E10)),
+ *         d_v = (height / pi) sum_c s_c ((1 - fx)(E10 - E00) + fx (E11 - E01)),
+ *         dphi/dd = (-dy, dx, 0) / r^2,  dtheta/dd = (dx dz / r, dy dz / r, -r) / |d|^2;  exactly 0 where r == 0
+ *   Each of the three outputs may be NULL (not computed).  accumulate == 0 overwrites all of them (d_texels is zeroed first:
+ *   texels no ray touches hold an exact 0), accumulate != 0 adds.  A ray whose s is all zero (acc == 1, g == 0) issues no
+ *   atomic.  d_texels goes through float atomics, so it can differ in the last bits from run to run; d_acc and d_rays_d are
+ *   written by one lane each.  Lanes of a wave that are neighbours and fall into the same cell (x0, y0) are summed in the wave
+ *   before the first of them adds (the run merge); voxe_background_debug_merge is a test aid that pins this for the calling
+ *   thread's later calls: 0 = the shipped choice, 1 = merge, 2 = one atomic per lane and tap (anything else: VOXE_ERR_BAD_SHAPE).
+ *
+ * Validation, before any device work: env or env->texels NULL: VOXE_ERR_NULL_POINTER; height < 2, width < 2, R < 0 or
+ * R >= 2^31: VOXE_ERR_BAD_SHAPE; R == 0: VOXE_OK and nothing is done (no output is touched); then a NULL rays_d, acc, colour_in,
+ * colour_out or d_colour_out: VOXE_ERR_NULL_POINTER.  All three outputs NULL: VOXE_OK with no launch.  Caller's stream, no host
+ * synchronisation, no allocation, no workspace.                                                                             */
+typedef struct VoxeEnvMap {
+  const float* texels;      /* device [height, width, 3], logits */
+  int32_t height, width;
+} VoxeEnvMap;
+
+int voxe_background_fwd(const VoxeEnvMap* env, const float* rays_d, int64_t R,
+                        const float* colour_in, const float* acc, float* colour_out, void* stream);
+int voxe_background_bwd(const VoxeEnvMap* env, const float* rays_d, int64_t R, const float* acc,
+                        const float* d_colour_out, float* d_acc /* [R] or NULL */,
+                        float* d_texels /* [height, width, 3] or NULL */, float* d_rays_d /* [R,3] or NULL */,
+                        int32_t accumulate, void* stream);
+int voxe_background_debug_merge(int32_t mode);
+
 /* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.

@@ -46,6 +46,8 @@ from thre3d_atom.utils.imaging_utils import (  # noqa: E402
 @click.option("-p", "--sds_prompt", type=click.STRING, required=False, default=None)
 @click.option("--render_geometry", is_flag=True, default=False,
               help="also write geometry frames: colour | depth | normals | 1 - acc, and rendered_geometry_video")
+@click.option("--ignore_background", is_flag=True, default=False,
+              help="do not composite the checkpoint's learned background (render over white, as for a checkpoint without one)")
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
     device = torch.device("cuda")
@@ -54,7 +56,11 @@ def main(**kwargs) -> None:
     if cfg.sds_prompt is not None:
         (out / "prompt.txt").write_text(cfg.sds_prompt)
     vol_mod, extra = create_volumetric_model_from_saved_model(Path(cfg.model_path), create_voxel_grid_from_saved_info_dict, device=device)
-    vol_mod.render_config.white_bkgd = True  # the reference forces a white background at inference (:97-98)
+    if cfg.ignore_background:
+        vol_mod.background = None
+    if vol_mod.background is None:
+        vol_mod.render_config.white_bkgd = True  # the reference forces a white background at inference (:97-98)
+    # (a checkpoint trained with a learned background renders over that background: white_bkgd stays off)
     if cfg.ref_path is not None:
         _, extra = create_volumetric_model_from_saved_model(Path(cfg.ref_path), create_voxel_grid_from_saved_info_dict, device=device)
     radius, intrinsics = extra[HEMISPHERICAL_RADIUS], extra[CAMERA_INTRINSICS]

@@ -75,6 +75,10 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
               help="> 0: refine the training cameras while training (Adam at this rate on per-camera pose deltas); 0 = off")
 @click.option("--intrinsics_learning_rate", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
               help="> 0 (with --pose_learning_rate): also learn fx, fy, cx, cy of the shared camera at this rate; 0 = off")
+@click.option("--background_resolution", type=click.IntRange(min=0), default=0, show_default=True,
+              help="N > 0: learn an environment-map background of N x 2N texels behind the grid (needs --white_bkgd False); 0 = off")
+@click.option("--background_learning_rate", type=click.FloatRange(min=0.0), default=None,
+              help="Adam rate of the background's texels (default: --learning_rate)")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -112,7 +116,8 @@ def main(**kwargs) -> None:
         save_freq=cfg.save_frequency, test_freq=cfg.test_frequency, feedback_freq=cfg.feedback_frequency,
         summary_freq=cfg.summary_frequency, verbose_rendering=cfg.verbose_rendering, lpips_weight=cfg.lpips_weight,
         num_workers=cfg.num_workers, distortion_weight=cfg.distortion_weight, pose_learning_rate=cfg.pose_learning_rate,
-        intrinsics_learning_rate=cfg.intrinsics_learning_rate)
+        intrinsics_learning_rate=cfg.intrinsics_learning_rate, background_resolution=cfg.background_resolution,
+        background_learning_rate=cfg.background_learning_rate)
 
 
 if __name__ == "__main__":

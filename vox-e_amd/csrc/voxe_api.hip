@@ -1539,6 +1539,49 @@ int voxe_distortion_debug_lanes(int32_t lanes) {
   return VOXE_OK;
 }
 
+// ---- environment-map background behind the grid ----------------------------------------------------------
+namespace {
+// the checks the two background calls share; *done: the call ends here with the returned status
+int validate_background(const VoxeEnvMap* env, int64_t R, bool* done) {
+  *done = true;
+  if (!env || !env->texels) return VOXE_ERR_NULL_POINTER;
+  if (env->height < 2 || env->width < 2 || R < 0 || R >= (1LL << 31)) return VOXE_ERR_BAD_SHAPE;
+  *done = R == 0;
+  return VOXE_OK;
+}
+}  // namespace
+
+int voxe_background_fwd(const VoxeEnvMap* env, const float* rays_d, int64_t R, const float* colour_in, const float* acc,
+                        float* colour_out, void* stream) {
+  bool done;
+  const int st = validate_background(env, R, &done);
+  if (done) return st;
+  if (!rays_d || !colour_in || !acc || !colour_out) return VOXE_ERR_NULL_POINTER;
+  launch_background_fwd(env->texels, env->height, env->width, rays_d, R, colour_in, acc, colour_out, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_background_bwd(const VoxeEnvMap* env, const float* rays_d, int64_t R, const float* acc, const float* d_colour_out,
+                        float* d_acc, float* d_texels, float* d_rays_d, int32_t accumulate, void* stream) {
+  bool done;
+  const int st = validate_background(env, R, &done);
+  if (done) return st;
+  if (!rays_d || !acc || !d_colour_out) return VOXE_ERR_NULL_POINTER;
+  if (!d_acc && !d_texels && !d_rays_d) return VOXE_OK;
+  if (d_texels && !accumulate &&
+      hipMemsetAsync(d_texels, 0, sizeof(float) * 3 * (size_t)env->height * (size_t)env->width, (hipStream_t)stream) != hipSuccess)
+    return VOXE_ERR_LAUNCH;
+  launch_background_bwd(env->texels, env->height, env->width, rays_d, R, acc, d_colour_out, d_acc, d_texels, d_rays_d,
+                        accumulate != 0, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_background_debug_merge(int32_t mode) {
+  if (mode < 0 || mode > 2) return VOXE_ERR_BAD_SHAPE;
+  tl_background_merge = mode;
+  return VOXE_OK;
+}
+
 // ---- ray and camera-pose gradients -------------------------------------------------------------------------
 int voxe_render_bwd_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
                          const float* jitter, const float* d_colour, const float* d_depth, const float* d_acc, float* d_rays_o,

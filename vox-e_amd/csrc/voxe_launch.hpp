@@ -261,6 +261,14 @@ hipError_t launch_cast_rays_camera_bwd(const VoxeCamera& cam, const float* poses
                                        const float* d_o, const float* d_d, float* d_poses, float* d_intrinsics,
                                        float* d_distortion, int accumulate, void* scratch, hipStream_t st);
 
+// voxe_background.hip: environment-map background behind the grid; arguments validated by the API
+extern thread_local int tl_background_merge;   // test aid (voxe_background_debug_merge): 1 = run merge, 2 = plain, 0 = shipped
+void launch_background_fwd(const float* texels, int He, int We, const float* rays_d, long long R, const float* colour_in,
+                           const float* acc, float* colour_out, hipStream_t st);
+void launch_background_bwd(const float* texels, int He, int We, const float* rays_d, long long R, const float* acc,
+                           const float* d_colour_out, float* d_acc, float* d_texels, float* d_rays_d, bool accumulate,
+                           hipStream_t st);
+
 // voxe_transform.hip: rigid transform / re-gridding / composition of grids; arguments validated by the API
 void launch_grid_resample(const float* src_dens, const float* src_feat, int X, int Y, int Z, int C, float* dst_dens, float* dst_feat,
                           int X2, int Y2, int Z2, const VoxeResample& xf, uint8_t* taken, hipStream_t st);

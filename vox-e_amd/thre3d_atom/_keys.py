@@ -33,6 +33,8 @@ CHECKPOINT_KEYS = {
     "CAMERA_BOUNDS": "camera_bounds",
     "CAMERA_INTRINSICS": "camera_intrinsics",
     "HEMISPHERICAL_RADIUS": "hemispherical_radius",
+    # optional (not in the reference): the environment-map background {state_dict, config_dict}, only when the model has one
+    "BACKGROUND": "background",
 }
 STATE_DICT_NAMES = {"u_DENSITIES": "_densities", "u_FEATURES": "_features", "u_ATTN": "attn"}
 

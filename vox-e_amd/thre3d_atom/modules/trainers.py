@@ -18,6 +18,7 @@ from thre3d_atom.modules.optim import FusedGridAdam, VoxeAdam
 from thre3d_atom.modules.testers import test_sh_vox_grid_vol_mod_with_posed_images
 from thre3d_atom.modules.volumetric_model import VolumetricModel
 from thre3d_atom.rendering.volumetric.utils.misc import is_general_camera, sample_random_rays_and_pixels_from_cameras
+from thre3d_atom.thre3d_reprs.background import EnvMapBackground
 from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, LearnedIntrinsics, write_camera_params
 from thre3d_atom.thre3d_reprs.renderers import _render_params, render_sh_voxel_grid
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid, scale_voxel_grid_with_required_output_size
@@ -96,11 +97,24 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     intrinsics_learning_rate: float = 0.0,   # addition of this build: > 0 also learns fx, fy, cx, cy of the shared camera (in
                                              # full-resolution pixels, scaled to each stage's images) by a second parameter group
                                              # of the pose optimiser; needs pose_learning_rate > 0.  0 = off, nothing changes
+    background_resolution: int = 0,    # addition of this build: N > 0 learns an environment-map background of [N, 2N] texels
+                                       # behind the grid (thre3d_reprs/background.py), fixed across the stages and saved with the
+                                       # checkpoints; needs white_bkgd=False.  0 = off, nothing changes.  Above 0 the iteration
+                                       # is not the one-call one either (voxe_recon_step knows no background)
+    background_learning_rate: Optional[float] = None,   # Adam rate of the background's texels; None = `learning_rate`, with the
+                                                        # same stage decay
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
     if lpips_weight != 0.0:
         raise NotImplementedError("LPIPS needs the external `lpips` network; not part of this build")
+    if background_resolution < 0 or background_resolution == 1:
+        raise ValueError(f"background_resolution must be 0 (off) or at least 2; got {background_resolution}")
+    if background_resolution > 0:
+        if vol_mod.render_config.white_bkgd:
+            raise ValueError("background_resolution > 0 needs white_bkgd=False: the white background is already composited by the "
+                             "renderer")
+        vol_mod.background = EnvMapBackground(background_resolution, 2 * background_resolution).requires_grad_(True)
     device = vol_mod.device
     output_dir = Path(output_dir)
     model_dir = output_dir / "saved_models"
@@ -168,6 +182,14 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
         else:
             optimizer = VoxeAdam([{"params": vol_mod.thre3d_repr.parameters(), "lr": lr}], betas=(0.9, 0.999))
         scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=lr_decay_gamma_per_stage)
+        background_optimizer = background_scheduler = None
+        if background_resolution > 0:
+            # a second Adam on the texels (their state does not survive a stage, like the grid's: the reference builds a fresh
+            # optimiser per stage)
+            background_lr = (learning_rate if background_learning_rate is None else background_learning_rate) \
+                * (stagewise_lr_decay_gamma ** (stage - 1))
+            background_optimizer = VoxeAdam([{"params": vol_mod.background.parameters(), "lr": background_lr}], betas=(0.9, 0.999))
+            background_scheduler = torch.optim.lr_scheduler.ExponentialLR(background_optimizer, gamma=lr_decay_gamma_per_stage)
         # (the one-call iteration reads RGB targets straight from the image stack)
         one_call = fused_grid_step and fused_iteration and data.images.shape[1] == 3 and data.images.is_contiguous()
         if distortion_weight > 0.0:
@@ -177,6 +199,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
         if pose_deltas is not None:
             if one_call and stage == 1:
                 log.info("pose_learning_rate > 0: the iterations cast, render and step separately (no one-call iteration)")
+            one_call = False
+        if background_resolution > 0:
+            if one_call and stage == 1:
+                log.info("background_resolution > 0: the iterations render, composite the background and step separately (no "
+                         "one-call iteration)")
             one_call = False
         if is_general_camera(intr):
             # voxe_recon_step casts (height, width, focal) cameras only: fx != fy, an off-centre principal point or a lens model
@@ -246,10 +273,14 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                     optimizer.zero_grad()
                     if pose_optimizer is not None:
                         pose_optimizer.zero_grad()
+                    if background_optimizer is not None:
+                        background_optimizer.zero_grad()
                     loss.backward()
                     optimizer.step()
                     if pose_optimizer is not None:
                         pose_optimizer.step()
+                    if background_optimizer is not None:
+                        background_optimizer.step()
                 global_step += 1
                 trained += time.perf_counter() - t0
                 if global_step % summary_freq == 0 or it in (1, num_iterations_per_stage):
@@ -262,6 +293,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                              + (f" distortion: {float(distortion.detach()): .6f}" if distortion_weight > 0.0 else ""))
                 if it % lr_decay_steps_per_stage == 0:
                     scheduler.step()
+                    if background_scheduler is not None:
+                        background_scheduler.step()
                 last = it == num_iterations_per_stage
                 if not fast_debug_mode and (global_step % feedback_freq == 0 or it == 1 or last):
                     log.info(f"TIME CHECK: time spent actually training till now: {trained:.1f} s")

@@ -22,6 +22,7 @@ from thre3d_atom.rendering.volumetric.utils.misc import (
     reshape_rendered_output_attn,
 )
 from thre3d_atom.thre3d_reprs.constants import (
+    BACKGROUND,
     CONFIG_DICT,
     RENDER_CONFIG,
     RENDER_CONFIG_TYPE,
@@ -30,7 +31,7 @@ from thre3d_atom.thre3d_reprs.constants import (
     THRE3D_REPR,
 )
 from thre3d_atom.thre3d_reprs.renderers import RenderConfig, RenderProcedure, render_sh_voxel_grid_attn
-from thre3d_atom.utils.constants import EXTRA_INFO
+from thre3d_atom.utils.constants import EXTRA_ACCUMULATED_WEIGHTS, EXTRA_INFO
 from thre3d_atom.utils.imaging_utils import CameraIntrinsics, CameraPose
 
 
@@ -42,12 +43,27 @@ class VolumetricModel:
         render_config: RenderConfig,
         render_procedure_attn=None,
         device: torch.device = torch.device("cuda" if torch.cuda.is_available() else "cpu"),
+        background: Optional[Module] = None,   # addition of this build: thre3d_reprs.background.EnvMapBackground behind the grid
     ) -> None:
         self._thre3d_repr = thre3d_repr.to(device)
         self._render_procedure = render_procedure
         self._render_procedure_attn = render_procedure_attn
         self._render_config = render_config
         self._device = device
+        self._background = None
+        self.background = background
+
+    @property
+    def background(self) -> Optional[Module]:
+        """the learned background composited behind every `render_rays` / `render` (None: black, or white_bkgd)"""
+        return self._background
+
+    @background.setter
+    def background(self, background: Optional[Module]) -> None:
+        if background is not None and getattr(self._render_config, "white_bkgd", False):
+            raise ValueError("a background model and white_bkgd=True exclude each other: the white background is already "
+                             "composited by the renderer")
+        self._background = None if background is None else background.to(self._device)
 
     @property
     def thre3d_repr(self) -> Module:
@@ -89,14 +105,28 @@ class VolumetricModel:
             RENDER_CONFIG_TYPE: type(self._render_config),
             RENDER_CONFIG: dataclasses.asdict(self._render_config),
         }
+        if self._background is not None:
+            save_info[BACKGROUND] = {
+                STATE_DICT: self._background.state_dict(),
+                CONFIG_DICT: self._background.get_save_config_dict(),
+            }
         if extra_info is not None:
             save_info[EXTRA_INFO] = extra_info
         return save_info
 
     # -- differentiable ---------------------------------------------------------------------------
-    def render_rays(self, rays: Rays, parallel_points_chunk_size: Optional[int] = None, **kwargs) -> RenderOut:
+    def render_rays(self, rays: Rays, parallel_points_chunk_size: Optional[int] = None, with_background: bool = True,
+                    **kwargs) -> RenderOut:
         config = self._update_render_config(self._render_config, kwargs)
-        return self._render_procedure(self._thre3d_repr, rays, config, parallel_points_chunk_size)
+        out = self._render_procedure(self._thre3d_repr, rays, config, parallel_points_chunk_size)
+        if self._background is None or not with_background:
+            return out
+        if getattr(config, "white_bkgd", False):
+            raise ValueError("a background model and white_bkgd=True exclude each other: the white background is already "
+                             "composited by the renderer")
+        # the background sees what the grid left of each ray: colour + (1 - acc) * b(direction); depth and extra stay the grid's
+        colour = self._background(out.colour, out.extra[EXTRA_ACCUMULATED_WEIGHTS], rays.directions)
+        return RenderOut(colour=colour, depth=out.depth, extra=out.extra)
 
     def render_rays_attn(
         self, rays: Rays, parallel_points_chunk_size: Optional[int] = None, orig_densities=False, **kwargs
@@ -134,10 +164,11 @@ class VolumetricModel:
         parallel_points_chunk_size: Optional[int] = None,
         gpu_render: bool = True,
         verbose: bool = False,
+        with_background: bool = True,
         **kwargs,
     ) -> RenderOut:
         return self._render_camera(
-            lambda r: self.render_rays(r, parallel_points_chunk_size, **kwargs),
+            lambda r: self.render_rays(r, parallel_points_chunk_size, with_background=with_background, **kwargs),
             collate_rendered_output, reshape_rendered_output,
             camera_pose, camera_intrinsics, parallel_rays_chunk_size, gpu_render, verbose,
         )
@@ -171,8 +202,20 @@ def _load_model(model_path: Path, make_repr, device) -> Tuple[VolumetricModel, D
         render_procedure_attn=render_sh_voxel_grid_attn,
         render_config=render_config,
         device=device,
+        background=_load_background(model_data),
     )
     return model, model_data.get(EXTRA_INFO)
+
+
+def _load_background(model_data: Dict[str, Any]) -> Optional[Module]:
+    """the checkpoint's environment-map background, frozen (None: the checkpoint has none -- every reference checkpoint)"""
+    if BACKGROUND not in model_data:
+        return None
+    from thre3d_atom.thre3d_reprs.background import EnvMapBackground
+
+    background = EnvMapBackground(**model_data[BACKGROUND][CONFIG_DICT])
+    background.load_state_dict(model_data[BACKGROUND][STATE_DICT])
+    return background.requires_grad_(False)
 
 
 def create_volumetric_model_from_saved_model(

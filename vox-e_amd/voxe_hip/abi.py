@@ -159,6 +159,11 @@ class VoxeCamera(C.Structure):
     ]
 
 
+class VoxeEnvMap(C.Structure):
+    """environment-map background: texels [height, width, 3] (logits) on the device (include/voxe.h)"""
+    _fields_ = [("texels", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32)]
+
+
 RESAMPLE_REPLACE, RESAMPLE_UNION = 0, 1
 SH_ROT_OFFSETS = (0, 1, 10, 35, 84)   # M_l starts at SH_ROT_OFFSETS[l]
 
@@ -262,6 +267,10 @@ HIP_ONLY = {
     "cast_rays_camera_bwd_scratch_bytes": (C.c_size_t, [C.c_int32]),
     "cast_rays_camera_bwd": (C.c_int, [C.POINTER(VoxeCamera), _P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P,
                                        C.c_size_t, _P]),
+    # environment-map background behind the grid (additive, still ABI v13)
+    "background_fwd": (C.c_int, [C.POINTER(VoxeEnvMap), _P, C.c_int64, _P, _P, _P, _P]),
+    "background_bwd": (C.c_int, [C.POINTER(VoxeEnvMap), _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P]),
+    "background_debug_merge": (C.c_int, [C.c_int32]),
 }
 
 CPU_ONLY = {

@@ -10,6 +10,7 @@ import torch
 from . import abi
 from . import dispatch as _dispatch
 from .args import GridSpec, RenderParams, _check_rays, _moments, _next_rng, _require_buffer, resolve_rng  # noqa: F401
+from .background import background_bwd, background_composite, background_fwd_into  # noqa: F401
 from .cameras import (cast_rays, cast_rays_bwd, cast_rays_camera, cast_rays_camera_bwd, cast_rays_from_camera,  # noqa: F401
                       cast_rays_from_poses, cast_rays_indexed, random_subset)
 from .desc import make_grid_desc, make_render_cfg
