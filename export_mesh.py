@@ -5,7 +5,8 @@ colours are the diffuse (DC) colour of the field at each vertex; --vertex_normal
 shading, vox-e_amd/csrc/voxe_normals.hip).  --edit_region_only keeps the voxels a refined model
 marks as its edit region (keep-grid value 0) and caps the mesh where that region cuts the object.  --visible_only keeps the
 voxels some camera actually weighs (vox-e_amd/csrc/voxe_visibility.hip): the training cameras of -d, or --num_views poses of the
-checkpoint's own 360 degree path."""
+checkpoint's own 360 degree path.  --region leaves out the voxels the masks of a lifted region voted out
+(lift_masks_to_grid.py, vox-e_amd/csrc/voxe_lift.hip)."""
 import os
 import sys
 import time
@@ -36,6 +37,8 @@ from thre3d_atom.thre3d_reprs.voxels import create_voxel_grid_from_saved_info_di
 @click.option("--num_views", type=click.IntRange(min=1), default=36, show_default=True, help="--visible_only: poses of the 360 degree path (without -d)")
 @click.option("-d", "--data_path", type=click.Path(file_okay=False, dir_okay=True), default=None,
               help="--visible_only: dataset whose training cameras are used")
+@click.option("--region", type=click.Path(file_okay=True, dir_okay=False), default=None,
+              help="region file of lift_masks_to_grid.py: leave out the voxels its masks voted out (label 1)")
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
     device = torch.device("cuda")
@@ -49,6 +52,8 @@ def main(**kwargs) -> None:
     mask = (grid.attn.detach()[..., 0] == 0) if cfg.edit_region_only else None
     if cfg.visible_only:
         mask = visible_mask(vol_mod, extra, cfg, mask)
+    if cfg.region is not None:
+        mask = region_mask(grid, cfg.region, mask)
     level = cfg.level if cfg.level is not None else default_level(grid)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -72,6 +77,14 @@ def visible_mask(vol_mod, extra, cfg, mask):
     vis = accumulate_visibility(vol_mod, poses, intrinsics)
     seen = ops.visibility_mask(vis.max_weight, cfg.visibility_threshold, 1)
     return seen if mask is None else seen * mask.to(torch.uint8)
+
+
+def region_mask(grid, region_path, mask):
+    """u8 [X,Y,Z]: the voxels the region's masks did not vote out (labels != 1), ANDed with `mask` when there is one"""
+    from thre3d_atom.thre3d_reprs.lifting import load_region, mesh_mask
+
+    labels = load_region(region_path, grid)["labels"].to(grid.densities.device)
+    return mesh_mask(labels, mask)
 
 
 if __name__ == "__main__":

@@ -713,6 +713,39 @@ int voxe_visibility_mask(const float* vis, int32_t X, int32_t Y, int32_t Z, floa
                          uint8_t* mask /* [X,Y,Z] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Lifting per-ray values into the grid by weighted back-projection (additive; still ABI v13), DESIGN.md section 4.16 "Lifting".
+ *   voxe_lift_accumulate: the samples, depths, inside test, T_k and w_k = T_k alpha_k are those of voxe_visibility_accumulate
+ *       for the same rays, cfg and jitter / (seed, rng_offset); the cfg fields honoured and ignored, the validation, the limits
+ *       and the error codes are those of voxe_visibility_accumulate.  For every sample that passes the strict AABB test and each
+ *       of its 8 footprint corners c inside the grid, with a = w_k * t_c -- the float32 value voxe_visibility_accumulate raises
+ *       max_weight with, t_c = (wx * wy) * wz:
+ *           sum_w[c]      += q(a)
+ *           sum_wv[c, ch] += q(a * values[r, ch])      ch = 0 .. C-1, the product rounded to float32
+ *           q(x) = (int64) round-to-nearest-even(x * 2^32)
+ *       The sums are 64-bit fixed point with 32 fraction bits, added with integer atomics: integer addition is associative, so
+ *       the result is the same bit for bit whatever the order of lanes, waves, launches and cameras.  A contribution whose q is 0
+ *       is skipped (an exact no-op).  values (f32 [R,C]) must be finite with |v| <= 1: a voxel then has room for 2^31 full-size
+ *       contributions.  The call ACCUMULATES into sum_wv (int64 [X,Y,Z,C]) and sum_w (int64 [X,Y,Z]); the caller zeroes them
+ *       first.  What a ray contributes depends on that ray and cfg only -- not on R, the ray's position in the batch or
+ *       image_width / image_height.
+ *         C in 1..8 with values and sum_wv both given: full accumulation (sum_w may still be NULL);
+ *         values and sum_wv both NULL: coverage only (C is not read);
+ *         exactly one of the two NULL: VOXE_ERR_NULL_POINTER (as for the rays, not when R == 0, where nothing is read);
+ *         either given and C outside 1..8: VOXE_ERR_BAD_SHAPE;
+ *         both outputs NULL, or R == 0: VOXE_OK, no launch.
+ *       Only grid->densities is read; no workspace, no forward record, no voxe_recon_prefetch hint is touched.  Caller's
+ *       stream, no host synchronisation, no allocation.
+ *   voxe_lift_debug_merge: a test aid.  The kernel has two variants that return identical bits: one atomic per lane, corner and
+ *       channel (1), and one that first sums, inside a wave, the contributions of lanes that sit in the same cell at the same
+ *       step (2).  0 = the shipped choice (DESIGN.md 4.16 holds the measurement).  Pins the calling thread's later calls; any
+ *       other value: VOXE_ERR_BAD_SHAPE.                                                                                      */
+int voxe_lift_accumulate(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                         const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                         const float* values /* [R,C] or NULL */, int32_t C,
+                         int64_t* sum_wv /* [X,Y,Z,C] or NULL */, int64_t* sum_w /* [X,Y,Z] or NULL */, void* stream);
+int voxe_lift_debug_merge(int32_t mode);
+
+/* ------------------------------------------------------------------------------------------------
  * Distortion loss on rays (additive; still ABI v13), DESIGN.md section 4.11 "Distortion".
  *   The samples z_k, the inside test, sigma_k, delta_k and the weights w_k = T_k alpha_k (last dl = 1e10) are those of
  *   voxe_render_fwd / voxe_render_normals / voxe_visibility_accumulate for the same rays, cfg and jitter / (seed, rng_offset);

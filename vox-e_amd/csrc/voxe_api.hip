@@ -1508,6 +1508,32 @@ int voxe_visibility_mask(const float* vis, int32_t X, int32_t Y, int32_t Z, floa
   return finish();
 }
 
+// ---- lifting per-ray values into the grid ----------------------------------------------------------------
+int voxe_lift_accumulate(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
+                         const float* jitter, const float* values, int32_t C, int64_t* sum_wv, int64_t* sum_w, void* stream) {
+  const int st = validate_normals_grid(grid);
+  if (st) return st;
+  if (!cfg) return VOXE_ERR_NULL_POINTER;
+  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  if ((values || sum_wv) && (C < 1 || C > 8)) return VOXE_ERR_BAD_SHAPE;
+  // (R == 0: nothing is read, rays and values may be NULL -- an empty tensor has no address)
+  if (R > 0 && (!rays_o || !rays_d || (values == nullptr) != (sum_wv == nullptr))) return VOXE_ERR_NULL_POINTER;
+  if (R == 0 || (!sum_wv && !sum_w)) return VOXE_OK;
+  DevGrid dg;
+  grid_to_dev(grid, &dg);
+  DevCfg dc;
+  sampling_cfg_to_dev(cfg, R, &dc);
+  launch_lift_accumulate(dg, dc, grid->densities, rays_o, rays_d, jitter, values, C, reinterpret_cast<long long*>(sum_wv),
+                         reinterpret_cast<long long*>(sum_w), (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_lift_debug_merge(int32_t mode) {
+  if (mode < 0 || mode > 2) return VOXE_ERR_BAD_SHAPE;
+  tl_lift_merge = mode;
+  return VOXE_OK;
+}
+
 // ---- distortion loss on rays -----------------------------------------------------------------------
 size_t voxe_distortion_scratch_bytes(int64_t R) { return distortion_scratch_bytes(R); }
 

@@ -231,6 +231,11 @@ void launch_visibility_accumulate(const DevGrid& g, const DevCfg& c, const float
                                   const float* jitter, float* max_weight, float* max_trans, hipStream_t st);
 void launch_visibility_mask(const float* vis, int X, int Y, int Z, float threshold, int dilate, uint8_t* mask, hipStream_t st);
 
+// voxe_lift.hip: weighted back-projection of per-ray values into the grid; reads the raw densities only
+extern thread_local int tl_lift_merge;   // test aid (voxe_lift_debug_merge): 1 = one atomic per lane, 2 = wave merge, 0 = shipped
+void launch_lift_accumulate(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
+                            const float* jitter, const float* values, int C, long long* sum_wv, long long* sum_w, hipStream_t st);
+
 // voxe_distortion.hip: distortion loss on rays, value + density gradient; reads the raw densities only
 int distortion_lanes_for(long long R);   // lanes per ray (1, 2, 4 or 8)
 extern thread_local int tl_distortion_lanes;   // test aid (voxe_distortion_debug_lanes): != 0 overrides distortion_lanes_for

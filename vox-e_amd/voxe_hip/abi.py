@@ -271,6 +271,9 @@ HIP_ONLY = {
     "background_fwd": (C.c_int, [C.POINTER(VoxeEnvMap), _P, C.c_int64, _P, _P, _P, _P]),
     "background_bwd": (C.c_int, [C.POINTER(VoxeEnvMap), _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "background_debug_merge": (C.c_int, [C.c_int32]),
+    # lifting per-ray values into the grid (additive, still ABI v13)
+    "lift_accumulate": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, C.c_int32, _P, _P, _P]),
+    "lift_debug_merge": (C.c_int, [C.c_int32]),
 }
 
 CPU_ONLY = {

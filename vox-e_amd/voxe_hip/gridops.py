@@ -255,6 +255,49 @@ def visibility_mask(vis: torch.Tensor, threshold: float, dilate: int = 0) -> tor
 
 
 # ------------------------------------------------------------------------------------------------
+# lifting per-ray values into the grid: reads the raw densities only, no workspace, not differentiable
+# ------------------------------------------------------------------------------------------------
+LIFT_ONE = 1 << 32                                       # the fixed-point unit of sum_w / sum_wv (32 fraction bits)
+LIFT_MERGE_SHIPPED, LIFT_MERGE_PER_LANE, LIFT_MERGE_WAVE = 0, 1, 2   # voxe_lift_debug_merge
+
+
+def lift_accumulate_(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                     values: Optional[torch.Tensor], sum_wv: Optional[torch.Tensor], sum_w: Optional[torch.Tensor],
+                     jitter: Optional[torch.Tensor] = None, rng: Optional[Tuple[int, int]] = (0, 0)) -> None:
+    """Add, in place, q(w_k t_c) to sum_w[c] and q(w_k t_c values[r, ch]) to sum_wv[c, ch] over every sample k of the flat rays
+    and every corner c of its trilinear footprint, q(x) = rint(x * 2^32), with the samples and weights visibility_accumulate_
+    uses for the same params, jitter and rng.  values [R,C] float32 (C in 1..8, finite, |v| <= 1) and sum_wv [X,Y,Z,C] int64
+    come together or are both None (coverage only); sum_w [X,Y,Z] int64 may be None.  The buffers ACCUMULATE: zero them before
+    the first call.  The result is the same bit for bit however the rays are split over calls or ordered."""
+    _check_densities(densities, "lift_accumulate_")
+    _check_rays("lift_accumulate_", rays_o, rays_d, jitter, params.num_samples)
+    device = densities.device
+    X, Y, Z = (int(s) for s in densities.shape[:3])
+    if (values is None) != (sum_wv is None):
+        raise VoxeError("lift_accumulate_: values and sum_wv come together or not at all")
+    Cn = 0
+    if values is not None:
+        require_device(values, "lift_accumulate_ (values)")
+        if values.dim() != 2 or values.shape[0] != rays_o.shape[0] or not 1 <= values.shape[1] <= 8:
+            raise VoxeError(f"lift_accumulate_: values must be [R,C]=({rays_o.shape[0]}, 1..8); got {tuple(values.shape)}")
+        Cn = int(values.shape[1])
+        _require_buffer("lift_accumulate_", "sum_wv", sum_wv, shape=(X, Y, Z, Cn), device=device, dtype=torch.int64)
+    if sum_w is not None:
+        _require_buffer("lift_accumulate_", "sum_w", sum_w, shape=(X, Y, Z), device=device, dtype=torch.int64)
+    rng = resolve_rng(params, jitter, rng)
+    g, c, dens, ro, rd, jit = _sampling_inputs(spec, params, densities, rays_o, rays_d, jitter, rng)
+    vals = None if values is None else f32c(values.detach())
+    with torch.cuda.device(device):
+        check(lib().voxe_lift_accumulate(C.byref(g), C.byref(c), ptr(ro), ptr(rd), ro.shape[0], ptr(jit), ptr(vals), Cn,
+                                         ptr(sum_wv), ptr(sum_w), stream_ptr(device)), "voxe_lift_accumulate")
+
+
+def lift_debug_merge(mode: int) -> None:
+    """test aid: pin the calling thread's later lift_accumulate_ calls to one kernel variant (LIFT_MERGE_*); 0 = shipped"""
+    check(lib().voxe_lift_debug_merge(int(mode)), "voxe_lift_debug_merge")
+
+
+# ------------------------------------------------------------------------------------------------
 # rigid transform / re-gridding / composition of grids (DESIGN.md section 4.12): no workspace, not differentiable
 # ------------------------------------------------------------------------------------------------
 def make_resample(A, b, sh_rot=None, sh_degree: int = -1, density_pre_act: int = abi.ACT_IDENTITY, density_fill: float = 0.0,

@@ -14,7 +14,8 @@ from .background import background_bwd, background_composite, background_fwd_int
 from .cameras import (cast_rays, cast_rays_bwd, cast_rays_camera, cast_rays_camera_bwd, cast_rays_from_camera,  # noqa: F401
                       cast_rays_from_poses, cast_rays_indexed, random_subset)
 from .desc import make_grid_desc, make_render_cfg
-from .gridops import (cc_largest_k, extract_mesh, graph_build, graphcut, grid_resample, make_resample, query_normals,  # noqa: F401
+from .gridops import (LIFT_MERGE_PER_LANE, LIFT_MERGE_SHIPPED, LIFT_MERGE_WAVE, LIFT_ONE, cc_largest_k, extract_mesh,  # noqa: F401
+                      graph_build, graphcut, grid_resample, lift_accumulate_, lift_debug_merge, make_resample, query_normals,
                       render_normals, upsample_trilinear, visibility_accumulate_, visibility_mask)
 from .losses import (adam_step_, attn_masked_l1, density_correlation_loss, density_diff_loss, distortion_fwd_bwd,  # noqa: F401
                      distortion_loss, feature_correlation_loss, tv_loss_on_grid)
