@@ -100,7 +100,7 @@ def _render_cases():
         ("sh0_hash_lindisp_multiview", 0, 24, 3, True, None, False, True, "multiview"),
         ("sh2_jitter_shuffled", 2, 32, 1, True, "caller", False, False, "shuffled"),
         ("sh2_hash_clip_lindisp_linear", 2, 36, 1, True, None, True, True, "linear"),
-        # the host's lanes per ray (normals_lanes_for): 8 below 262 144 rays, 4 below 524 288, 2 below 1 048 576, then 1
+        # the host's lanes per ray (lanes_per_ray): 8 below 262 144 rays, 4 below 524 288, 2 below 1 048 576, then 1
         ("sh0_400_g8", 0, 400, 1, False, None, True, False, "image"),
         ("sh0_600_g4_jitter", 0, 600, 1, True, "caller", False, False, "linear"),
         ("sh0_800_g2", 0, 800, 1, False, None, False, False, "image"),

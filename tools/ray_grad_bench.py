@@ -107,7 +107,7 @@ def case_times(spec, dens, feat0, feat, deg, ro, rd, S, width, iters, ref_rays):
 
 
 def _lanes_for(R):
-    """rays_bwd_lanes_for() of the library"""
+    """lanes_per_ray() of the library (voxe_ray_march.hpp)"""
     for G in (1, 2, 4):
         if R * G >= (1 << 20):
             return G

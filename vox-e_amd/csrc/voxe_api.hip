@@ -1454,6 +1454,31 @@ static void sampling_cfg_to_dev(const VoxeRenderCfg* cfg, int64_t R, DevCfg* out
   }
 }
 
+// The prologue of the five calls that march the forward's samples over the raw densities (voxe_ray_march.hpp), in two steps
+// so that a call can put checks of its own between them: the grid, cfg and the R / num_samples range ...
+static int sampling_call_shape(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
+  const int st = validate_normals_grid(grid);
+  if (st) return st;
+  if (!cfg) return VOXE_ERR_NULL_POINTER;
+  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  return VOXE_OK;
+}
+// ... then the rays (R == 0: nothing is read, they may be NULL -- an empty tensor has no address) and the device structs
+static int sampling_call_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, const float* rays_o,
+                              const float* rays_d, DevGrid* dg, DevCfg* dc) {
+  if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
+  grid_to_dev(grid, dg);
+  sampling_cfg_to_dev(cfg, R, dc);
+  return VOXE_OK;
+}
+static int sampling_call(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R, const float* rays_o, const float* rays_d,
+                         DevGrid* dg, DevCfg* dc) {
+  const int st = sampling_call_shape(grid, cfg, R);
+  return st ? st : sampling_call_rays(grid, cfg, R, rays_o, rays_d, dg, dc);
+}
+// lanes per ray a *_debug_lanes test aid may pin (0: the library's choice)
+static bool lanes_ok(int32_t lanes) { return lanes == 0 || lanes == 1 || lanes == 2 || lanes == 4 || lanes == 8; }
+
 int voxe_query_normals(const VoxeGridDesc* grid, const float* points, int64_t N, float* normals, void* stream) {
   const int st = validate_normals_grid(grid);
   if (st) return st;
@@ -1468,16 +1493,12 @@ int voxe_query_normals(const VoxeGridDesc* grid, const float* points, int64_t N,
 
 int voxe_render_normals(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
                         const float* jitter, float* normals, float* depth, float* acc, void* stream) {
-  const int st = validate_normals_grid(grid);
-  if (st) return st;
-  if (!cfg) return VOXE_ERR_NULL_POINTER;
-  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
-  if (R > 0 && (!rays_o || !rays_d || !normals)) return VOXE_ERR_NULL_POINTER;
-  if (R == 0) return VOXE_OK;
   DevGrid dg;
-  grid_to_dev(grid, &dg);
   DevCfg dc;
-  sampling_cfg_to_dev(cfg, R, &dc);
+  const int st = sampling_call(grid, cfg, R, rays_o, rays_d, &dg, &dc);
+  if (st) return st;
+  if (R > 0 && !normals) return VOXE_ERR_NULL_POINTER;
+  if (R == 0) return VOXE_OK;
   launch_render_normals(dg, dc, grid->densities, rays_o, rays_d, jitter, normals, depth, acc, (hipStream_t)stream);
   return finish();
 }
@@ -1485,16 +1506,11 @@ int voxe_render_normals(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, cons
 // ---- per-voxel visibility ----------------------------------------------------------------------------
 int voxe_visibility_accumulate(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d,
                                int64_t R, const float* jitter, float* max_weight, float* max_trans, void* stream) {
-  const int st = validate_normals_grid(grid);
-  if (st) return st;
-  if (!cfg) return VOXE_ERR_NULL_POINTER;
-  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
-  if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
-  if (R == 0 || (!max_weight && !max_trans)) return VOXE_OK;
   DevGrid dg;
-  grid_to_dev(grid, &dg);
   DevCfg dc;
-  sampling_cfg_to_dev(cfg, R, &dc);
+  const int st = sampling_call(grid, cfg, R, rays_o, rays_d, &dg, &dc);
+  if (st) return st;
+  if (R == 0 || (!max_weight && !max_trans)) return VOXE_OK;
   launch_visibility_accumulate(dg, dc, grid->densities, rays_o, rays_d, jitter, max_weight, max_trans, (hipStream_t)stream);
   return finish();
 }
@@ -1511,18 +1527,13 @@ int voxe_visibility_mask(const float* vis, int32_t X, int32_t Y, int32_t Z, floa
 // ---- lifting per-ray values into the grid ----------------------------------------------------------------
 int voxe_lift_accumulate(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
                          const float* jitter, const float* values, int32_t C, int64_t* sum_wv, int64_t* sum_w, void* stream) {
-  const int st = validate_normals_grid(grid);
-  if (st) return st;
-  if (!cfg) return VOXE_ERR_NULL_POINTER;
-  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  if (const int st = sampling_call_shape(grid, cfg, R)) return st;
   if ((values || sum_wv) && (C < 1 || C > 8)) return VOXE_ERR_BAD_SHAPE;
-  // (R == 0: nothing is read, rays and values may be NULL -- an empty tensor has no address)
-  if (R > 0 && (!rays_o || !rays_d || (values == nullptr) != (sum_wv == nullptr))) return VOXE_ERR_NULL_POINTER;
-  if (R == 0 || (!sum_wv && !sum_w)) return VOXE_OK;
   DevGrid dg;
-  grid_to_dev(grid, &dg);
   DevCfg dc;
-  sampling_cfg_to_dev(cfg, R, &dc);
+  if (const int st = sampling_call_rays(grid, cfg, R, rays_o, rays_d, &dg, &dc)) return st;
+  if (R > 0 && (values == nullptr) != (sum_wv == nullptr)) return VOXE_ERR_NULL_POINTER;   // (R == 0: values may be NULL too)
+  if (R == 0 || (!sum_wv && !sum_w)) return VOXE_OK;
   launch_lift_accumulate(dg, dc, grid->densities, rays_o, rays_d, jitter, values, C, reinterpret_cast<long long*>(sum_wv),
                          reinterpret_cast<long long*>(sum_w), (hipStream_t)stream);
   return finish();
@@ -1540,27 +1551,22 @@ size_t voxe_distortion_scratch_bytes(int64_t R) { return distortion_scratch_byte
 int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
                             const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_densities,
                             int32_t accumulate, void* scratch, size_t scratch_bytes, void* stream) {
-  const int st = validate_normals_grid(grid);
+  DevGrid dg;
+  DevCfg dc;
+  const int st = sampling_call(grid, cfg, R, rays_o, rays_d, &dg, &dc);
   if (st) return st;
-  if (!cfg) return VOXE_ERR_NULL_POINTER;
-  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
-  if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
   if (R > 0 && loss_out && (!scratch || scratch_bytes < distortion_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
   const bool clear = d_densities && !accumulate;
   if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
     return VOXE_ERR_LAUNCH;
   if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
-  DevGrid dg;
-  grid_to_dev(grid, &dg);
-  DevCfg dc;
-  sampling_cfg_to_dev(cfg, R, &dc);
   launch_distortion(dg, dc, grid->densities, rays_o, rays_d, jitter, grad_scale, loss_out, ray_loss, d_densities, scratch,
                     (hipStream_t)stream);
   return finish();
 }
 
 int voxe_distortion_debug_lanes(int32_t lanes) {
-  if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8) return VOXE_ERR_BAD_SHAPE;
+  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
   tl_distortion_lanes = lanes;
   return VOXE_OK;
 }
@@ -1612,20 +1618,15 @@ int voxe_background_debug_merge(int32_t mode) {
 int voxe_render_bwd_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
                          const float* jitter, const float* d_colour, const float* d_depth, const float* d_acc, float* d_rays_o,
                          float* d_rays_d, int32_t accumulate, void* stream) {
-  const int st = validate_normals_grid(grid);
-  if (st) return st;
-  if (!cfg) return VOXE_ERR_NULL_POINTER;
-  if (R < 0 || R >= (1LL << 31) || cfg->num_samples <= 0) return VOXE_ERR_BAD_SHAPE;
+  if (const int st = sampling_call_shape(grid, cfg, R)) return st;
   if (grid->feature_kind != VOXE_FEAT_SH || cfg->sh_degree < 0 || cfg->sh_degree > 3) return VOXE_ERR_UNSUPPORTED;
   if (grid->F != 3 * (cfg->sh_degree + 1) * (cfg->sh_degree + 1)) return VOXE_ERR_BAD_SHAPE;
   if (const int se = grid_extent_status(grid, grid->F + 1)) return se;
   if (!grid->features) return VOXE_ERR_NULL_POINTER;
-  if (R > 0 && (!rays_o || !rays_d)) return VOXE_ERR_NULL_POINTER;
-  if (R == 0 || (!d_rays_o && !d_rays_d)) return VOXE_OK;
   DevGrid dg;
-  grid_to_dev(grid, &dg);
   DevCfg dc;
-  sampling_cfg_to_dev(cfg, R, &dc);
+  if (const int st = sampling_call_rays(grid, cfg, R, rays_o, rays_d, &dg, &dc)) return st;
+  if (R == 0 || (!d_rays_o && !d_rays_d)) return VOXE_OK;
   dc.white = cfg->white_bkgd;
   launch_render_rays_bwd(dg, dc, cfg->sh_degree, cfg->render_diffuse, grid->densities, grid->features, rays_o, rays_d, jitter,
                          d_colour, d_depth, d_acc, d_rays_o, d_rays_d, accumulate, (hipStream_t)stream);
@@ -1633,7 +1634,7 @@ int voxe_render_bwd_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, con
 }
 
 int voxe_render_bwd_rays_debug_lanes(int32_t lanes) {
-  if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8) return VOXE_ERR_BAD_SHAPE;
+  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
   tl_rays_bwd_lanes = lanes;
   return VOXE_OK;
 }

@@ -1,7 +1,7 @@
 // voxe_distortion.hip -- distortion loss on rays, value and gradient in one call ("Distortion").
 //
-// Per ray, with the forward's exact samples (RayCtx / DepthGen / inside_range / footprint / post_activate / fast_exp, raw
-// densities with pre_activate per corner as in voxe_normals.hip) and s_k = (z_k - near) / (far - near) from cfg's bounds:
+// Per ray, with the forward's exact samples (voxe_ray_march.hpp: both marches are a march_block over the density sample) and
+// s_k = (z_k - near) / (far - near) from cfg's bounds:
 //   d_k = s_{k+1} - s_k (0 for the last sample),  m_k = s_k + d_k / 2,  w_k = T_k alpha_k
 //   L_r = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
 // The depths of a ray never decrease, so |m_i - m_j| = m_i - m_j for j < i and, with the exclusive prefixes
@@ -10,7 +10,8 @@
 //   g_i = dL_r/dw_i = 2 [(m_i W_i - WM_i) + (WM_tot - WM_i - w_i m_i) - m_i (W_tot - W_i - w_i)] + (2/3) w_i d_i
 //   dL_r/dsigma_k = delta_k [g_k (T_k - w_k) - sum_{i>k} g_i w_i],   sum_i g_i w_i = 2 L_r  (L_r is homogeneous of degree 2)
 //
-// G consecutive lanes share a ray (G in {1, 2, 4, 8}); lane j owns the j-th contiguous block of the ray's S samples.
+// G consecutive lanes share a ray (G in {1, 2, 4, 8}, lanes_per_ray(); WaveRectTile, lane_block and group_exclusive_product of
+// voxe_ray_march.hpp); lane j owns the j-th contiguous block of the ray's S samples.
 //   march 1 : the block with a local T = 1: its transmittance product and A = sum w~, B = sum w~ m, the block's own pair term
 //             P = sum_i w~_i (m_i A_i - B_i) and U = sum w~^2 d.  With T_s the transmittance in front of the block (exclusive
 //             product over the lanes before it) the true weights are w = T_s w~, so the block adds T_s A to W, T_s B to WM and
@@ -25,86 +26,12 @@
 #include <hip/hip_runtime.h>
 
 #include "voxe_launch.hpp"
-#include "voxe_render_common.hpp"
+#include "voxe_ray_march.hpp"
 
 namespace voxe {
 namespace {
 
-constexpr int kDistThreads = 256;
-
-// Pixel rectangle of one block in image order: 4 waves as 2 x 2 rectangles of WW x WH pixels, 64 / G rays each.  G == 1 is
-// map_ray()'s 16 x 16 tile of 8 x 8 sub-tiles; more lanes per ray shrink the rectangle, not its compactness.
-template <int G>
-struct DistTile {
-  static constexpr int kRays = kDistThreads / G;
-  static constexpr int WW = G <= 2 ? 8 : 4;
-  static constexpr int WH = 64 / G / WW;
-  static constexpr int TW = 2 * WW, TH = 2 * WH;
-};
-
-template <int G>
-__device__ __forceinline__ bool distortion_ray(const DevCfg& c, long long& r) {
-  using T = DistTile<G>;
-  const int wave = threadIdx.x >> 6, q = (threadIdx.x & 63) / G;   // ray slot of the wave
-  if (c.image_width > 0) {
-    const int W = c.image_width, H = c.image_height;
-    const long long ntx = (W + T::TW - 1) / T::TW, per = ntx * ((H + T::TH - 1) / T::TH);
-    const long long b = blockIdx.x, img = b / per, t = b - img * per;
-    const int ty = (int)(t / ntx), tx = (int)(t - (long long)ty * ntx);
-    const int px = tx * T::TW + (wave & 1) * T::WW + q % T::WW, py = ty * T::TH + (wave >> 1) * T::WH + q / T::WW;
-    r = (img * H + py) * (long long)W + px;
-    return px < W && py < H && r < c.R;
-  }
-  r = (long long)blockIdx.x * T::kRays + wave * (64 / G) + q;
-  return r < c.R;
-}
-
-template <int G>
-long long distortion_blocks(const DevCfg& c) {
-  using T = DistTile<G>;
-  if (c.image_width > 0) {
-    const long long nimg = c.R / ((long long)c.image_width * c.image_height);
-    return nimg * ((c.image_width + T::TW - 1) / T::TW) * (long long)((c.image_height + T::TH - 1) / T::TH);
-  }
-  return (c.R + T::kRays - 1) / T::kRays;
-}
-
-// One sample of a lane's march: everything the two marches share.  false: the sample fails the AABB test (w = 0).
-struct DistSample {
-  float t[8], raw[8];
-  unsigned idx[8];
-  float delta, e, om, dpost;
-};
-__device__ __forceinline__ bool eval_sample(const DevGrid& g, const RayCtx<1, 1, 1>& rc, const float* __restrict__ dens, float z,
-                                            float dl, DistSample& s) {
-  float p[3];
-  rc.point(z, p);
-  Footprint fp;
-  footprint(g, p, fp);
-  if (!fp.inside) return false;   // sigma = 0 -> w = 0, T unchanged (the forward's rule)
-  Cell cell;
-  make_cell_fast(g, fp, cell);
-  const CellAddr ad = cell_addr(g, cell);
-  // the 8 loads of a sample go out together: one memory latency per sample
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    s.idx[q] = ad.base + (q & 1) * ad.sx + ((q >> 1) & 1) * ad.sy + (q >> 2) * ad.sz;
-    s.raw[q] = dens[s.idx[q]];
-  }
-  float v = 0.0f;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {   // the forward's weights and FMA order (gather(): w = (wx * wy) * wz, corners ascending)
-    s.t[q] = (cell.w[0][q & 1] * cell.w[1][(q >> 1) & 1]) * cell.w[2][q >> 2];
-    v = fmaf(pre_activate(g.pre_act, s.raw[q], g.density_scale), s.t[q], v);
-  }
-  float sigma;
-  post_activate_vg(g.post_act, v, sigma, s.dpost);
-  s.delta = dl * rc.dnorm;
-  s.e = fast_exp(-(sigma * s.delta));
-  const float alpha = 1.0f - s.e;
-  s.om = 1.0f - alpha;
-  return true;
-}
+constexpr int kDistThreads = kMarchThreads;
 
 // inclusive scan over the G lanes of a ray (sum)
 template <int G>
@@ -139,51 +66,43 @@ __global__ __launch_bounds__(kDistThreads) void distortion_kernel(DevGrid g, Dev
                                                                   float* __restrict__ ray_loss, double* __restrict__ partial,
                                                                   float* d_dens) {
   long long r;
-  const bool valid = distortion_ray<G>(c, r);   // (uniform over the G lanes of a ray: every lane joins the shuffles below)
+  const bool valid = group_ray<WaveRectTile<G>>(c, r);   // (uniform over the G lanes of a ray: every lane joins the shuffles below)
   const int j = threadIdx.x % G;
   const double snear = (double)c.near, sinv = 1.0 / ((double)c.far - (double)c.near);
   RayCtx<1, 1, 1> rc;
   int k_lo = 1, k_hi = 0;
   float T = 1.0f;
   double A = 0.0, B = 0.0, P = 0.0, U = 0.0;
+  // one sample of either march: the density sample, then w, d and m in double
+  const auto sample = [&](const DepthStep& st, const Cell& cell, float T, DensityTaps& tp, DensitySample& s, double& w, double& d,
+                          double& m) {
+    load_density(g, dens, cell, tp);
+    eval_density<true>(g, cell, tp, st.dl(), rc.dnorm, s);
+    w = (double)((1.0f - s.e) * T);
+    d = st.last ? 0.0 : ((double)st.z_next - (double)st.z) * sinv;
+    m = ((double)st.z - snear) * sinv + 0.5 * d;
+  };
   if (valid) {
     rc.init(g, c, r, rays_o, rays_d, jitter);
-    const int len = (c.S + G - 1) / G;
-    k_lo = max(rc.k_lo, j * len);
-    k_hi = min(rc.k_hi, min(c.S, (j + 1) * len) - 1);
-    if (k_lo <= k_hi) {
-      float z_next = rc.dg.z(k_lo);
-      for (int k = k_lo; k <= k_hi; ++k) {
-        const float z = z_next;
-        const bool last = (k == c.S - 1);
-        if (!last) z_next = rc.dg.z(k + 1);
-        DistSample s;
-        if (!eval_sample(g, rc, dens, z, last ? kInfinity : (z_next - z), s)) continue;
-        const double w = (double)((1.0f - s.e) * T);
-        const double d = last ? 0.0 : ((double)z_next - (double)z) * sinv;
-        const double m = ((double)z - snear) * sinv + 0.5 * d;
-        P += w * (m * A - B);
-        A += w;
-        B += w * m;
-        U += (w * w) * d;
-        T = T * s.om;
-        if (!(T > 0.0f)) break;   // every later w of the block is 0
-      }
-    }
+    lane_block(c, rc, j, G, k_lo, k_hi);
+    march_block(g, c, rc, k_lo, k_hi, T, [&](const DepthStep& st, const Footprint&, const Cell& cell, float T) {
+      DensityTaps tp;
+      DensitySample s;
+      double w, d, m;
+      sample(st, cell, T, tp, s, w, d, m);
+      P += w * (m * A - B);
+      A += w;
+      B += w * m;
+      U += (w * w) * d;
+      return s.om;   // (T ends: every later w of the block is 0)
+    });
   }
   // the blocks of a ray folded front to back
   float Ts = 1.0f;
   double W0 = 0.0, WM0 = 0.0, Lpre = 0.0;
   double Wtot = A, WMtot = B, Ltot = 2.0 * P + U * (1.0 / 3.0);
   if constexpr (G > 1) {
-    float Pt = T;
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) {
-      const float t = __shfl_up(Pt, off, G);
-      if (j >= off) Pt = Pt * t;
-    }
-    Ts = __shfl_up(Pt, 1, G);
-    if (j == 0) Ts = 1.0f;
+    Ts = group_exclusive_product<G>(T, j);
     const double ts = (double)Ts;
     const double a = ts * A, b = ts * B;
     const double ai = group_scan<G>(a, j), bi = group_scan<G>(b, j);
@@ -207,35 +126,28 @@ __global__ __launch_bounds__(kDistThreads) void distortion_kernel(DevGrid g, Dev
     double W = W0, WM = WM0;
     double GW = 2.0 * Lpre + 2.0 * (W0 * (WMtot - WM0) - WM0 * (Wtot - W0));   // sum g w over the samples in front of the block
     const double total = 2.0 * Ltot;
-    rc.dg.kc = INT_MIN;   // (the jitter window restarts at k_lo)
-    float z_next = rc.dg.z(k_lo);
-    for (int k = k_lo; k <= k_hi; ++k) {
-      const float z = z_next;
-      const bool last = (k == c.S - 1);
-      if (!last) z_next = rc.dg.z(k + 1);
-      DistSample s;
-      if (!eval_sample(g, rc, dens, z, last ? kInfinity : (z_next - z), s)) continue;
-      const double w = (double)((1.0f - s.e) * T);
-      const double d = last ? 0.0 : ((double)z_next - (double)z) * sinv;
-      const double m = ((double)z - snear) * sinv + 0.5 * d;
+    march_block(g, c, rc, k_lo, k_hi, T, [&](const DepthStep& st, const Footprint&, const Cell& cell, float T) {
+      DensityTaps tp;
+      DensitySample s;
+      double w, d, m;
+      sample(st, cell, T, tp, s, w, d, m);
       const double gi = 2.0 * ((m * W - WM) + ((WMtot - WM - w * m) - m * (Wtot - W - w))) + (2.0 / 3.0) * (w * d);
       W += w;
       WM += w * m;
       GW += gi * w;
       // (om == 0: T ends here, every later w is 0 and so is the true suffix; what the subtraction leaves is rounding)
-      const double suffix = (last || !(s.om > 0.0f)) ? 0.0 : (total - GW);
+      const double suffix = (st.last || !(s.om > 0.0f)) ? 0.0 : (total - GW);
       const float dsig = s.delta * (float)(gi * (double)(T * s.e) - suffix);   // T e = T - w
       const float dv = (dsig * s.dpost) * gscale;
       if (dv != 0.0f) {   // adding exact zeros is skipped
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          const float gq = (dv * s.t[q]) * pre_activate_grad(g.pre_act, s.raw[q], g.density_scale);
-          if (gq != 0.0f) atomicAdd(d_dens + s.idx[q], gq);
+          const float gq = (dv * s.t[q]) * pre_activate_grad(g.pre_act, tp.raw[q], g.density_scale);
+          if (gq != 0.0f) atomicAdd(d_dens + tp.idx[q], gq);
         }
       }
-      T = T * s.om;
-      if (!(T > 0.0f)) break;   // every later term is 0
-    }
+      return s.om;   // (T ends: every later term is 0)
+    });
   }
 }
 
@@ -252,7 +164,7 @@ template <int G>
 void launch_distortion_t(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                          const float* jitter, float gscale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
                          hipStream_t st) {
-  const long long nb = distortion_blocks<G>(c);
+  const long long nb = group_blocks<WaveRectTile<G>>(c);
   double* partial = loss_out ? (double*)scratch : nullptr;
   if (d_dens)
     distortion_kernel<G, true><<<(unsigned)nb, kDistThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, gscale, ray_loss,
@@ -267,14 +179,6 @@ void launch_distortion_t(const DevGrid& g, const DevCfg& c, const float* dens, c
 
 thread_local int tl_distortion_lanes = 0;
 
-int distortion_lanes_for(long long R) {
-  if (tl_distortion_lanes) return tl_distortion_lanes;
-  // as normals_lanes_for(): R * G >= 2^20 lane-rays where R allows it, at most 8 lanes per ray
-  for (int G = 1; G < 8; G <<= 1)
-    if (R * G >= (1ll << 20)) return G;
-  return 8;
-}
-
 // one partial per block, and a launch never has more blocks than rays (every pixel tile holds at least one pixel)
 size_t distortion_scratch_bytes(long long R) { return sizeof(double) * (size_t)(R > 0 ? R : 0) + 256; }
 
@@ -282,7 +186,7 @@ void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, con
                        const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
                        hipStream_t st) {
   const float gscale = (float)((double)grad_scale / (double)c.R);
-  switch (distortion_lanes_for(c.R)) {
+  switch (lanes_per_ray(c.R, tl_distortion_lanes)) {
     case 1: launch_distortion_t<1>(g, c, dens, rays_o, rays_d, jitter, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
     case 2: launch_distortion_t<2>(g, c, dens, rays_o, rays_d, jitter, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
     case 4: launch_distortion_t<4>(g, c, dens, rays_o, rays_d, jitter, gscale, loss_out, ray_loss, d_dens, scratch, st); break;

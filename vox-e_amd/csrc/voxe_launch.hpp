@@ -220,8 +220,9 @@ void launch_mesh_count(const VoxeGridDesc* g, float L, const uint8_t* mask, int6
 void launch_mesh_emit(const VoxeGridDesc* g, float L, const uint8_t* mask, float* vertices, long long max_vertices,
                       int32_t* faces, long long max_faces, void* scratch, hipStream_t st);
 
+// The five calls below that take a DevCfg march the forward's samples over the raw densities with voxe_ray_march.hpp
+// (DESIGN.md 4.17); lanes per ray, where a call splits its rays, are lanes_per_ray() there.
 // voxe_normals.hip: density-gradient normals; both read the raw densities only, no workspace
-int normals_lanes_for(long long R);   // lanes per ray of the render kernel (1, 2, 4 or 8)
 void launch_query_normals(const DevGrid& g, const float* dens, const float* points, long long N, float* normals, hipStream_t st);
 void launch_render_normals(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                            const float* jitter, float* normals, float* depth, float* acc, hipStream_t st);
@@ -237,8 +238,7 @@ void launch_lift_accumulate(const DevGrid& g, const DevCfg& c, const float* dens
                             const float* jitter, const float* values, int C, long long* sum_wv, long long* sum_w, hipStream_t st);
 
 // voxe_distortion.hip: distortion loss on rays, value + density gradient; reads the raw densities only
-int distortion_lanes_for(long long R);   // lanes per ray (1, 2, 4 or 8)
-extern thread_local int tl_distortion_lanes;   // test aid (voxe_distortion_debug_lanes): != 0 overrides distortion_lanes_for
+extern thread_local int tl_distortion_lanes;   // test aid (voxe_distortion_debug_lanes): != 0 pins the lanes per ray
 size_t distortion_scratch_bytes(long long R);
 void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                        const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
@@ -246,8 +246,7 @@ void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, con
 
 // voxe_render_rays_bwd.hip: gradient of a render w.r.t. its rays; reads the raw densities and features, no
 // workspace, no atomics
-int rays_bwd_lanes_for(long long R);   // lanes per ray (1, 2, 4 or 8)
-extern thread_local int tl_rays_bwd_lanes;   // test aid (voxe_render_bwd_rays_debug_lanes): != 0 overrides rays_bwd_lanes_for
+extern thread_local int tl_rays_bwd_lanes;   // test aid (voxe_render_bwd_rays_debug_lanes): != 0 pins the lanes per ray
 void launch_render_rays_bwd(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const float* dens, const float* feat,
                             const float* rays_o, const float* rays_d, const float* jitter, const float* g_col,
                             const float* g_depth, const float* g_acc, float* d_o, float* d_d, int accumulate, hipStream_t st);

@@ -1,8 +1,8 @@
 // voxe_lift.hip -- weighted back-projection of per-ray values into the voxel grid ("Lifting").
 //
-//   accumulate : one thread per ray marches the forward's exact samples front to back, exactly as voxe_visibility.hip does
-//                (RayCtx / DepthGen / footprint / make_cell_fast / post_activate / fast_exp, raw densities with pre_activate per
-//                corner), and for every sample inside the box and every corner c of its cell takes  a = w_k * t_c  -- the float
+//   accumulate : one thread per ray marches the forward's exact samples front to back with the pieces of voxe_ray_march.hpp
+//                (depth step, sample cell, the two halves of the density sample; the loop is its own, see "Merge" below), and
+//                for every sample inside the box and every corner c of its cell takes  a = w_k * t_c  -- the float
 //                voxe_visibility_accumulate raises max_weight with, t_c = (wx * wy) * wz, w_k = T_k alpha_k -- and adds
 //                    sum_w[c]      += q(a)
 //                    sum_wv[c, ch] += q(a * values[r, ch])         q(x) = (int64) rint(x * 2^32), a * v rounded to float first
@@ -24,12 +24,12 @@
 #include <climits>
 
 #include "voxe_launch.hpp"
-#include "voxe_render_common.hpp"
+#include "voxe_ray_march.hpp"
 
 namespace voxe {
 namespace {
 
-constexpr int kLiftThreads = 256;   // map_ray(): a 16x16 pixel tile (8x8 per wave) or 256 consecutive rays
+constexpr int kLiftThreads = kMarchThreads;   // map_ray(): a 16x16 pixel tile (8x8 per wave) or 256 consecutive rays
 constexpr float kLiftOne = 4294967296.0f;   // 2^32: the scaling is exact in float
 
 __device__ __forceinline__ long long quantise(float x) { return __float2ll_rn(x * kLiftOne); }
@@ -110,7 +110,8 @@ __global__ __launch_bounds__(kLiftThreads) void lift_accumulate_kernel(DevGrid g
     if (!alive) return;
   }
   float T = 1.0f;
-  float z_next = 0.0f;
+  DepthStep st;
+  st.z_next = 0.0f;
   for (;; ++k) {
     const bool more = alive && k <= k_hi;
     if constexpr (MERGE) {
@@ -125,40 +126,20 @@ __global__ __launch_bounds__(kLiftThreads) void lift_accumulate_kernel(DevGrid g
 #pragma unroll
     for (int q = 0; q < 8; ++q) { idx[q] = 0u; t[q] = 0.0f; }
     if (more && k >= k_lo) {
-      if (k == k_lo) z_next = rc.dg.z(k);
-      const float z = z_next;
-      const bool last = (k == c.S - 1);
-      if (!last) z_next = rc.dg.z(k + 1);
-      float p[3];
-      rc.point(z, p);
-      Footprint fp;
-      footprint(g, p, fp);
-      if (fp.inside) {   // outside: sigma = 0 -> w = 0, T unchanged (the forward's rule); no footprint either
-        Cell cell;
-        make_cell_fast(g, fp, cell);
-        const CellAddr ad = cell_addr(g, cell);
-        float raw[8];
+      if (k == k_lo) st.start(rc, k);
+      st.advance(rc, c, k);
+      SampleCell sc;
+      if (sc.locate(g, rc, st.z)) {
+        sc.make(g);
+        DensityTaps tp;
+        load_density(g, dens, sc.cell, tp);
+        DensitySample s;
+        eval_density<false>(g, sc.cell, tp, st.dl(), rc.dnorm, s);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          idx[q] = ad.base + (q & 1) * ad.sx + ((q >> 1) & 1) * ad.sy + (q >> 2) * ad.sz;
-          raw[q] = dens[idx[q]];
-        }
-        float v = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {   // the forward's weights and FMA order (gather(): w = (wx * wy) * wz, corners ascending)
-          t[q] = (cell.w[0][q & 1] * cell.w[1][(q >> 1) & 1]) * cell.w[2][q >> 2];
-          v = fmaf(pre_activate(g.pre_act, raw[q], g.density_scale), t[q], v);
-        }
-        const float sigma = post_activate(g.post_act, v);
-        const float dl = last ? kInfinity : (z_next - z);
-        const float delta = dl * rc.dnorm;
-        const float e = fast_exp(-(sigma * delta));
-        const float alpha = 1.0f - e;
-        const float om = 1.0f - alpha;
-        w = alpha * T;
+        for (int q = 0; q < 8; ++q) { idx[q] = tp.idx[q]; t[q] = s.t[q]; }
+        w = s.alpha * T;
         has = w > 0.0f;     // (false for NaN)
-        T = T * om;
-        if (!(T > 0.0f)) alive = false;   // every later w is 0 (or NaN): nothing more to add
+        if (!attenuate(T, s.om)) alive = false;   // every later w is 0 (or NaN): nothing more to add
       }
     }
     MergePlan mp;
@@ -198,9 +179,7 @@ constexpr bool kLiftMergeShipped = true;
 void launch_lift_accumulate(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                             const float* jitter, const float* values, int C, long long* sum_wv, long long* sum_w,
                             hipStream_t st) {
-  const long long ntx = c.image_width > 0 ? (c.image_width + 15) / 16 : 1;
-  const long long nty = c.image_width > 0 ? tile_rows_total(c, 16) : (c.R + kLiftThreads - 1) / kLiftThreads;
-  const unsigned nb = (unsigned)blocks_for_tiles(c.map_mode, ntx, nty);
+  const unsigned nb = map_ray_blocks(c);
   const bool merge = tl_lift_merge ? tl_lift_merge == 2 : kLiftMergeShipped;
 #define VOXE_LIFT(CN)                                                                                                          \
   case CN:                                                                                                                     \

@@ -1,7 +1,8 @@
 // voxe_render_rays_bwd.hip -- gradient of a render with respect to its rays ("Ray gradients").
 //
-// Per ray, with the forward's exact samples (RayCtx / DepthGen / inside_range / footprint / post_activate / fast_exp, raw
-// densities with pre_activate per corner and raw feature texels, as voxe_normals.hip / voxe_distortion.hip read them) and the
+// Per ray, with the forward's exact samples (the depth step, sample cell and tail of voxe_ray_march.hpp; the corner loop is this
+// file's own interp_cell, which blends the raw feature texels and the slopes along with the density, and the two loops are
+// written out: handed to march_block as lambdas, the SH-0 kernels are scheduled differently and lose 5 - 9 %) and the
 // upstream gradients g_col [3], g_depth, g_acc of the ray's outputs:
 //   q_k = g_col . rad_k + g_depth z_k + g_acc - (white ? sum_c g_col_c : 0)        (dL/dw_k, w_k = T_k alpha_k)
 //   E_k = q_k (T_k - w_k) - sum_{i>k} w_i q_i
@@ -10,7 +11,7 @@
 //   d_o = sum_k dL/dp_k
 //   d_d = sum_k z_k dL/dp_k + (sum_k sigma_k E_k dl_k) d/|d| + Jn^T (dB/dv)^T m,   m_j = sum_k w_k sum_c s_kc F_cj(p_k)
 // with s_kc = g_col_c rad_kc (1 - rad_kc), F_cj the interpolated SH coefficients, Jn = (I - v v^T) / |d|, v = d / |d|.  grad of
-// an interpolant is its slope inside the cell floor(u) the forward used, zero padding included (voxe_normals.hip's slope_coefs),
+// an interpolant is its slope inside the cell floor(u) the forward used, zero padding included (slope_coefs of voxe_ray_march.hpp),
 // in world units.  The sample depths are constants (no gradient through near / far / the aabb_clip bounds).
 //
 // The slope is linear in the corner values, so the corner loop keeps, per sample, the value and the three slopes of v and of the
@@ -18,7 +19,8 @@
 // value stays live, and the loop over the corners can stay rolled for the wide texels.  m_j takes a second pass over the corners
 // (L2-resident texels) once s_kc is known.
 //
-// G consecutive lanes share a ray (G in {1, 2, 4, 8}); lane j owns the j-th contiguous block of the ray's S samples.
+// G consecutive lanes share a ray (G in {1, 2, 4, 8}, lanes_per_ray(); WaveRectTile, lane_block and group_exclusive_product of
+// voxe_ray_march.hpp); lane j owns the j-th contiguous block of the ray's S samples.
 //   march 1 : the block with a local T = 1: its transmittance product and Q = sum w~ q.
 //   scans   : T_s = exclusive product of the block transmittances; prefix of sum w q = exclusive sum of T_s Q; total.
 //   march 2 : the block again with the true T; per sample the suffix is total - (inclusive prefix); the 3 + 3 + 1 sums of the
@@ -27,48 +29,12 @@
 #include <hip/hip_runtime.h>
 
 #include "voxe_launch.hpp"
-#include "voxe_render_common.hpp"
+#include "voxe_ray_march.hpp"
 
 namespace voxe {
 namespace {
 
-constexpr int kRayThreads = 256;
-
-// Pixel rectangle of one block in image order (voxe_distortion.hip's DistTile): 4 waves as 2 x 2 rectangles of WW x WH pixels
-template <int G>
-struct RayTile {
-  static constexpr int kRays = kRayThreads / G;
-  static constexpr int WW = G <= 2 ? 8 : 4;
-  static constexpr int WH = 64 / G / WW;
-  static constexpr int TW = 2 * WW, TH = 2 * WH;
-};
-
-template <int G>
-__device__ __forceinline__ bool ray_of_group(const DevCfg& c, long long& r) {
-  using T = RayTile<G>;
-  const int wave = threadIdx.x >> 6, q = (threadIdx.x & 63) / G;   // ray slot of the wave
-  if (c.image_width > 0) {
-    const int W = c.image_width, H = c.image_height;
-    const long long ntx = (W + T::TW - 1) / T::TW, per = ntx * ((H + T::TH - 1) / T::TH);
-    const long long b = blockIdx.x, img = b / per, t = b - img * per;
-    const int ty = (int)(t / ntx), tx = (int)(t - (long long)ty * ntx);
-    const int px = tx * T::TW + (wave & 1) * T::WW + q % T::WW, py = ty * T::TH + (wave >> 1) * T::WH + q / T::WW;
-    r = (img * H + py) * (long long)W + px;
-    return px < W && py < H && r < c.R;
-  }
-  r = (long long)blockIdx.x * T::kRays + wave * (64 / G) + q;
-  return r < c.R;
-}
-
-template <int G>
-long long ray_blocks(const DevCfg& c) {
-  using T = RayTile<G>;
-  if (c.image_width > 0) {
-    const long long nimg = c.R / ((long long)c.image_width * c.image_height);
-    return nimg * ((c.image_width + T::TW - 1) / T::TW) * (long long)((c.image_height + T::TH - 1) / T::TH);
-  }
-  return (c.R + T::kRays - 1) / T::kRays;
-}
+constexpr int kRayThreads = kMarchThreads;
 
 struct RayBwdArgs {
   const float *dens, *feat, *rays_o, *rays_d, *jitter;
@@ -77,13 +43,6 @@ struct RayBwdArgs {
   int accumulate;
   int ncm;   // SH coefficients per colour channel in memory (F / 3)
 };
-
-// slope coefficients of one axis in terms of the cell's two corners (voxe_normals.hip): slope = d0 * c0 + d1 * c1
-__device__ __forceinline__ void slope_coefs(int i0, int N, float& d0, float& d1) {
-  const bool lo = i0 < 0, hi = i0 >= N - 1;
-  d0 = lo ? (i0 == -1 ? 1.0f : 0.0f) : (hi ? 0.0f : -1.0f);
-  d1 = lo ? 0.0f : (hi ? (i0 == N - 1 ? -1.0f : 0.0f) : 1.0f);
-}
 
 // value (index 0) and slope along x, y, z in index units (1 .. 3) of the interpolated density and pre-sigmoid radiance
 struct Interp {
@@ -211,7 +170,7 @@ __device__ __forceinline__ void shade(const DevGrid& g, const Interp& it, float 
 template <int G, int NCU>
 __global__ __launch_bounds__(kRayThreads) void render_rays_bwd_kernel(DevGrid g, DevCfg c, RayBwdArgs a) {
   long long r;
-  const bool valid = ray_of_group<G>(c, r);   // (uniform over the G lanes of a ray: every lane joins the shuffles below)
+  const bool valid = group_ray<WaveRectTile<G>>(c, r);   // (uniform over the G lanes of a ray: every lane joins the shuffles below)
   const int j = threadIdx.x % G;
   RayCtx<3, NCU, NCU> rc;
   int k_lo = 1, k_hi = 0;
@@ -225,31 +184,23 @@ __global__ __launch_bounds__(kRayThreads) void render_rays_bwd_kernel(DevGrid g,
     }
     if (a.g_depth) gd = a.g_depth[r];
     q0 = (a.g_acc ? a.g_acc[r] : 0.0f) - (c.white ? (gc[0] + gc[1]) + gc[2] : 0.0f);
-    const int len = (c.S + G - 1) / G;
-    k_lo = max(rc.k_lo, j * len);
-    k_hi = min(rc.k_hi, min(c.S, (j + 1) * len) - 1);
+    lane_block(c, rc, j, G, k_lo, k_hi);
     if (k_lo <= k_hi) {
-      float z_next = rc.dg.z(k_lo);
+      DepthStep st;
+      st.start(rc, k_lo);
       for (int k = k_lo; k <= k_hi; ++k) {
-        const float z = z_next;
-        const bool last = (k == c.S - 1);
-        if (!last) z_next = rc.dg.z(k + 1);
-        float p[3];
-        rc.point(z, p);
-        Footprint fp;
-        footprint(g, p, fp);
-        if (!fp.inside) continue;   // sigma = 0 -> w = 0, T unchanged (the forward's rule)
-        Cell cell;
-        make_cell_fast(g, fp, cell);
+        st.advance(rc, c, k);
+        SampleCell scl;
+        if (!scl.locate(g, rc, st.z)) continue;
+        scl.make(g);
         Interp it;
-        interp_cell<NCU, false>(g, a, fp, cell, rc.basis, it);
+        interp_cell<NCU, false>(g, a, scl.fp, scl.cell, rc.basis, it);
         Shade s;
-        shade(g, it, last ? kInfinity : (z_next - z), rc.dnorm, s);
+        shade(g, it, st.dl(), rc.dnorm, s);
         const float w = (1.0f - s.e) * T;
-        const float qk = fmaf(gc[0], s.rad[0], fmaf(gc[1], s.rad[1], fmaf(gc[2], s.rad[2], fmaf(gd, z, q0))));
+        const float qk = fmaf(gc[0], s.rad[0], fmaf(gc[1], s.rad[1], fmaf(gc[2], s.rad[2], fmaf(gd, st.z, q0))));
         Q += (double)w * (double)qk;
-        T = T * s.om;
-        if (!(T > 0.0f)) break;   // every later w of the block is 0
+        if (!attenuate(T, s.om)) break;   // every later w of the block is 0
       }
     }
   }
@@ -257,14 +208,7 @@ __global__ __launch_bounds__(kRayThreads) void render_rays_bwd_kernel(DevGrid g,
   float Ts = 1.0f;
   double pre = 0.0, total = Q;
   if constexpr (G > 1) {
-    float Pt = T;
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) {
-      const float t = __shfl_up(Pt, off, G);
-      if (j >= off) Pt = Pt * t;
-    }
-    Ts = __shfl_up(Pt, 1, G);
-    if (j == 0) Ts = 1.0f;
+    Ts = group_exclusive_product<G>(T, j);
     const double mine = (double)Ts * Q;
     double inc = mine;
 #pragma unroll
@@ -280,35 +224,28 @@ __global__ __launch_bounds__(kRayThreads) void render_rays_bwd_kernel(DevGrid g,
 #pragma unroll
   for (int i = 0; i < NCU; ++i) m[i] = 0.0f;
   if (valid && k_lo <= k_hi && Ts > 0.0f) {
-    const int N[3] = {g.X, g.Y, g.Z};
-    float gs[3];   // index units -> world units
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) gs[ax] = ((float)N[ax] * g.scale[ax]) * 0.5f;
+    float gs[3];
+    index_to_world(g, gs);
     T = Ts;
     double GW = pre;   // sum w q over the samples up to and including the current one
-    rc.dg.kc = INT_MIN;   // (the jitter window restarts at k_lo)
-    float z_next = rc.dg.z(k_lo);
+    DepthStep st;
+    st.start(rc, k_lo);
     for (int k = k_lo; k <= k_hi; ++k) {
-      const float z = z_next;
-      const bool last = (k == c.S - 1);
-      if (!last) z_next = rc.dg.z(k + 1);
-      float p[3];
-      rc.point(z, p);
-      Footprint fp;
-      footprint(g, p, fp);
-      if (!fp.inside) continue;
-      Cell cell;
-      make_cell_fast(g, fp, cell);
+      st.advance(rc, c, k);
+      SampleCell scl;
+      if (!scl.locate(g, rc, st.z)) continue;
+      scl.make(g);
+      const Cell& cell = scl.cell;
       Interp it;
-      interp_cell<NCU, true>(g, a, fp, cell, rc.basis, it);
-      const float dl = last ? kInfinity : (z_next - z);
+      interp_cell<NCU, true>(g, a, scl.fp, cell, rc.basis, it);
+      const float z = st.z, dl = st.dl();
       Shade s;
       shade(g, it, dl, rc.dnorm, s);
       const float w = (1.0f - s.e) * T;
       const float qk = fmaf(gc[0], s.rad[0], fmaf(gc[1], s.rad[1], fmaf(gc[2], s.rad[2], fmaf(gd, z, q0))));
       GW += (double)w * (double)qk;
       // (om == 0: T ends here, every later w is 0 and so is the true suffix; what the subtraction leaves is rounding)
-      const double suffix = (last || !(s.om > 0.0f)) ? 0.0 : (total - GW);
+      const double suffix = (st.last || !(s.om > 0.0f)) ? 0.0 : (total - GW);
       const float E = (float)((double)qk * (double)(T * s.e) - suffix);   // T e = T - w
       const float cd = (s.delta * E) * s.dpost;
       float sc[3];
@@ -330,8 +267,7 @@ __global__ __launch_bounds__(kRayThreads) void render_rays_bwd_kernel(DevGrid g,
           basis_moments<NCU>(g, a, cell, ws, m);
         }
       }
-      T = T * s.om;
-      if (!(T > 0.0f)) break;   // every later term is 0
+      if (!attenuate(T, s.om)) break;   // every later term is 0
     }
   }
   if constexpr (G > 1) {
@@ -364,7 +300,7 @@ __global__ __launch_bounds__(kRayThreads) void render_rays_bwd_kernel(DevGrid g,
 
 template <int G, int NCU>
 void launch_t(const DevGrid& g, const DevCfg& c, const RayBwdArgs& a, hipStream_t st) {
-  render_rays_bwd_kernel<G, NCU><<<(unsigned)ray_blocks<G>(c), kRayThreads, 0, st>>>(g, c, a);
+  render_rays_bwd_kernel<G, NCU><<<(unsigned)group_blocks<WaveRectTile<G>>(c), kRayThreads, 0, st>>>(g, c, a);
 }
 
 template <int NCU>
@@ -381,20 +317,12 @@ void launch_g(int G, const DevGrid& g, const DevCfg& c, const RayBwdArgs& a, hip
 
 thread_local int tl_rays_bwd_lanes = 0;
 
-int rays_bwd_lanes_for(long long R) {
-  if (tl_rays_bwd_lanes) return tl_rays_bwd_lanes;
-  // as distortion_lanes_for(): R * G >= 2^20 lane-rays where R allows it, at most 8 lanes per ray
-  for (int G = 1; G < 8; G <<= 1)
-    if (R * G >= (1ll << 20)) return G;
-  return 8;
-}
-
 void launch_render_rays_bwd(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const float* dens, const float* feat,
                             const float* rays_o, const float* rays_d, const float* jitter, const float* g_col,
                             const float* g_depth, const float* g_acc, float* d_o, float* d_d, int accumulate, hipStream_t st) {
   const int ncm = (deg + 1) * (deg + 1);
   const RayBwdArgs a{dens, feat, rays_o, rays_d, jitter, g_col, g_depth, g_acc, d_o, d_d, accumulate, ncm};
-  const int G = rays_bwd_lanes_for(c.R);
+  const int G = lanes_per_ray(c.R, tl_rays_bwd_lanes);
   switch (diffuse ? 1 : ncm) {
     case 1: launch_g<1>(G, g, c, a, st); break;
     case 4: launch_g<4>(G, g, c, a, st); break;

@@ -1,7 +1,7 @@
 // voxe_visibility.hip -- per-voxel visibility of a voxel grid under a set of rays ("Visibility").
 //
-//   accumulate : one thread per ray marches the forward's exact samples front to back (RayCtx / DepthGen / inside_range /
-//                footprint / post_activate / fast_exp, raw densities with pre_activate per corner as in voxe_normals.hip) and,
+//   accumulate : one thread per ray marches the forward's exact samples front to back (voxe_ray_march.hpp: march_block with
+//                the two halves of the density sample) and,
 //                for every sample inside the box and every corner c of its cell with gather weight t_c = (wx * wy) * wz,
 //                raises  max_weight[c] to w_k * t_c  and  max_trans[c] to T_k (where t_c > 0),  w_k = T_k * alpha_k, T_k the
 //                transmittance on arrival.  Non-negative floats order like their bit patterns, so the update is an unsigned
@@ -15,12 +15,12 @@
 #include <hip/hip_runtime.h>
 
 #include "voxe_launch.hpp"
-#include "voxe_render_common.hpp"
+#include "voxe_ray_march.hpp"
 
 namespace voxe {
 namespace {
 
-constexpr int kVisThreads = 256;          // map_ray(): a 16x16 pixel tile (8x8 per wave) or 256 consecutive rays
+constexpr int kVisThreads = kMarchThreads;   // map_ray(): a 16x16 pixel tile (8x8 per wave) or 256 consecutive rays
 constexpr int kMaskMaxBlocks = 8192;      // grid-stride beyond this
 
 // buf[i] = max(buf[i], v) for v > 0 on the uint32 view (no-return atomic); `seen` = what a plain load of buf[i] returned before:
@@ -40,63 +40,35 @@ __global__ __launch_bounds__(kVisThreads) void visibility_accumulate_kernel(DevG
   if (!map_ray(c, r)) return;
   RayCtx<1, 1, 1> rc;
   rc.init(g, c, r, rays_o, rays_d, jitter);
-  if (rc.k_lo > rc.k_hi) return;
   float T = 1.0f;
-  float z_next = rc.dg.z(rc.k_lo);
-  for (int k = rc.k_lo; k <= rc.k_hi; ++k) {
-    const float z = z_next;
-    const bool last = (k == c.S - 1);
-    if (!last) z_next = rc.dg.z(k + 1);
-    float p[3];
-    rc.point(z, p);
-    Footprint fp;
-    footprint(g, p, fp);
-    if (!fp.inside) continue;   // sigma = 0 -> w = 0, T unchanged (the forward's rule); no footprint either
-    Cell cell;
-    make_cell_fast(g, fp, cell);
-    const CellAddr ad = cell_addr(g, cell);
-    unsigned idx[8], seen_w[8], seen_t[8];
-    float raw[8], t[8];
+  march_block(g, c, rc, rc.k_lo, rc.k_hi, T, [&](const DepthStep& st, const Footprint&, const Cell& cell, float T) {
+    DensityTaps tp;
+    unsigned seen_w[8], seen_t[8];
     // the 8 densities and the stored values of the 16 pre-checks do not depend on each other: all loads go out together, one
     // memory latency per sample instead of one per corner
+    load_density(g, dens, cell, tp);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      idx[q] = ad.base + (q & 1) * ad.sx + ((q >> 1) & 1) * ad.sy + (q >> 2) * ad.sz;
-      raw[q] = dens[idx[q]];
-    }
+    for (int q = 0; q < 8; ++q) seen_t[q] = max_trans ? max_trans[tp.idx[q]] : 0u;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) seen_t[q] = max_trans ? max_trans[idx[q]] : 0u;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) seen_w[q] = max_weight ? max_weight[idx[q]] : 0u;
-    float v = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {   // the forward's weights and FMA order (gather(): w = (wx * wy) * wz, corners ascending)
-      t[q] = (cell.w[0][q & 1] * cell.w[1][(q >> 1) & 1]) * cell.w[2][q >> 2];
-      v = fmaf(pre_activate(g.pre_act, raw[q], g.density_scale), t[q], v);
-    }
-    const float sigma = post_activate(g.post_act, v);
-    const float dl = last ? kInfinity : (z_next - z);
-    const float delta = dl * rc.dnorm;
-    const float e = fast_exp(-(sigma * delta));
-    const float alpha = 1.0f - e;
-    const float om = 1.0f - alpha;
-    const float w = alpha * T;
+    for (int q = 0; q < 8; ++q) seen_w[q] = max_weight ? max_weight[tp.idx[q]] : 0u;
+    DensitySample s;
+    eval_density<false>(g, cell, tp, st.dl(), rc.dnorm, s);
+    const float w = s.alpha * T;
     // (corners make_cell moved into the grid carry weight 0: only footprint corners inside the grid are ever raised)
     if (max_trans && T > 0.0f) {
 #pragma unroll
       for (int q = 0; q < 8; ++q)
-        if (t[q] > 0.0f) raise_to(max_trans, idx[q], T, seen_t[q]);
+        if (s.t[q] > 0.0f) raise_to(max_trans, tp.idx[q], T, seen_t[q]);
     }
     if (max_weight && w > 0.0f) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float cw = w * t[q];
-        if (cw > 0.0f) raise_to(max_weight, idx[q], cw, seen_w[q]);
+        const float cw = w * s.t[q];
+        if (cw > 0.0f) raise_to(max_weight, tp.idx[q], cw, seen_w[q]);
       }
     }
-    T = T * om;
-    if (!(T > 0.0f)) break;   // every later w and T is 0 (or NaN): nothing more to raise
-  }
+    return s.om;   // (T ends: every later w and T is 0, nothing more to raise)
+  });
 }
 
 __global__ __launch_bounds__(kVisThreads) void visibility_mask_kernel(const float* __restrict__ vis, int X, int Y, int Z,
@@ -121,10 +93,7 @@ __global__ __launch_bounds__(kVisThreads) void visibility_mask_kernel(const floa
 
 void launch_visibility_accumulate(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                                   const float* jitter, float* max_weight, float* max_trans, hipStream_t st) {
-  const long long ntx = c.image_width > 0 ? (c.image_width + 15) / 16 : 1;
-  const long long nty = c.image_width > 0 ? tile_rows_total(c, 16) : (c.R + kVisThreads - 1) / kVisThreads;
-  const int nb = blocks_for_tiles(c.map_mode, ntx, nty);
-  visibility_accumulate_kernel<<<(unsigned)nb, kVisThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter,
+  visibility_accumulate_kernel<<<map_ray_blocks(c), kVisThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter,
                                                                      reinterpret_cast<unsigned*>(max_weight),
                                                                      reinterpret_cast<unsigned*>(max_trans));
 }
