@@ -786,6 +786,43 @@ int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
 int voxe_distortion_debug_lanes(int32_t lanes);
 
 /* ------------------------------------------------------------------------------------------------
+ * SSIM of two image batches, value and gradient in one call (additive; still ABI v13), DESIGN.md section 4.18 "SSIM".  No
+ * voxe_cpu_ twin; the float64 restatement is tests/ssim_ref.py.
+ *   x, y: device float, channel-last [N,H,W,C], C in 1..4 (a render's colour viewed as patches or as an image).  Wang et al.
+ *   2004: an 11 x 11 Gaussian window of sigma 1.5 -- g1[i] ~ exp(-(i-5)^2 / 4.5), normalised to sum 1 in double, then rounded to
+ *   float; the 2-D window is the outer product -- over VALID windows only: an H x W image gives an (H-10) x (W-10) map, there
+ *   is no padding of any kind.  With L = data_range, C1 = (0.01 L)^2, C2 = (0.03 L)^2 and, per window, channel and image, the
+ *   window sums m_x = sum g x, m_y, m_xx = sum g x^2, m_yy, m_xy:
+ *       vx = m_xx - m_x^2,  vy = m_yy - m_y^2,  vxy = m_xy - m_x m_y
+ *       A1 = 2 m_x m_y + C1,  A2 = 2 vxy + C2,  B1 = m_x^2 + m_y^2 + C1,  B2 = vx + vy + C2
+ *       S = A1 A2 / (B1 B2),   ssim = mean of S over all M = N C (H-10) (W-10) windows
+ *   Gradient w.r.t. x only (y is a target and receives none):
+ *       Q = dS/dm_xx = -S / B2,   R = dS/dm_xy = 2 A1 / (B1 B2)
+ *       P = dS/dm_x  = 2 m_y (A2 - A1) / (B1 B2) + 2 m_x S (1/B2 - 1/B1)
+ *       dssim/dx_p = (1/M) sum_{windows q containing p} g(p - q) [P_q + 2 x_p Q_q + y_p R_q]
+ *   Outputs (each may be NULL): mean_out  device float[1], the mean over all windows (grad_scale does not apply to it);
+ *                               per_image device [N], the mean over the windows of one image;
+ *                               ssim_map  device [N,H-10,W-10,C], S;
+ *                               d_x       device [N,H,W,C] = grad_scale * dssim/dx, written to every element, or added to the
+ *                                         buffer when accumulate != 0.  NULL skips the gradient.
+ *   The window sums, S, P, Q, R and the transposed passes of the gradient are double; the images and the three maps the
+ *   gradient passes through `scratch` are float.  No atomics: every output has the same bits on every run.  `scratch`
+ *   (voxe_ssim_scratch_bytes(N, H, W, C, d_x != NULL); 0 for shapes the call refuses) carries the per-block partial sums and
+ *   the maps; its contents mean nothing between calls.  All four outputs NULL: VOXE_OK with no launch.  Caller's stream, no
+ *   host synchronisation, no allocation.  Validation, before any device work: x, y or scratch NULL -> VOXE_ERR_NULL_POINTER;
+ *   N < 1, H < 11, W < 11, C outside 1..4, data_range <= 0 (or more than 2^31-1 16 x 16 tiles) -> VOXE_ERR_BAD_SHAPE; scratch too
+ *   small -> VOXE_ERR_WORKSPACE.                                                                                           */
+size_t voxe_ssim_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t with_grad);
+int voxe_ssim_fwd_bwd(const float* x, const float* y, int32_t N, int32_t H, int32_t W, int32_t C,
+                      float data_range, float grad_scale,
+                      float* mean_out   /* device float[1] or NULL */,
+                      float* per_image  /* device [N] or NULL */,
+                      float* ssim_map   /* device [N,H-10,W-10,C] or NULL */,
+                      float* d_x        /* device [N,H,W,C] or NULL: skip the gradient */,
+                      int32_t accumulate,
+                      void* scratch, size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Ray and camera-pose gradients (additive; still ABI v13), DESIGN.md section 4.13 "Ray gradients".  No voxe_cpu_ twin; the
  * float64 restatement is tests/ray_grad_ref.py.
  *

@@ -79,6 +79,10 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
               help="N > 0: learn an environment-map background of N x 2N texels behind the grid (needs --white_bkgd False); 0 = off")
 @click.option("--background_learning_rate", type=click.FloatRange(min=0.0), default=None,
               help="Adam rate of the background's texels (default: --learning_rate)")
+@click.option("--ssim_weight", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
+              help="weight of a D-SSIM term, weight * (1 - SSIM), on random pixel patches instead of a random pixel set; 0 = off")
+@click.option("--ssim_patch_size", type=click.IntRange(min=11), default=32, show_default=True,
+              help="side of the SSIM term's pixel patches (a stage with smaller images uses its smaller side)")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -117,7 +121,7 @@ def main(**kwargs) -> None:
         summary_freq=cfg.summary_frequency, verbose_rendering=cfg.verbose_rendering, lpips_weight=cfg.lpips_weight,
         num_workers=cfg.num_workers, distortion_weight=cfg.distortion_weight, pose_learning_rate=cfg.pose_learning_rate,
         intrinsics_learning_rate=cfg.intrinsics_learning_rate, background_resolution=cfg.background_resolution,
-        background_learning_rate=cfg.background_learning_rate)
+        background_learning_rate=cfg.background_learning_rate, ssim_weight=cfg.ssim_weight, ssim_patch_size=cfg.ssim_patch_size)
 
 
 if __name__ == "__main__":

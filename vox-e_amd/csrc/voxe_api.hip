@@ -1571,6 +1571,29 @@ int voxe_distortion_debug_lanes(int32_t lanes) {
   return VOXE_OK;
 }
 
+// ---- SSIM of channel-last images --------------------------------------------------------------------------
+namespace {
+bool ssim_shape_ok(int32_t N, int32_t H, int32_t W, int32_t C) { return N >= 1 && H >= 11 && W >= 11 && C >= 1 && C <= 4; }
+}  // namespace
+
+size_t voxe_ssim_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t with_grad) {
+  return ssim_shape_ok(N, H, W, C) ? ssim_scratch_bytes(N, H, W, C, with_grad) : 0;
+}
+
+int voxe_ssim_fwd_bwd(const float* x, const float* y, int32_t N, int32_t H, int32_t W, int32_t C, float data_range, float grad_scale,
+                      float* mean_out, float* per_image, float* ssim_map, float* d_x, int32_t accumulate, void* scratch,
+                      size_t scratch_bytes, void* stream) {
+  if (!x || !y || !scratch) return VOXE_ERR_NULL_POINTER;
+  if (!ssim_shape_ok(N, H, W, C) || !(data_range > 0.0f)) return VOXE_ERR_BAD_SHAPE;
+  const size_t need = ssim_scratch_bytes(N, H, W, C, d_x != nullptr);
+  if (need == 0) return VOXE_ERR_BAD_SHAPE;   // more 16 x 16 tiles than one launch holds
+  if (scratch_bytes < need) return VOXE_ERR_WORKSPACE;
+  if (!mean_out && !per_image && !ssim_map && !d_x) return VOXE_OK;
+  launch_ssim(x, y, N, H, W, C, data_range, grad_scale, mean_out, per_image, ssim_map, d_x, accumulate, scratch,
+              (hipStream_t)stream);
+  return finish();
+}
+
 // ---- environment-map background behind the grid ----------------------------------------------------------
 namespace {
 // the checks the two background calls share; *done: the call ends here with the returned status

@@ -273,6 +273,11 @@ void launch_background_bwd(const float* texels, int He, int We, const float* ray
                            const float* d_colour_out, float* d_acc, float* d_texels, float* d_rays_d, bool accumulate,
                            hipStream_t st);
 
+// voxe_ssim.hip: SSIM of channel-last images, value + gradient to x; arguments validated by the API
+size_t ssim_scratch_bytes(int N, int H, int W, int C, int with_grad);   // 0: the launch would not fit (too many blocks)
+void launch_ssim(const float* x, const float* y, int N, int H, int W, int C, float data_range, float grad_scale, float* mean_out,
+                 float* per_image, float* ssim_map, float* d_x, int accumulate, void* scratch, hipStream_t st);
+
 // voxe_transform.hip: rigid transform / re-gridding / composition of grids; arguments validated by the API
 void launch_grid_resample(const float* src_dens, const float* src_feat, int X, int Y, int Z, int C, float* dst_dens, float* dst_feat,
                           int X2, int Y2, int Z2, const VoxeResample& xf, uint8_t* taken, hipStream_t st);

@@ -1,7 +1,7 @@
 """Held-out evaluation of a trained model (interface of the reference's thre3d_atom/modules/testers.py:17-71).
 
 Every test view is one fused HIP forward launch (`optimized_sampling=True`, `render_num_samples_per_ray` samples, like
-the reference); PSNR is computed on the GPU.  LPIPS needs the external `lpips` network: it is reported when that
+the reference); PSNR and SSIM (voxe_hip.ops.ssim; not in the reference) are computed on the GPU.  LPIPS needs the external `lpips` network: it is reported when that
 package is importable and skipped otherwise (the reference hard-requires it)."""
 from typing import Any, Dict, Optional
 
@@ -12,7 +12,7 @@ from torch.nn.functional import mse_loss
 from thre3d_atom.modules.volumetric_model import VolumetricModel
 from thre3d_atom.utils.imaging_utils import CameraPose
 from thre3d_atom.utils.logging import log
-from thre3d_atom.utils.metric_utils import mse2psnr
+from thre3d_atom.utils.metric_utils import SSIM_MIN_SIDE, mse2psnr, ssim
 
 
 def test_sh_vox_grid_vol_mod_with_posed_images(
@@ -32,7 +32,7 @@ def test_sh_vox_grid_vol_mod_with_posed_images(
         lpips_net = lpips.LPIPS(net="vgg").to(vol_mod.device)
     except ImportError:
         pass
-    psnrs, lpipss = [], []
+    psnrs, lpipss, ssims = [], [], []
     for index in range(len(dataset)):
         image, pose, _ = dataset[index]
         image, pose = image.to(vol_mod.device), pose
@@ -43,15 +43,22 @@ def test_sh_vox_grid_vol_mod_with_posed_images(
         colour = rendered.colour.permute(2, 0, 1)
         with torch.no_grad():
             psnrs.append(float(mse2psnr(mse_loss(colour, image).item())))
+            if min(colour.shape[1:]) >= SSIM_MIN_SIDE:   # smaller views have no 11 x 11 window: skipped for this key
+                ssims.append(ssim(rendered.colour, image.permute(1, 2, 0)))
             if lpips_net is not None:
                 lpipss.append(float(lpips_net(colour[None], image[None], normalize=True).item()))
     out = {"psnr": float(np.mean(psnrs))}
     log.info(f"Mean PSNR on holdout set: {out['psnr']}")
+    if ssims:
+        out["ssim"] = float(np.mean(ssims))
+        log.info(f"Mean SSIM on holdout set: {out['ssim']}")
     if lpipss:
         out["lpips"] = float(np.mean(lpipss))
         log.info(f"Mean LPIPS on holdout set: {out['lpips']}")
     if tensorboard_writer is not None and global_step is not None:
         tensorboard_writer.add_scalar("TEST_SET_PSNR", out["psnr"], global_step=global_step)
+        if "ssim" in out:
+            tensorboard_writer.add_scalar("TEST_SET_SSIM", out["ssim"], global_step=global_step)
         if "lpips" in out:
             tensorboard_writer.add_scalar("TEST_SET_LPIPS", out["lpips"], global_step=global_step)
     return out

@@ -17,7 +17,8 @@ from torch import Tensor
 from thre3d_atom.modules.optim import FusedGridAdam, VoxeAdam
 from thre3d_atom.modules.testers import test_sh_vox_grid_vol_mod_with_posed_images
 from thre3d_atom.modules.volumetric_model import VolumetricModel
-from thre3d_atom.rendering.volumetric.utils.misc import is_general_camera, sample_random_rays_and_pixels_from_cameras
+from thre3d_atom.rendering.volumetric.utils.misc import (is_general_camera, sample_random_patches_and_pixels_from_cameras,
+                                                          sample_random_rays_and_pixels_from_cameras)
 from thre3d_atom.thre3d_reprs.background import EnvMapBackground
 from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, LearnedIntrinsics, write_camera_params
 from thre3d_atom.thre3d_reprs.renderers import _render_params, render_sh_voxel_grid
@@ -27,7 +28,11 @@ from thre3d_atom.utils.imaging_utils import CameraPose, to8b
 from thre3d_atom.utils.logging import log
 from thre3d_atom.utils.metric_utils import mse2psnr
 from thre3d_atom.utils.misc import compute_thre3d_grid_sizes
+from voxe_hip import ops as _ops
 from voxe_hip.ops import _next_rng
+
+
+_SSIM_MIN_PATCH = 11   # SSIM's window: a smaller patch has no valid window
 
 
 class _PinnedStaging:
@@ -103,11 +108,19 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                        # is not the one-call one either (voxe_recon_step knows no background)
     background_learning_rate: Optional[float] = None,   # Adam rate of the background's texels; None = `learning_rate`, with the
                                                         # same stage decay
+    ssim_weight: float = 0.0,          # addition of this build: weight of a D-SSIM term, ssim_weight * (1 - SSIM) on pixel patches
+                                       # (voxe_hip.ops.ssim); 0 = off, nothing changes.  Above 0 the batch is
+                                       # floor(ray_batch_size / P^2) random P x P patches instead of a random pixel set (the L1
+                                       # terms run over the same pixels) and the iteration is not the one-call one either
+    ssim_patch_size: int = 32,         # P; a stage whose images are smaller uses min(H, W), and skips the term below 11
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
     if lpips_weight != 0.0:
         raise NotImplementedError("LPIPS needs the external `lpips` network; not part of this build")
+    if ssim_weight < 0.0 or (ssim_weight > 0.0 and ssim_patch_size < _SSIM_MIN_PATCH):
+        raise ValueError(f"ssim_weight must not be negative and ssim_patch_size at least {_SSIM_MIN_PATCH} (SSIM's window); got "
+                         f"{ssim_weight} and {ssim_patch_size}")
     if background_resolution < 0 or background_resolution == 1:
         raise ValueError(f"background_resolution must be 0 (off) or at least 2; got {background_resolution}")
     if background_resolution > 0:
@@ -205,6 +218,19 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 log.info("background_resolution > 0: the iterations render, composite the background and step separately (no "
                          "one-call iteration)")
             one_call = False
+        patch = 0   # side of this stage's SSIM patches; 0: the term is off and the batch is the random pixel set
+        if ssim_weight > 0.0:
+            if one_call and stage == 1:
+                log.info("ssim_weight > 0: the iterations draw pixel patches, render, add the term and step separately (no one-call "
+                         "iteration)")
+            one_call = False
+            patch = min(int(ssim_patch_size), int(intr.height), int(intr.width))
+            if patch < _SSIM_MIN_PATCH:
+                log.info(f"stage {stage}: images [{intr.height} x {intr.width}] are smaller than SSIM's {_SSIM_MIN_PATCH} x "
+                         f"{_SSIM_MIN_PATCH} window: no SSIM term in this stage")
+                patch = 0
+            elif patch * patch > ray_batch_size:
+                raise ValueError(f"ray_batch_size {ray_batch_size} holds no {patch} x {patch} patch")
         if is_general_camera(intr):
             # voxe_recon_step casts (height, width, focal) cameras only: fx != fy, an off-centre principal point or a lens model
             # takes the composed iteration with voxe_cast_rays_camera
@@ -254,11 +280,16 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         poses_batch, refine = pose_deltas.apply(poses_batch, picks), {"differentiable": True}
                         if learned_intrinsics is not None:
                             refine["intrinsics"] = learned_intrinsics.values / stage_factor
-                    rays_batch, pixels_batch = sample_random_rays_and_pixels_from_cameras(
-                        intr, poses_batch, data.images, ray_batch_size, image_ids=picks, **refine,
-                        # (sorting the batch by (camera, row, column) helps the ray-ordered gather of small batches; batches of
-                        #  16384+ rays take the space-binned render, which does not care about the order: skip the sort)
-                        memory_order=ray_batch_size < 16384, fast_subset=True)
+                    if patch:
+                        num_patches = ray_batch_size // (patch * patch)
+                        rays_batch, pixels_batch = sample_random_patches_and_pixels_from_cameras(
+                            intr, poses_batch, data.images, num_patches, patch, image_ids=picks, **refine)
+                    else:
+                        rays_batch, pixels_batch = sample_random_rays_and_pixels_from_cameras(
+                            intr, poses_batch, data.images, ray_batch_size, image_ids=picks, **refine,
+                            # (sorting the batch by (camera, row, column) helps the ray-ordered gather of small batches; batches of
+                            #  16384+ rays take the space-binned render, which does not care about the order: skip the sort)
+                            memory_order=ray_batch_size < 16384, fast_subset=True)
                     specular = vol_mod.render_rays(rays_batch).colour
                     loss = torch.nn.functional.l1_loss(specular, pixels_batch)
                     psnr = mse2psnr(torch.nn.functional.mse_loss(specular.detach(), pixels_batch))
@@ -270,6 +301,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         #  densities.grad, which step() adds; under VoxeAdam plain autograd sums both)
                         distortion = vol_mod.distortion_loss(rays_batch)
                         loss = loss + distortion_weight * distortion
+                    if patch:
+                        # (the batch is patch-major, row, column: the render's colour viewed as channel-last patches)
+                        shape = (num_patches, patch, patch, specular.shape[-1])
+                        ssim, _ = _ops.ssim(specular.view(shape), pixels_batch.contiguous().view(shape))
+                        loss = loss + ssim_weight * (1.0 - ssim)
                     optimizer.zero_grad()
                     if pose_optimizer is not None:
                         pose_optimizer.zero_grad()
@@ -290,7 +326,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         psnr = mse2psnr(torch.tensor(mse_spec))
                     log.info(f"Stage: {stage} Global Iteration: {global_step} Stage Iteration: {it} "
                              f"loss: {float(loss.detach()): .3f} psnr: {float(psnr): .3f}"
-                             + (f" distortion: {float(distortion.detach()): .6f}" if distortion_weight > 0.0 else ""))
+                             + (f" distortion: {float(distortion.detach()): .6f}" if distortion_weight > 0.0 else "")
+                             + (f" ssim: {float(ssim.detach()): .4f}" if patch else ""))
                 if it % lr_decay_steps_per_stage == 0:
                     scheduler.step()
                     if background_scheduler is not None:

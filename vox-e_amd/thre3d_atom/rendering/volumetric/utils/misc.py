@@ -108,19 +108,57 @@ def sample_random_rays_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsi
         subset = torch.randperm(K * per, dtype=torch.long, device=images.device)[:sample_size]
     if memory_order:
         subset = torch.sort(subset).values
+    return _cast_and_gather(camera_intrinsics, poses, images, subset, image_ids, differentiable, intrinsics)
+
+
+def _cast_and_gather(camera_intrinsics: CameraIntrinsics, poses: Tensor, images: Tensor, flat_index: Tensor, image_ids: Any,
+                     differentiable: bool, intrinsics: Any) -> Tuple[Rays, Tensor]:
+    """rays and target pixels of flat (camera, row, column) indices: the cast branches and the gather the samplers share"""
+    height, width, focal = camera_intrinsics
+    per = int(height) * int(width)
     if intrinsics is not None or is_general_camera(camera_intrinsics):
         if differentiable:
-            origins, directions = _ops.cast_rays_from_camera(camera_intrinsics, poses, subset, intrinsics=intrinsics)
+            origins, directions = _ops.cast_rays_from_camera(camera_intrinsics, poses, flat_index, intrinsics=intrinsics)
         else:
-            origins, directions = _ops.cast_rays_camera(camera_intrinsics, poses, subset, intrinsics=intrinsics)
+            origins, directions = _ops.cast_rays_camera(camera_intrinsics, poses, flat_index, intrinsics=intrinsics)
     else:
         cast = _ops.cast_rays_from_poses if differentiable else _ops.cast_rays_indexed
-        origins, directions = cast(height, width, focal, poses, subset)
-    cam = torch.div(subset, per, rounding_mode="floor")
-    rem = subset - cam * per
+        origins, directions = cast(height, width, focal, poses, flat_index)
+    cam = torch.div(flat_index, per, rounding_mode="floor")
+    rem = flat_index - cam * per
     rows = cam if image_ids is None else torch.as_tensor(image_ids, device=images.device, dtype=torch.long)[cam]
     pixels = images[rows, :, torch.div(rem, int(width), rounding_mode="floor"), rem % int(width)]
     return Rays(origins, directions), pixels
+
+
+def patch_flat_indices(cameras: Tensor, top: Tensor, left: Tensor, patch_size: int, height: int, width: int) -> Tensor:
+    """Flat (camera, row, column) indices, camera * H * W + row * W + column, of square patches given by their camera and top-left
+    corner ([n] long tensors, any device): [n * P * P] in patch-major, row, column order.  Pure index arithmetic."""
+    P = int(patch_size)
+    offs = torch.arange(P, dtype=torch.long, device=cameras.device)
+    rows = top.long()[:, None, None] + offs[None, :, None]
+    cols = left.long()[:, None, None] + offs[None, None, :]
+    return ((cameras.long()[:, None, None] * int(height) + rows) * int(width) + cols).reshape(-1)
+
+
+def sample_random_patches_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsics, poses: Tensor, images: Tensor,
+                                                  num_patches: int, patch_size: int, image_ids: Any = None,
+                                                  differentiable: bool = False, intrinsics: Any = None) -> Tuple[Rays, Tensor]:
+    """`num_patches` square patches of `patch_size` pixels a side for a loss that sees neighbourhoods (SSIM): each patch has a
+    uniformly random camera among the K of `poses` and a uniformly random top-left corner in [0, H-P] x [0, W-P]; the flat
+    indices are built on the device.  Rays and pixels come back flat, [num_patches * P * P, ...], in patch-major, row, column
+    order, so `.view(num_patches, P, P, C)` is the channel-last patch batch.  Casting, `image_ids`, `differentiable` and
+    `intrinsics` are those of sample_random_rays_and_pixels_from_cameras."""
+    height, width, _ = camera_intrinsics
+    height, width, P, n = int(height), int(width), int(patch_size), int(num_patches)
+    if not 1 <= P <= min(height, width) or n < 1:
+        raise ValueError(f"patches of {P} pixels a side ({n} of them) do not fit a {height} x {width} image")
+    device = images.device
+    cameras = torch.randint(0, int(poses.shape[0]), (n,), device=device)
+    top = torch.randint(0, height - P + 1, (n,), device=device)
+    left = torch.randint(0, width - P + 1, (n,), device=device)
+    flat_index = patch_flat_indices(cameras, top, left, P, height, width)
+    return _cast_and_gather(camera_intrinsics, poses, images, flat_index, image_ids, differentiable, intrinsics)
 
 
 def sample_rays_and_pixels_synchronously(rays: Rays, pixels: Tensor, indices: Any, sample_size: int):

@@ -274,6 +274,10 @@ HIP_ONLY = {
     # lifting per-ray values into the grid (additive, still ABI v13)
     "lift_accumulate": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, C.c_int32, _P, _P, _P]),
     "lift_debug_merge": (C.c_int, [C.c_int32]),
+    # SSIM of channel-last images, value + gradient (additive, still ABI v13)
+    "ssim_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ssim_fwd_bwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int32,
+                               _P, C.c_size_t, _P]),
 }
 
 CPU_ONLY = {

@@ -1,4 +1,4 @@
-"""Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss on rays) and Adam
+"""Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss on rays, SSIM) and Adam
 on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
 import ctypes as C
 from typing import Optional, Tuple
@@ -180,3 +180,79 @@ def distortion_loss(spec: GridSpec, params: RenderParams, densities: torch.Tenso
     forward, only when it is needed); return_ray_loss=True: (loss, L_r [R], not differentiable)."""
     rng = resolve_rng(params, jitter, rng)
     return _DistortionFn.apply(densities, spec, params, rays_o, rays_d, jitter, rng, bool(return_ray_loss), int(_lanes))
+
+
+# ------------------------------------------------------------------------------------------------
+# SSIM of channel-last images (DESIGN.md section 4.18): no grid, no workspace; differentiable w.r.t. x
+# ------------------------------------------------------------------------------------------------
+SSIM_WINDOW = 11   # valid windows only: [N,H,W,C] gives an [N,H-10,W-10,C] map
+
+
+def _check_ssim_images(x: torch.Tensor, y: torch.Tensor) -> None:
+    for name, t in (("x", x), ("y", y)):
+        require_device(t, f"ssim ({name})")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise VoxeError(f"ssim: {name} must be a contiguous float32 tensor; got {t.dtype}, contiguous={t.is_contiguous()}")
+    if x.dim() != 4 or x.shape != y.shape or x.device != y.device:
+        raise VoxeError(f"ssim: x and y must be [N,H,W,C] of one shape on one device; got {tuple(x.shape)} and {tuple(y.shape)}")
+    N, H, W, Cn = x.shape
+    if N < 1 or H < SSIM_WINDOW or W < SSIM_WINDOW or not 1 <= Cn <= 4:
+        raise VoxeError(f"ssim: needs N >= 1, H and W >= {SSIM_WINDOW} and 1..4 channels (channel-last); got {tuple(x.shape)}")
+
+
+def ssim_fwd_bwd(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, grad_scale: float = 1.0, want_mean: bool = True,
+                 want_per_image: bool = True, want_map: bool = False, d_x: Optional[torch.Tensor] = None,
+                 accumulate: bool = False):
+    """voxe_ssim_fwd_bwd as it stands: (mean [] or None, per_image [N] or None, ssim_map [N,H-10,W-10,C] or None); `d_x`
+    (contiguous float32 of x's shape, or None) receives grad_scale * dssim/dx, added to its contents when `accumulate`."""
+    _check_ssim_images(x, y)
+    if not data_range > 0:
+        raise VoxeError(f"ssim: data_range must be positive; got {data_range}")
+    device = x.device
+    if d_x is not None:
+        _require_buffer("ssim", "d_x", d_x, shape=x.shape, device=device)
+    ensure_gfx950(device)
+    N, H, W, Cn = (int(v) for v in x.shape)
+    xd, yd = x.detach(), y.detach()
+    L = lib()
+    with torch.cuda.device(device):
+        mean = torch.empty((), dtype=torch.float32, device=device) if want_mean else None
+        per_image = torch.empty((N,), dtype=torch.float32, device=device) if want_per_image else None
+        ssim_map = (torch.empty((N, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1, Cn), dtype=torch.float32, device=device)
+                    if want_map else None)
+        need = L.voxe_ssim_scratch_bytes(N, H, W, Cn, 1 if d_x is not None else 0)
+        if need == 0:
+            raise VoxeError(f"ssim: {tuple(x.shape)} has more tiles than one launch holds")
+        sc = _scratch_for(device, need)
+        check(L.voxe_ssim_fwd_bwd(ptr(xd), ptr(yd), N, H, W, Cn, float(data_range), float(grad_scale), ptr(mean), ptr(per_image),
+                                  ptr(ssim_map), ptr(d_x), 1 if accumulate else 0, ptr(sc), sc.numel(), stream_ptr(device)),
+              "voxe_ssim_fwd_bwd")
+    wrote(d_x)
+    return mean, per_image, ssim_map
+
+
+class _SsimFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range):
+        d_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        mean, per_image, _ = ssim_fwd_bwd(x, y, data_range, d_x=d_x)
+        ctx.save_for_backward(d_x)
+        ctx.mark_non_differentiable(per_image)
+        return mean, per_image
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (d_x,) = ctx.saved_tensors
+        return (None if d_x is None else d_x * g), None, None
+
+
+def ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0):
+    """SSIM (Wang et al. 2004: 11 x 11 Gaussian window of sigma 1.5, valid windows only, C1 = (0.01 L)^2, C2 = (0.03 L)^2 with
+    L = data_range) of two channel-last batches [N,H,W,C], C in 1..4, float32 contiguous on the device -- a render's colour viewed
+    as patches or as an image.  Returns (mean [], per_image [N]): the mean of the (H-10) x (W-10) x C map over the batch and per
+    image.  `mean` is differentiable w.r.t. `x` (the gradient is computed in the forward, only when x requires one); `y` is a
+    target and receives no gradient, `per_image` is not differentiable."""
+    if y.requires_grad:
+        raise VoxeError("ssim: the target y receives no gradient; detach it")
+    _check_ssim_images(x, y)
+    return _SsimFn.apply(x, y, float(data_range))
