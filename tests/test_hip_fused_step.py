@@ -330,16 +330,51 @@ def test_density_correlation_inside_the_grid_step_equals_the_separate_pass():
         ops.grid_adam_step_(spec, d, f, 0, ws, 1, 1e-2, state_densities=None, state_features=st_f, dcl_reference=ref, dcl_weight=weight)
 
 
-@pytest.mark.parametrize("case", ["whole", "slab", "features_frozen", "extras"])
+# hand-made gradient regions for every texel width.  (8, 6, 6): 36 voxels per x plane, slab [2, 6) = voxels 72 .. 215 = two 64-voxel
+# chunks + a tail of 16.  (16, 5, 7): 35 voxels per x plane, 560 voxels = two 256-voxel chunks + a tail of 48 (the coalesced SH-0
+# kernel in both sweep directions over the three steps, then the per-voxel kernel); slab [4, 12) starts at voxel 140 (16-byte
+# aligned: one chunk + 24), slab [1, 9) at voxel 35 (unaligned: the per-voxel kernel alone).
+# name: channels, dims, x_range, layout, options
+STEP_CASES = {
+    "whole": (13, (8, 6, 6), None, "linear", ()),
+    "slab": (13, (8, 6, 6), (2, 6), "linear", ()),
+    "features_frozen": (13, (8, 6, 6), None, "linear", ("features_frozen",)),
+    "extras": (13, (8, 6, 6), None, "linear", ("extras",)),
+    "c13_bricked": (13, (8, 6, 6), None, "bricked", ()),
+    "c28_whole": (28, (8, 6, 6), None, "linear", ()),
+    "c28_slab": (28, (8, 6, 6), (2, 6), "linear", ()),
+    "c49_whole": (49, (8, 6, 6), None, "linear", ()),
+    "c49_slab": (49, (8, 6, 6), (2, 6), "linear", ()),
+    "c4_whole": (4, (16, 5, 7), None, "linear", ()),
+    "c4_slab_aligned": (4, (16, 5, 7), (4, 12), "linear", ()),
+    "c4_slab_unaligned": (4, (16, 5, 7), (1, 9), "linear", ()),
+    "c4_bricked": (4, (16, 5, 7), None, "bricked", ()),
+    "c4_bricked_slab": (4, (16, 5, 7), (4, 12), "bricked", ()),
+    "c4_extras": (4, (16, 5, 7), None, "linear", ("extras",)),
+    "c4_features_frozen": (4, (16, 5, 7), None, "linear", ("features_frozen",)),
+    "c4_densities_frozen": (4, (16, 5, 7), None, "linear", ("densities_frozen",)),
+    "c4_step_features": (4, (16, 5, 7), None, "linear", ("step_features",)),
+    "c13_step_features": (13, (8, 6, 6), None, "linear", ("step_features",)),
+    "c2_whole": (2, (16, 5, 7), None, "linear", ()),
+    "c2_slab_unaligned": (2, (16, 5, 7), (1, 9), "linear", ()),
+    "c2_bricked": (2, (16, 5, 7), None, "bricked", ()),
+}
+
+
+@pytest.mark.parametrize("case", list(STEP_CASES))
 def test_wide_texel_grid_step_chunks_tail_and_slabs(case):
-    """view-dependent grids take the fused grid step 64 voxels at a time with 16-byte accesses (r04); the tail, x-slabs that are
-    not 16-byte aligned and bricked buffers take the element kernel: a hand-made gradient region -> the same parameters, moments
-    and packed grid as voxe_adam_step per tensor on the decoded gradient, bit for bit"""
+    """every kernel of the fused grid step against voxe_adam_step: view-dependent grids take the step 64 voxels at a time with
+    16-byte accesses (r04), SH-0 grids 256 voxels per wave; the tails, x-slabs that are not 16-byte aligned, bricked buffers and
+    attention grids take the per-element / per-voxel kernels: a hand-made gradient region -> the same parameters, moments and
+    packed grid as voxe_adam_step per tensor on the decoded gradient, bit for bit"""
+    C, dims, x_range, layout_name, opts = STEP_CASES[case]
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(31)
-    dims, F = (8, 6, 6), 12                      # 36 voxels per x plane: slab [2, 6) = voxels 72 .. 215 = 2 chunks + a tail of 16
-    C = F + 1
-    spec = ops.GridSpec(aabb=((-1.5, 1.5),) * 3, density_scale=3.0, density_pre_act=abi.ACT_ABS, density_post_act=abi.ACT_SOFTPLUS)
+    F = C - 1
+    plane = dims[1] * dims[2]
+    layout = abi.GRAD_BRICKED if layout_name == "bricked" else abi.GRAD_LINEAR
+    spec = ops.GridSpec(aabb=((-1.5, 1.5),) * 3, density_scale=3.0, density_pre_act=abi.ACT_ABS, density_post_act=abi.ACT_SOFTPLUS,
+                        feature_kind=abi.FEAT_ATTN if F == 1 else abi.FEAT_SH)
     dens = torch.empty((*dims, 1)).uniform_(-1, 1, generator=gen).to(dev)
     feat = torch.empty((*dims, F)).uniform_(-1, 1, generator=gen).to(dev)
     ws = ops.Workspace()
@@ -348,32 +383,102 @@ def test_wide_texel_grid_step_chunks_tail_and_slabs(case):
     m = [torch.zeros_like(dens), torch.zeros_like(feat)]
     v = [torch.zeros_like(dens), torch.zeros_like(feat)]
     ref = [dens.clone(), feat.clone(), [t.clone() for t in m], [t.clone() for t in v]]
-    x_range = (2, 6) if case == "slab" else None
     x0, x1 = x_range if x_range else (0, dims[0])
+    frozen = {"densities_frozen": 0, "features_frozen": 1}
     for step in (1, 2, 3):
+        steps = (step, step + 2 if "step_features" in opts else step)     # torch.optim.Adam counts per parameter
         region = ops.workspace_grad_view(spec, dens, feat, ws)
-        g = torch.empty(dens.numel() * C).normal_(generator=gen).to(dev)
-        region[: g.numel()] = g
-        ex_d = torch.empty(dens.shape).normal_(generator=gen).to(dev) if case == "extras" else None
-        ex_f = torch.empty(feat.shape).normal_(generator=gen).to(dev) if case == "extras" else None
-        d_d, d_f = _region_to_gradients(region.clone(), abi.GRAD_LINEAR, ref[0], spec, C)
+        region.copy_(torch.empty(region.numel()).normal_(generator=gen))       # (the padding slots of a bricked buffer too)
+        before = region.clone()
+        ex_d = torch.empty(dens.shape).normal_(generator=gen).to(dev) if "extras" in opts else None
+        ex_f = torch.empty(feat.shape).normal_(generator=gen).to(dev) if "extras" in opts else None
+        d_d, d_f = _region_to_gradients(before.clone(), layout, ref[0], spec, C)
         if ex_d is not None:
             d_d, d_f = d_d + ex_d, d_f + ex_f
-        ops.grid_adam_step_(spec, dens, feat, abi.GRAD_LINEAR, ws, step, LR, (m[0], v[0]),
-                            None if case == "features_frozen" else (m[1], v[1]), ex_d, ex_f, x_range=x_range)
+        ops.grid_adam_step_(spec, dens, feat, layout, ws, steps[0], LR, None if "densities_frozen" in opts else (m[0], v[0]),
+                            None if "features_frozen" in opts else (m[1], v[1]), ex_d, ex_f, x_range=x_range,
+                            step_features=steps[1])
         sl = slice(x0, x1)
         for i, (p, grad) in enumerate(((ref[0], d_d), (ref[1], d_f))):
-            if i == 1 and case == "features_frozen":
+            if any(frozen.get(o) == i for o in opts):
                 continue
             ps, gs, ms, vs = (t[sl].contiguous() for t in (p, grad, ref[2][i], ref[3][i]))
-            ops.adam_step_(ps, gs, ms, vs, step, LR)
+            ops.adam_step_(ps, gs, ms, vs, steps[i], LR)
             p[sl], ref[2][i][sl], ref[3][i][sl] = ps, ms, vs
         for nm, a, b in (("densities", dens, ref[0]), ("features", feat, ref[1]), ("exp_avg d", m[0], ref[2][0]),
                          ("exp_avg f", m[1], ref[2][1]), ("exp_avg_sq d", v[0], ref[3][0]), ("exp_avg_sq f", v[1], ref[3][1])):
             assert torch.equal(a, b), (case, step, nm, float((a - b).abs().max()))
         packed = ops.workspace_packed_view(spec, dens, feat, ws).view(*dims, C)[sl]
         assert torch.equal(packed[..., :F], feat[sl]) and torch.equal(packed[..., F:], (dens[sl] * 3.0).abs())
-        assert float(ops.workspace_grad_view(spec, dens, feat, ws)[x0 * 36 * C: x1 * 36 * C].abs().max()) == 0.0
+        # the slab's gradient is cleared, every other slot of the region keeps its bits
+        after = ops.workspace_grad_view(spec, dens, feat, ws)
+        if layout == abi.GRAD_LINEAR:
+            assert float(after[x0 * plane * C: x1 * plane * C].abs().max()) == 0.0
+            assert torch.equal(after[: x0 * plane * C], before[: x0 * plane * C])
+            assert torch.equal(after[x1 * plane * C:], before[x1 * plane * C:])
+        else:
+            one = torch.ones_like(dens)      # (decoded against unit densities: the chain rule is then the constant scale)
+            got, was = (torch.cat(_region_to_gradients(r.clone(), layout, one, spec, C), -1) for r in (after, before))
+            assert float(got[sl].abs().max()) == 0.0
+            assert torch.equal(got[:x0], was[:x0]) and torch.equal(got[x1:], was[x1:])
+
+
+@pytest.mark.parametrize("kind", ["l2", "l1", "feature_correlation"])
+def test_in_step_regulariser_terms_equal_the_stand_alone_passes(kind):
+    """the l2_mode / l1_mode density terms and the feature-correlation term evaluated inside voxe_grid_adam_step == the stand-alone
+    entry point with grad_scale = weight into a gradient tensor + the same step with it as extra gradient, bit for bit, through
+    the coalesced SH-0 kernel (linear layout) and the per-voxel kernel (bricked): one copy of the per-element expressions serves
+    both.  8^3 voxels: 1 / n is exact in float, so the two host foldings of the weight (2 w / n in double; w x float(1 / n)) give
+    the same constant.  (The correlation kind folds its weight on the device: its own test, to a tolerance, is above.)"""
+    from voxe_hip.runtime import check, lib, ptr, stream_ptr
+
+    dev = torch.device("cuda:0")
+    gen = torch.Generator().manual_seed(47)
+    dims, F, C = (8, 8, 8), 3, 4
+    n = dims[0] * dims[1] * dims[2]
+    spec = ops.GridSpec(aabb=((-1.5, 1.5),) * 3, density_scale=3.0, density_pre_act=abi.ACT_ABS, density_post_act=abi.ACT_SOFTPLUS)
+    dens0 = torch.empty((*dims, 1)).uniform_(-1, 1, generator=gen).to(dev)
+    feat0 = torch.empty((*dims, F)).uniform_(-1, 1, generator=gen).to(dev)
+    dref = (dens0 * 0.8 + 0.1 * torch.empty(dens0.shape).normal_(generator=gen).to(dev)).contiguous()
+    dref.view(-1)[::7] = dens0.view(-1)[::7]                 # (a - b == 0: l1's sign(0) = 0)
+    fref = (feat0 + 0.3 * torch.empty(feat0.shape).normal_(generator=gen).to(dev)).contiguous()
+    weight = {"l2": 50.0, "l1": 5.0, "feature_correlation": 0.01}[kind]
+    L = lib()
+    for layout in (abi.GRAD_LINEAR, abi.GRAD_BRICKED):
+        grads = [torch.empty(n * C).normal_(generator=gen).to(dev) for _ in range(3)]
+        runs = []
+        for mode in ("in_step", "stand_alone"):
+            d, f = dens0.clone(), feat0.clone()
+            st_d, st_f = (torch.zeros_like(d), torch.zeros_like(d)), (torch.zeros_like(f), torch.zeros_like(f))
+            ws = ops.Workspace()
+            ws.ensure(4 * 2 * (d.numel() + f.numel()) * 2 + (1 << 16), dev)
+            ws.buf.zero_()
+            for step in (1, 2, 3):
+                ops.workspace_grad_view(spec, d, f, ws)[: n * C] = grads[step - 1]
+                kw = {}
+                if mode == "in_step" and kind == "feature_correlation":
+                    kw = dict(feat_reference=fref, feat_weight=weight)
+                elif mode == "in_step":
+                    kw = dict(dcl_reference=dref, dcl_weight=weight, density_kind=abi.DREG_L2 if kind == "l2" else abi.DREG_L1)
+                elif kind == "feature_correlation":
+                    extra = torch.empty_like(f)
+                    check(L.voxe_feature_correlation_fwd_bwd(ptr(f), ptr(fref), n, F, weight, None, ptr(extra), 0, None, 0,
+                                                             stream_ptr(dev)), "voxe_feature_correlation_fwd_bwd")
+                    kw = dict(extra_d_features=extra)
+                else:
+                    extra = torch.empty_like(d)
+                    check(L.voxe_density_diff_fwd_bwd(ptr(d), ptr(dref), n, abi.DREG_L2 if kind == "l2" else abi.DREG_L1, weight,
+                                                      None, ptr(extra), 0, None, 0, stream_ptr(dev)), "voxe_density_diff_fwd_bwd")
+                    kw = dict(extra_d_densities=extra)
+                    if kind == "l1" and step == 1:
+                        assert float(extra.view(-1)[::7].abs().max()) == 0.0 and float(extra.abs().max()) > 0.0
+                ops.grid_adam_step_(spec, d, f, layout, ws, step, LR, st_d, st_f, **kw)
+            runs.append((d, f, *st_d, *st_f, ops.workspace_packed_view(spec, d, f, ws).clone()))
+        for nm, a, b in zip(("densities", "features", "exp_avg d", "exp_avg_sq d", "exp_avg f", "exp_avg_sq f", "packed grid"), *runs):
+            assert torch.equal(a, b), (kind, layout, nm, float((a - b).abs().max()))
+        moved = runs[0][1] if kind == "feature_correlation" else runs[0][0]
+        plain = feat0 if kind == "feature_correlation" else dens0
+        assert not torch.equal(moved, plain)
 
 
 @pytest.mark.parametrize("case", ["sh0_tile", "sh0_scatter_bricked_odd", "sh0_preact_abs_relu", "attn_frozen_density", "sh1_linear"])

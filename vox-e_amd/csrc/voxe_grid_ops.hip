@@ -1,7 +1,6 @@
 // voxe_grid_ops.hip -- ray casting and the whole-grid (HBM-streaming) passes of an SDS /
 // reconstruction step: density-correlation loss, total-variation loss, Adam, trilinear upsampling.
-#include "voxe_device.hpp"
-#include "voxe_launch.hpp"
+#include "voxe_grid_elem.hpp"
 
 namespace voxe {
 
@@ -258,8 +257,7 @@ __global__ __launch_bounds__(256) void dcl_grad_kernel(const float* __restrict__
   const float k1 = (float)(stats[2] * (double)grad_scale), k2 = (float)(stats[3] * (double)grad_scale);
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float A = a[i] - ma, B = b[i] - mb;
-    const float gv = A * k2 - B * k1;
+    const float gv = dcl_grad(a[i], b[i], ma, mb, k1, k2);
     d_a[i] = accumulate ? d_a[i] + gv : gv;
   }
 }
@@ -295,8 +293,6 @@ void launch_dcl(const float* a, const float* b, long long n, float grad_scale, f
 // _feature_correlation_loss -- modules/sds_trainer.py:526-534 (+ autograd): per voxel D = sum_c (sigmoid(f_c) - sigmoid(r_c)),
 // loss = sum_v D^2, d f_c = 2 w D sigmoid(f_c) (1 - sigmoid(f_c)).  Values: per-block double partials, fixed-order final sum.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }   // (torch.sigmoid; not the render's fast path)
-
 __global__ __launch_bounds__(256) void density_diff_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n,
                                                            int kind, float k, double* __restrict__ partial,
                                                            float* __restrict__ d_a, int accumulate) {
@@ -306,7 +302,7 @@ __global__ __launch_bounds__(256) void density_diff_kernel(const float* __restri
     const float d = a[i] - b[i];
     if (partial) s[0] += kind == VOXE_DREG_L2 ? (double)d * (double)d : (double)fabsf(d);
     if (d_a) {
-      const float gv = kind == VOXE_DREG_L2 ? d * k : (d > 0.0f ? k : (d < 0.0f ? -k : 0.0f));
+      const float gv = density_diff_grad(kind, d, k);
       d_a[i] = accumulate ? d_a[i] + gv : gv;
     }
   }
@@ -341,12 +337,11 @@ __global__ __launch_bounds__(256) void feature_correlation_kernel(const float* _
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += stride) {
     float D = 0.0f;
-    for (int c = 0; c < F; ++c) D += sigmoid_ref(f[v * F + c]) - sigmoid_ref(r[v * F + c]);
+    for (int c = 0; c < F; ++c) D += featcorr_diff(f[v * F + c], r[v * F + c]);
     if (partial) s[0] += (double)D * (double)D;
     if (d_f) {
       for (int c = 0; c < F; ++c) {
-        const float sc = sigmoid_ref(f[v * F + c]);
-        const float gv = (k2 * D) * ((1.0f - sc) * sc);
+        const float gv = featcorr_grad(k2, D, sigmoid_ref(f[v * F + c]));
         d_f[v * F + c] = accumulate ? d_f[v * F + c] + gv : gv;
       }
     }
@@ -513,16 +508,11 @@ void launch_tv(const float* grid, int X, int Y, int Z, int C, float grad_scale, 
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
-                                                   long long n, float step_size, float bc2_sqrt,
-                                                   float beta1, float beta2, float eps) {
+                                                   long long n, AdamHyper h) {
   const long long stride = (long long)gridDim.x * blockDim.x;
-  const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gi = g[i];
-    const float mi = m[i] + (gi - m[i]) * omb1;              // exp_avg.lerp_(grad, 1-beta1)
-    const float vi = v[i] * beta2 + (omb2 * gi) * gi;        // mul_(beta2).addcmul_(g, g, 1-beta2)
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);                  // addcdiv_(exp_avg, denom, -step_size)
+    float mi = m[i], vi = v[i];
+    p[i] = adam_update(p[i], g[i], mi, vi, h);
     m[i] = mi;
     v[i] = vi;
   }
@@ -530,13 +520,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 
 void launch_adam(float* param, const float* grad, float* m, float* v, long long n, float lr,
                  float beta1, float beta2, float eps, long long step, hipStream_t st) {
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
   if (n == 0) return;
   const int nb = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  adam_kernel<<<nb, 256, 0, st>>>(param, grad, m, v, n, step_size, bc2_sqrt, beta1, beta2, eps);
+  adam_kernel<<<nb, 256, 0, st>>>(param, grad, m, v, n, adam_hyper(lr, beta1, beta2, eps, step));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -67,7 +67,7 @@ struct ProbeArgs {
 };
 
 
-// voxe_render.hip
+// voxe_grid_step.hip: pack, un-pack of the gradient, the fused grid step (element arithmetic: voxe_grid_elem.hpp)
 void launch_pack_any(const VoxeGridDesc* gd, float* packed, hipStream_t st);
 void launch_unpack_any(const VoxeGridDesc* gd, const float* gpacked, float* d_dens, float* d_feat,
                        int accumulate, int bricked, hipStream_t st);
@@ -91,7 +91,9 @@ bool launch_grid_adam(const VoxeGridDesc* gd, bool bricked, int x_begin, int x_e
 // moments + finalize of the density-correlation loss (no gradient kernel): stats = (mean a, mean b, k1 * scale, k2 * scale)
 // in `scratch` (returned pointer), loss value to loss_out (nullable)
 const double* launch_dcl_moments(const float* a, const float* b, long long n, float grad_scale, float* loss_out, void* scratch,
-                                 hipStream_t st);
+                                 hipStream_t st);   // (voxe_grid_ops.hip)
+
+// voxe_render.hip
 void launch_fwd(const DevGrid& g, const HostCfg& c, int deg, int diffuse, const FwdArgs& a,
                 hipStream_t st);
 void launch_bwd(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const BwdArgs& a,
