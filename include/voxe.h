@@ -296,7 +296,9 @@ int voxe_render_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
  *   points [N,3] world coordinates  ->  out [N,F+1] = (trilinear features f_0..f_{F-1}, post(trilinear pre(d*scale)))
  *   NOT masked by the AABB (the reference masks later, process.py:80-84): zero padding outside the grid.
  *   Backward: d_out [N,F+1] -> d_densities / d_features (either may be NULL), accumulate as above.
- *   workspace: >= voxe_workspace_bytes(grid, NULL, 0); cfg-less, so packed-grid reuse is an explicit flag.
+ *   workspace: >= voxe_workspace_bytes(grid, NULL, 0) (packed grid + gradient region; the forward alone reads and writes only
+ *   the packed grid, the first voxe_workspace_grad_offset(grid) bytes, and is refused only below that); cfg-less, so packed-grid
+ *   reuse is an explicit flag.
  * ---------------------------------------------------------------------------------------------- */
 int voxe_query_fwd(const VoxeGridDesc* grid, const float* points, int64_t N, float* out,
                    int32_t reuse_packed_grid, void* workspace, size_t workspace_bytes, void* stream);
@@ -467,7 +469,8 @@ int voxe_disparity_bwd(const float* depth, const float* acc, const float* d_disp
  *             (trainers.py:316,333); each runs in its own workspace (per-ray states), both gradients sum into the FIRST
  *             workspace's gradient region (voxe_render_bwd_acc_into);
  *   loss    : mean |colour - target| per render (torch.nn.functional.l1_loss), summed; losses[0..3] (DEVICE floats) receive
- *             L1 specular, MSE specular (the trainer logs it as PSNR), L1 diffuse, MSE diffuse;
+ *             L1 specular, MSE specular (the trainer logs it as PSNR), L1 diffuse, MSE diffuse (the diffuse pair is written
+ *             only when diffuse_regularisation != 0: without that render losses[2..3] keep what they held);
  *   update  : voxe_grid_adam_step over the whole grid with the given Adam state / hyper-parameters; afterwards
  *             `workspace` holds the updated grid packed (pass cfg->reuse_packed_grid = 1 next time) and a cleared gradient.
  *   scratch : voxe_recon_scratch_bytes(batch) bytes of device memory (rays, targets, outputs, upstream gradients).

@@ -701,6 +701,11 @@ int render_bwd(const RenderPlan& p, const RenderCall& c, const float* colour, co
   const WsLayout& l = p.l;
   if (!workspace || c.workspace_bytes < l.total) return VOXE_ERR_WORKSPACE;
   if (grad_workspace && grad_workspace_bytes < l.state_off) return VOXE_ERR_WORKSPACE;   // (packed grid + gradient region)
+  // (every refusal comes before the first launch: a refused call leaves the workspace as it found it)
+  if (p.det && c.R > 0) {
+    if (!det_bwd_supported(p.dc, cfg->sh_degree, cfg->render_diffuse)) return VOXE_ERR_UNSUPPORTED;
+    if (!p.tier(c.workspace_bytes).with_src) return VOXE_ERR_WORKSPACE;
+  }
   if (c.drop_hint) g_hints.workspace_written(workspace, s);
   float* packed = at<float>(workspace, l.packed_off);
   float* gpacked = at<float>(grad_workspace ? grad_workspace : workspace, l.grad_off);
@@ -726,9 +731,7 @@ int render_bwd(const RenderPlan& p, const RenderCall& c, const float* colour, co
     if (p.nseg > 1) a.sample_fwd = at<const float>(workspace, l.fwdval_off);   // (only the depth-segmented forward writes them)
     a.grad_planar = at<float>(workspace, l.planar_off);
   }
-  if (p.det) {
-    if (!det_bwd_supported(dc, cfg->sh_degree, cfg->render_diffuse)) return VOXE_ERR_UNSUPPORTED;
-    if (!tier.with_src) return VOXE_ERR_WORKSPACE;
+  if (p.det) {   // (supported and sized: checked above)
     a.gdet = at<unsigned long long>(workspace, l.det_off);
     a.det_scale = at<float>(workspace, l.det_scale_off);
     a.ray_state = state;
@@ -1006,19 +1009,25 @@ int voxe_recon_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const Vo
     }
   }
   const ReconBatchPtrs bp = recon_batch_ptrs(l, scratch, 0);
-  assemble_recon_batch(cfg, rs, bp, s);
   VoxeRenderCfg rc[2] = {*cfg, *cfg};
   RenderPlan plan[2]; RenderCall call[2];
+  // plan both renders and check what their forward and backward will ask of the workspaces BEFORE the first launch: a refused
+  // step leaves the scratch, the losses and both workspaces as it found them
   for (int i = 0; i < nrender; ++i) {
     rc[i].rng_offset = cfg->rng_offset + 1 + (uint64_t)i;
     rc[i].ray_state_valid = 0;
     rc[i].render_diffuse = i == 1 ? 1 : cfg->render_diffuse;
     rc[i].linear_grad = 1;                         // both renders write ONE gradient layout, whatever kernel runs
     if (i == 1) rc[i].reuse_packed_grid = 0;       // the second workspace still holds the previous iteration's grid
-    float* colour = at<float>(scratch, l.out[i]);
-    float *depth = colour + 3 * B, *acc = depth + B;
     st = plan_render(grid, &rc[i], B, nullptr, nullptr, &plan[i]);
     if (st) return st;
+    void* const ws = i == 0 ? workspace : workspace2;
+    if (!ws || (i == 0 ? workspace_bytes : workspace2_bytes) < plan[i].l.total) return VOXE_ERR_WORKSPACE;
+  }
+  assemble_recon_batch(cfg, rs, bp, s);
+  for (int i = 0; i < nrender; ++i) {
+    float* colour = at<float>(scratch, l.out[i]);
+    float *depth = colour + 3 * B, *acc = depth + B;
     call[i] = RenderCall{grid, &rc[i], bp.rays_o, bp.rays_d, B, nullptr, i == 0 ? workspace : workspace2, i == 0 ? workspace_bytes : workspace2_bytes, s};
     st = render_fwd(plan[i], call[i], FwdOutputs{colour, depth, acc, nullptr});
     if (st) return st;
@@ -1091,6 +1100,8 @@ int voxe_attn_refine_step(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, co
   RenderPlan plan;
   int st = plan_render(grid, &rc, R, nullptr, nullptr, &plan);
   if (st) return st;
+  // (the backward's need, checked before the forward runs: a refused step has written nothing)
+  if (!workspace || workspace_bytes < plan.l.total) return VOXE_ERR_WORKSPACE;
   const RenderCall call{grid, &rc, rays_o, rays_d, R, nullptr, workspace, workspace_bytes, s, nullptr, false, /*drop_hint=*/true};
   st = render_fwd(plan, call, FwdOutputs{attn, depth, acc, nullptr});
   if (st) return st;
