@@ -789,6 +789,46 @@ int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
 int voxe_distortion_debug_lanes(int32_t lanes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth supervision: ray-termination loss towards per-ray depth targets (additive; still ABI v13), DESIGN.md section 4.19.
+ * DS-NeRF's term (Deng et al., CVPR 2022) as its published code evaluates it; no voxe_cpu_ twin, the float64 restatement is
+ * tests/depth_ref.py.
+ *   The samples z_k, the inside test, sigma_k, delta_k = dl_k |d| (last dl = 1e10) and T_k are those of
+ *   voxe_distortion_fwd_bwd for the same rays, cfg and jitter / (seed, rng_offset), and so are the cfg fields honoured and
+ *   ignored.  The weights w_k = T_k alpha_k are those of the same call in exact arithmetic; this call forms its alpha_k as
+ *   -expm1(-sigma_k delta_k) (w sits at or below eps in a nearly empty field, where 1 - exp cancels), the transmittance
+ *   product keeps the renderer's 1 - alpha.  With a target depth D_r and a width s_r > 0 per ray, both in the units of z_k:
+ *       dz_k = z_{k+1} - z_k for k < S-1, dz_{S-1} = 0
+ *       c_k  = exp(-(z_k - D_r)^2 / (2 s_r^2)) dz_k
+ *       L_r  = -sum_k c_k log(w_k + eps)
+ *       loss = (1/R) sum_r omega_r L_r                      (omega = ray_weight, 1 when NULL)
+ *   over ALL S samples: one that fails the AABB test, or lies behind the point where T reaches 0, has w = 0 and contributes
+ *   -c_k log(eps) to the value and nothing to the gradient.  eps must be finite and > 0 (VOXE_ERR_BAD_SHAPE otherwise);
+ *   DS-NeRF's is 1e-5.  Gradient w.r.t. the raw densities [X,Y,Z,1]:
+ *       g_k = dL_r/dw_k = -c_k / (w_k + eps)
+ *       dL_r/dsigma_k = delta_k [g_k (T_k - w_k) - sum_{i>k} g_i w_i]
+ *   and from there through post_activate', the gather weights and pre_activate' * density_scale into the 8 footprint
+ *   corners as in voxe_distortion_fwd_bwd, scaled by grad_scale * omega_r / R.  No gradient flows to z, D, s or omega.
+ *   target_depth / target_sigma NULL with R > 0: VOXE_ERR_NULL_POINTER.  The caller guarantees finite D, finite s > 0 and
+ *   finite omega >= 0; the three arrays are read for [R] only.
+ *   Outputs (each may be NULL): loss_out  device float[1], the weighted mean above (grad_scale does not apply to it);
+ *                               ray_loss  device [R], L_r (without omega_r);
+ *                               d_densities [X,Y,Z,1], accumulate as in voxe_distortion_fwd_bwd.
+ *   loss_out and ray_loss are the same bits from run to run (fixed-order sums); the gradient goes through float atomics.
+ *   scratch (voxe_depth_scratch_bytes(R), read only when loss_out != NULL), R == 0, all outputs NULL, validation, limits, error
+ *   codes, stream and the "no workspace, no forward record, no voxe_recon_prefetch hint is touched" clause: as
+ *   voxe_distortion_fwd_bwd.  voxe_depth_debug_lanes: test aid, as voxe_distortion_debug_lanes.                                */
+size_t voxe_depth_scratch_bytes(int64_t R);
+int voxe_depth_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                       const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                       const float* target_depth  /* [R] D_r, in the units of the renderer's z_k */,
+                       const float* target_sigma  /* [R] s_r > 0, same units */,
+                       const float* ray_weight    /* [R] or NULL (= 1) */,
+                       float eps, float grad_scale,
+                       float* loss_out, float* ray_loss, float* d_densities, int32_t accumulate,
+                       void* scratch, size_t scratch_bytes, void* stream);
+int voxe_depth_debug_lanes(int32_t lanes);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM of two image batches, value and gradient in one call (additive; still ABI v13), DESIGN.md section 4.18 "SSIM".  No
  * voxe_cpu_ twin; the float64 restatement is tests/ssim_ref.py.
  *   x, y: device float, channel-last [N,H,W,C], C in 1..4 (a render's colour viewed as patches or as an image).  Wang et al.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """COLMAP text model (cameras.txt, images.txt, optionally points3D.txt) -> `<split>_camera_params.json` of this project,
-with the camera's fx, fy, cx, cy and OpenCV distortion coefficients.
+with the camera's fx, fy, cx, cy and OpenCV distortion coefficients and, when points3D.txt is there,
+`<split>_sparse_points.npz` next to it: the sparse point cloud as per-image depth measurements.
 
     python tools/convert_from_colmap_text.py -m sparse/0 -o scene [--split train] [--recentre] [--near 0.5 --far 6]
 
@@ -9,7 +10,12 @@ shared camera per dataset).  COLMAP stores world-to-camera (qvec, tvec) with Ope
 this project wants camera-to-world with x right, y up, looking down -z:  R_c2w = R_w2c^T diag(1, -1, -1),  t = -R_w2c^T tvec.
 COLMAP's pixel coordinates put the centre of the top-left pixel at (0.5, 0.5), as this project does, so cx, cy pass unchanged.
 Bounds: the 1st / 99th percentile of the depths of the image's own 3D points when points3D.txt is there, else --near / --far.
---recentre moves the least-squares meeting point of the optical axes to the origin.  Standard library + numpy only."""
+--recentre moves the least-squares meeting point of the optical axes to the origin.
+The sparse-point file (--no_sparse_points suppresses it) holds, for the images in the JSON's order: `names` [K], `offsets` [K+1]
+(the observations of image i are rows offsets[i] .. offsets[i+1]), `xy` [M,2] float32 (COLMAP pixel coordinates of the
+keypoint), `xyz` [M,3] float32 (the world point, after the --recentre shift) and `error` [M] float32 (the point's mean
+reprojection error in pixels).  Observations of points behind the camera or outside the image are dropped.
+Standard library + numpy only."""
 import argparse
 import os
 import sys
@@ -65,8 +71,8 @@ def quaternion_to_matrix(q):
 
 
 def read_images(path, camera_id):
-    """-> [(name, R_c2w, centre, [point3D ids])], sorted by name.  images.txt: two lines per image, the second (possibly empty)
-    holding its 2D points"""
+    """-> [(name, R_c2w, centre, [point3D ids], [(x, y, point3D id)])], sorted by name.  images.txt: two lines per image, the
+    second (possibly empty) holding its 2D points; those without a 3D point (id -1) are left out"""
     raw = [line.rstrip("\n") for line in Path(path).read_text().splitlines() if not line.lstrip().startswith("#")]
     while raw and not raw[-1].strip():
         raw.pop()
@@ -86,12 +92,43 @@ def read_images(path, camera_id):
         R = R_w2c.T @ np.diag([1.0, -1.0, -1.0])
         centre = -R_w2c.T @ tvec
         ids = [int(v) for v in points[2::3] if int(v) >= 0]
-        out.append((" ".join(head[9:]), R, centre, ids))
+        obs = [(float(x), float(y), int(v)) for x, y, v in zip(points[0::3], points[1::3], points[2::3]) if int(v) >= 0]
+        out.append((" ".join(head[9:]), R, centre, ids, obs))
     return sorted(out, key=lambda t: t[0])
 
 
 def read_points(path):
     return {int(p[0]): np.array([float(v) for v in p[1:4]]) for p in (line.split() for line in _lines(path))}
+
+
+def read_point_errors(path):
+    """point3D id -> mean reprojection error in pixels (POINT3D_ID X Y Z R G B ERROR TRACK[])"""
+    return {int(p[0]): float(p[7]) for p in (line.split() for line in _lines(path))}
+
+
+def sparse_points(model_dir, recentre=False):
+    """the arrays of `<split>_sparse_points.npz` (see the module's text), or None without points3D.txt"""
+    model_dir = Path(model_dir)
+    if not (model_dir / "points3D.txt").exists():
+        return None
+    cam_id, width, height = read_camera(model_dir / "cameras.txt")[:3]
+    images = read_images(model_dir / "images.txt", cam_id)
+    points, errors = read_points(model_dir / "points3D.txt"), read_point_errors(model_dir / "points3D.txt")
+    shift = CI.optical_axes_meeting_point([im[1] for im in images], [im[2] for im in images]) if recentre else np.zeros(3)
+    names, offsets, xy, xyz, error = [], [0], [], [], []
+    for name, R, centre, _, obs in images:
+        for x, y, pid in obs:
+            if pid not in points or not (0.0 <= x < width and 0.0 <= y < height):
+                continue
+            if (points[pid] - centre) @ -R[:, 2] <= 0.0:      # behind the camera
+                continue
+            xy.append((x, y))
+            xyz.append(points[pid] - shift)
+            error.append(errors[pid])
+        names.append(name)
+        offsets.append(len(xy))
+    return dict(names=np.array(names), offsets=np.array(offsets, np.int64), xy=np.array(xy, np.float32).reshape(-1, 2),
+                xyz=np.array(xyz, np.float32).reshape(-1, 3), error=np.array(error, np.float32))
 
 
 def convert(model_dir, near=None, far=None, recentre=False):
@@ -105,7 +142,7 @@ def convert(model_dir, near=None, far=None, recentre=False):
         raise ValueError("no points3D.txt: give --near and --far")
     shift = CI.optical_axes_meeting_point([im[1] for im in images], [im[2] for im in images]) if recentre else np.zeros(3)
     entries = {}
-    for name, R, centre, ids in images:
+    for name, R, centre, ids, _ in images:
         if points is not None:
             seen = np.array([points[i] for i in ids if i in points] or list(points.values()))
             lo, hi = CI.depth_bounds(R, centre, seen)
@@ -123,14 +160,20 @@ def main(argv=None) -> int:
     ap.add_argument("--near", type=float, default=None)
     ap.add_argument("--far", type=float, default=None)
     ap.add_argument("--recentre", action="store_true")
+    ap.add_argument("--no_sparse_points", action="store_true", help="do not write <split>_sparse_points.npz")
     args = ap.parse_args(argv)
     try:
         entries = convert(args.model_path, args.near, args.far, args.recentre)
+        sparse = None if args.no_sparse_points else sparse_points(args.model_path, args.recentre)
     except UnsupportedModel as e:
         print(f"convert_from_colmap_text: unsupported: {e}", file=sys.stderr)
         return 2
     path = CI.write_params(args.output_path, args.split, entries)
     print(f"{len(entries)} cameras -> {path}")
+    if sparse is not None:
+        side = path.with_name(f"{args.split}_sparse_points.npz")
+        np.savez(side, **sparse)
+        print(f"{len(sparse['xy'])} observations of sparse points -> {side}")
     return 0
 
 

@@ -83,6 +83,13 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
               help="weight of a D-SSIM term, weight * (1 - SSIM), on random pixel patches instead of a random pixel set; 0 = off")
 @click.option("--ssim_patch_size", type=click.IntRange(min=11), default=32, show_default=True,
               help="side of the SSIM term's pixel patches (a stage with smaller images uses its smaller side)")
+@click.option("--depth_weight", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
+              help="weight of the depth supervision from the sparse points the COLMAP importer wrote (<split>_sparse_points.npz); "
+                   "0 = off")
+@click.option("--depth_ray_batch_size", type=click.IntRange(min=1), default=4096, show_default=True,
+              help="keypoint rays of the depth term per iteration")
+@click.option("--depth_sigma_scale", type=click.FloatRange(min=0.0, min_open=True), default=1.0, show_default=True,
+              help="multiplies the width of each depth measurement (its reprojection error at its depth)")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -121,7 +128,8 @@ def main(**kwargs) -> None:
         summary_freq=cfg.summary_frequency, verbose_rendering=cfg.verbose_rendering, lpips_weight=cfg.lpips_weight,
         num_workers=cfg.num_workers, distortion_weight=cfg.distortion_weight, pose_learning_rate=cfg.pose_learning_rate,
         intrinsics_learning_rate=cfg.intrinsics_learning_rate, background_resolution=cfg.background_resolution,
-        background_learning_rate=cfg.background_learning_rate, ssim_weight=cfg.ssim_weight, ssim_patch_size=cfg.ssim_patch_size)
+        background_learning_rate=cfg.background_learning_rate, ssim_weight=cfg.ssim_weight, ssim_patch_size=cfg.ssim_patch_size,
+        depth_weight=cfg.depth_weight, depth_ray_batch_size=cfg.depth_ray_batch_size, depth_sigma_scale=cfg.depth_sigma_scale)
 
 
 if __name__ == "__main__":

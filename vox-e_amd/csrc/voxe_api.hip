@@ -4,6 +4,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
+
 #include <mutex>
 #include <unordered_map>
 
@@ -1579,6 +1581,35 @@ int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, 
 int voxe_distortion_debug_lanes(int32_t lanes) {
   if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
   tl_distortion_lanes = lanes;
+  return VOXE_OK;
+}
+
+// ---- ray-termination loss towards depth targets --------------------------------------------------------
+size_t voxe_depth_scratch_bytes(int64_t R) { return depth_scratch_bytes(R); }
+
+int voxe_depth_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
+                       const float* jitter, const float* target_depth, const float* target_sigma, const float* ray_weight, float eps,
+                       float grad_scale, float* loss_out, float* ray_loss, float* d_densities, int32_t accumulate, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+  DevGrid dg;
+  DevCfg dc;
+  const int st = sampling_call(grid, cfg, R, rays_o, rays_d, &dg, &dc);
+  if (st) return st;
+  if (!(eps > 0.0f) || !std::isfinite(eps)) return VOXE_ERR_BAD_SHAPE;
+  if (R > 0 && (!target_depth || !target_sigma)) return VOXE_ERR_NULL_POINTER;
+  if (R > 0 && loss_out && (!scratch || scratch_bytes < depth_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
+  const bool clear = d_densities && !accumulate;
+  if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
+    return VOXE_ERR_LAUNCH;
+  if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
+  launch_depth(dg, dc, grid->densities, rays_o, rays_d, jitter, target_depth, target_sigma, ray_weight, eps, grad_scale, loss_out,
+               ray_loss, d_densities, scratch, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_depth_debug_lanes(int32_t lanes) {
+  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
+  tl_depth_lanes = lanes;
   return VOXE_OK;
 }
 

@@ -33,31 +33,6 @@ namespace {
 
 constexpr int kDistThreads = kMarchThreads;
 
-// inclusive scan over the G lanes of a ray (sum)
-template <int G>
-__device__ __forceinline__ double group_scan(double v, int j) {
-#pragma unroll
-  for (int off = 1; off < G; off <<= 1) {
-    const double t = __shfl_up(v, off, G);
-    if (j >= off) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ double block_sum(double v) {
-  __shared__ double sm[kDistThreads / 64];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < kDistThreads / 64; ++i) s += sm[i];
-  }
-  return s;   // (thread 0 only)
-}
-
 template <int G, bool GRAD>
 __global__ __launch_bounds__(kDistThreads) void distortion_kernel(DevGrid g, DevCfg c, const float* __restrict__ dens,
                                                                   const float* __restrict__ rays_o,
@@ -172,10 +147,14 @@ void launch_distortion_t(const DevGrid& g, const DevCfg& c, const float* dens, c
   else
     distortion_kernel<G, false><<<(unsigned)nb, kDistThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, gscale, ray_loss,
                                                                        partial, d_dens);
-  if (loss_out) distortion_finalize_kernel<<<1, kDistThreads, 0, st>>>(partial, nb, 1.0 / (double)c.R, loss_out);
+  if (loss_out) launch_partial_mean(partial, nb, c.R, loss_out, st);
 }
 
 }  // namespace
+
+void launch_partial_mean(const double* partial, long long nb, long long R, float* loss_out, hipStream_t st) {
+  distortion_finalize_kernel<<<1, kDistThreads, 0, st>>>(partial, nb, 1.0 / (double)R, loss_out);
+}
 
 thread_local int tl_distortion_lanes = 0;
 

@@ -1,8 +1,8 @@
 // voxe_ray_march.hpp -- the density-only sample march ("The shared sample march").
 //
-// Five calls walk the forward's exact samples over the RAW densities without rendering colour: voxe_render_normals,
-// voxe_visibility_accumulate, voxe_distortion_fwd_bwd, voxe_render_bwd_rays and voxe_lift_accumulate.  What ties them to the
-// renderer lives here, once:
+// Six calls walk the forward's exact samples over the RAW densities without rendering colour: voxe_render_normals,
+// voxe_visibility_accumulate, voxe_distortion_fwd_bwd, voxe_render_bwd_rays, voxe_lift_accumulate and voxe_depth_fwd_bwd.  What
+// ties them to the renderer lives here, once:
 //   depth step : sample k sits at z_k = DepthGen::z(k); its interval is dl_k = z_{k+1} - z_k, kInfinity for the last sample
 //   cell       : p = o + d z, footprint(); a sample outside the box has sigma = 0 -> w = 0, T unchanged (the forward's rule)
 //   density    : 8 raw loads, v = sum_q pre(raw_q) t_q with t_q = (wx * wy) * wz and the corners ascending (gather()'s
@@ -99,6 +99,32 @@ __device__ __forceinline__ float group_exclusive_product(float T, int j) {
   return j == 0 ? 1.0f : Ts;
 }
 
+// inclusive scan over the G lanes of a ray (sum; distortion, depth)
+template <int G>
+__device__ __forceinline__ double group_scan(double v, int j) {
+#pragma unroll
+  for (int off = 1; off < G; off <<= 1) {
+    const double t = __shfl_up(v, off, G);
+    if (j >= off) v += t;
+  }
+  return v;
+}
+
+// sum over the block, fixed order (thread 0 only holds it)
+__device__ __forceinline__ double block_sum(double v) {
+  __shared__ double sm[kMarchThreads / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < kMarchThreads / 64; ++i) s += sm[i];
+  }
+  return s;   // (thread 0 only)
+}
+
 // ---- one sample ------------------------------------------------------------------------------------------------------------
 // The depth step: z of the current sample, z_next of the one behind it, `last`, and the interval dl.
 struct DepthStep {
@@ -185,8 +211,8 @@ __device__ __forceinline__ void eval_density(const DevGrid& g, const Cell& cell,
 // ---- the march ---------------------------------------------------------------------------------------------------------------
 // Samples k_lo .. k_hi of a ray front to back with the running transmittance T.  body(step, footprint, cell, T) handles one
 // sample inside the box and returns its 1 - alpha.
-// (Visibility and both distortion marches.  Normals, the ray gradients and lifting write their loops out over the same pieces;
-// each says why.)
+// (Visibility, both distortion marches and the three of the depth loss.  Normals, the ray gradients and lifting write their
+// loops out over the same pieces; each says why.)
 template <class RC, class Body>
 __device__ __forceinline__ void march_block(const DevGrid& g, const DevCfg& c, RC& rc, int k_lo, int k_hi, float& T, Body&& body) {
   if (k_lo > k_hi) return;

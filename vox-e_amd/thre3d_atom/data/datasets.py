@@ -4,11 +4,12 @@
 `<split>_camera_params.json`, reference thre3d_atom/data/datasets.py:32-390 and tools/
 convert_from_nerf_blender_dataset.py); `InMemoryPosedImages` wraps tensors (synthetic scenes, tests).
 Both expose what the trainers use: `camera_intrinsics`, `camera_bounds`,
-`get_hemispherical_radius_estimate()`, `images [N,C,H,W]`, `poses [N,3,4]`, `downsampled(factor)`.
+`get_hemispherical_radius_estimate()`, `images [N,C,H,W]`, `poses [N,3,4]`, `downsampled(factor)`, and `sparse_points`
+(the structure-from-motion points seen by each image, or None: depth supervision).
 Image decoding is host I/O, outside the render hot path."""
 import json
 from pathlib import Path
-from typing import Any, Dict, Tuple
+from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -61,13 +62,57 @@ def camera_to_params(camera: CameraIntrinsics) -> Dict[str, Any]:
     return out
 
 
+SPARSE_POINTS_SUFFIX = "_sparse_points.npz"     # next to `<split>_camera_params.json` (tools/convert_from_colmap_text.py)
+
+
+class SparsePoints(NamedTuple):
+    """The sparse structure-from-motion points as depth measurements: the observations of image i (the dataset's order) are
+    rows offsets[i] .. offsets[i+1] of `xy` [M,2] (pixel coordinates of the keypoint in the dataset's images, the centre of the
+    top-left pixel at (0.5, 0.5)), `xyz` [M,3] (the world point) and `error` [M] (its mean reprojection error in pixels)."""
+    offsets: Tensor
+    xy: Tensor
+    xyz: Tensor
+    error: Tensor
+
+    def scaled(self, factor: float) -> "SparsePoints":
+        """for images downsampled by `factor`: pixel coordinates and pixel errors divided by it"""
+        return SparsePoints(self.offsets, self.xy / factor, self.xyz, self.error / factor)
+
+    def to(self, device) -> "SparsePoints":
+        return SparsePoints(*(t.to(device) for t in self))
+
+
+def sparse_points_path(camera_params_json: Path) -> Path:
+    """`<split>_sparse_points.npz` of `<split>_camera_params.json` (any other name: `<stem>_sparse_points.npz`)"""
+    path = Path(camera_params_json)
+    stem = path.name[:-len("_camera_params.json")] if path.name.endswith("_camera_params.json") else path.stem
+    return path.with_name(stem + SPARSE_POINTS_SUFFIX)
+
+
+def load_sparse_points(path: Path, names, scale: float = 1.0) -> SparsePoints:
+    """the sidecar's observations regrouped to the images `names` (matched by file name; an image the file does not list has
+    none), world points multiplied by `scale`"""
+    with np.load(path) as f:
+        listed = {str(n): i for i, n in enumerate(f["names"].tolist())}
+        off, xy, xyz, error = f["offsets"].astype(np.int64), f["xy"], f["xyz"], f["error"]
+    rows = [np.arange(off[listed[n]], off[listed[n] + 1]) if n in listed else np.zeros(0, np.int64) for n in names]
+    take = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    return SparsePoints(torch.from_numpy(offsets), torch.from_numpy(xy[take].astype(np.float32)).reshape(-1, 2),
+                        torch.from_numpy(xyz[take].astype(np.float32) * np.float32(scale)).reshape(-1, 3),
+                        torch.from_numpy(error[take].astype(np.float32)).reshape(-1))
+
+
 class InMemoryPosedImages(Dataset):
     def __init__(self, images: Tensor, poses: Tensor, camera_intrinsics: CameraIntrinsics,
-                 camera_bounds: CameraBounds):
+                 camera_bounds: CameraBounds, sparse_points: Optional[SparsePoints] = None):
         if images.dim() != 4 or poses.shape[1:] != (3, 4) or len(images) != len(poses):
             raise ValueError("images must be [N,C,H,W] and poses [N,3,4]")
+        if sparse_points is not None and sparse_points.offsets.numel() != len(images) + 1:
+            raise ValueError("sparse_points.offsets must hold one entry per image plus one")
         self.images, self.poses = images.float(), poses.float()
         self.camera_intrinsics, self.camera_bounds = camera_intrinsics, camera_bounds
+        self.sparse_points = sparse_points
         self.cached_data_mode = True
 
     def __len__(self) -> int:
@@ -92,11 +137,12 @@ class InMemoryPosedImages(Dataset):
             small = self.camera_intrinsics.scaled(factor)      # (the same truncated size; fx fy cx cy / factor)
         else:
             small = CameraIntrinsics(nh, nw, f / factor)
-        return InMemoryPosedImages(images, self.poses, small, self.camera_bounds)
+        return InMemoryPosedImages(images, self.poses, small, self.camera_bounds,
+                                   None if self.sparse_points is None else self.sparse_points.scaled(factor))
 
     def to(self, device) -> "InMemoryPosedImages":
         return InMemoryPosedImages(self.images.to(device), self.poses.to(device), self.camera_intrinsics,
-                                   self.camera_bounds)
+                                   self.camera_bounds, None if self.sparse_points is None else self.sparse_points.to(device))
 
 
 class PosedImagesDataset(InMemoryPosedImages):
@@ -148,10 +194,13 @@ class PosedImagesDataset(InMemoryPosedImages):
         bounds = CameraBounds(float(all_bounds.min() * 0.9) * scale, float(all_bounds.max() * 1.1) * scale)
         lo, hi = image_data_range
         images = torch.stack(imgs) * (hi - lo) + lo
-        super().__init__(images, torch.stack(poses), intr, bounds)
+        # the sparse points the importer wrote next to the camera parameters, when it did: scaled with the scene
+        side = sparse_points_path(camera_params_json)
+        sparse = load_sparse_points(side, [p.name for p in files], scale) if side.exists() else None
+        super().__init__(images, torch.stack(poses), intr, bounds, sparse)
         if downsample_factor != 1.0:
             small = self.downsampled(downsample_factor)
-            self.images, self.camera_intrinsics = small.images, small.camera_intrinsics
+            self.images, self.camera_intrinsics, self.sparse_points = small.images, small.camera_intrinsics, small.sparse_points
 
     @property
     def camera_parameters(self) -> Dict[str, Any]:

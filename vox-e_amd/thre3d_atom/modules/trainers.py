@@ -17,9 +17,11 @@ from torch import Tensor
 from thre3d_atom.modules.optim import FusedGridAdam, VoxeAdam
 from thre3d_atom.modules.testers import test_sh_vox_grid_vol_mod_with_posed_images
 from thre3d_atom.modules.volumetric_model import VolumetricModel
-from thre3d_atom.rendering.volumetric.utils.misc import (is_general_camera, sample_random_patches_and_pixels_from_cameras,
+from thre3d_atom.rendering.volumetric.utils.misc import (_cast_and_gather, is_general_camera,
+                                                          sample_random_patches_and_pixels_from_cameras,
                                                           sample_random_rays_and_pixels_from_cameras)
 from thre3d_atom.thre3d_reprs.background import EnvMapBackground
+from thre3d_atom.thre3d_reprs.depth import depth_targets_on_rays
 from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, LearnedIntrinsics, write_camera_params
 from thre3d_atom.thre3d_reprs.renderers import _render_params, render_sh_voxel_grid
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid, scale_voxel_grid_with_required_output_size
@@ -33,6 +35,35 @@ from voxe_hip.ops import _next_rng
 
 
 _SSIM_MIN_PATCH = 11   # SSIM's window: a smaller patch has no valid window
+
+
+def _depth_batch(data: Any, intr: Any, poses_batch: Tensor, picks: Tensor, batch_size: int, sigma_scale: float,
+                 min_sigma: float, refine: dict):
+    """One batch of depth measurements for the depth term: `batch_size` observations drawn uniformly (with replacement) from the
+    sparse points seen by the picked cameras, each cast at the nearest pixel of its keypoint through `poses_batch` (the poses of
+    `picks`, refined or not: `refine` holds _cast_and_gather's differentiable / intrinsics arguments).  Returns (rays, D, s,
+    omega): the target depth of each ray (depth_targets_on_rays), s = max(sigma_scale * error * D / fx, min_sigma) -- the
+    lateral size of the point's reprojection error at that depth, but no narrower than the mean sample spacing, below which
+    the Gaussian falls between samples -- and omega = 1 (0 for every ray when the picked cameras see no point).  No host
+    synchronisation."""
+    sp = data.sparse_points
+    device = picks.device
+    height, width = int(intr.height), int(intr.width)
+    counts = sp.offsets[picks + 1] - sp.offsets[picks]
+    ends = torch.cumsum(counts, dim=0)
+    total = ends[-1]
+    flat = (torch.rand(int(batch_size), device=device) * total).long().clamp_(max=(total - 1).clamp_min(0))
+    cam = torch.searchsorted(ends, flat, right=True).clamp_(max=picks.numel() - 1)
+    row = (sp.offsets[picks[cam]] + (flat - (ends[cam] - counts[cam]))).clamp_(0, max(sp.xy.shape[0] - 1, 0))
+    # (the centre of the top-left pixel is at (0.5, 0.5): the nearest pixel of a keypoint is the floor of its position)
+    px = sp.xy[row, 0].floor().long().clamp_(0, width - 1)
+    py = sp.xy[row, 1].floor().long().clamp_(0, height - 1)
+    rays, _ = _cast_and_gather(intr, poses_batch, data.images, (cam * height + py) * width + px, picks,
+                               refine.get("differentiable", False), refine.get("intrinsics"))
+    D = depth_targets_on_rays(rays, sp.xyz[row])
+    fx = float(getattr(intr, "fx", intr.focal))
+    s = (sigma_scale * sp.error[row] * D.clamp_min(0.0) / fx).clamp_min(min_sigma)
+    return rays, D, s, (total > 0).to(torch.float32).expand(int(batch_size)).contiguous()
 
 
 class _PinnedStaging:
@@ -113,6 +144,12 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                        # floor(ray_batch_size / P^2) random P x P patches instead of a random pixel set (the L1
                                        # terms run over the same pixels) and the iteration is not the one-call one either
     ssim_patch_size: int = 32,         # P; a stage whose images are smaller uses min(H, W), and skips the term below 11
+    depth_weight: float = 0.0,         # addition of this build: weight of the depth supervision from the dataset's sparse
+                                       # structure-from-motion points (DS-NeRF's ray-termination loss, thre3d_reprs/depth.py,
+                                       # DESIGN.md 4.19); 0 = off, nothing changes.  Above 0 the dataset must carry
+                                       # `sparse_points` and the iteration is not the one-call one either
+    depth_ray_batch_size: int = 4096,  # keypoint rays per iteration, drawn from the observations of the picked cameras
+    depth_sigma_scale: float = 1.0,    # multiplies the width s_r = error_r * D_r / fx of each measurement
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
@@ -121,6 +158,19 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     if ssim_weight < 0.0 or (ssim_weight > 0.0 and ssim_patch_size < _SSIM_MIN_PATCH):
         raise ValueError(f"ssim_weight must not be negative and ssim_patch_size at least {_SSIM_MIN_PATCH} (SSIM's window); got "
                          f"{ssim_weight} and {ssim_patch_size}")
+    if depth_weight < 0.0 or (depth_weight > 0.0 and (depth_ray_batch_size < 1 or not depth_sigma_scale > 0.0)):
+        raise ValueError(f"depth_weight must not be negative, depth_ray_batch_size at least 1 and depth_sigma_scale positive; got "
+                         f"{depth_weight}, {depth_ray_batch_size} and {depth_sigma_scale}")
+    if depth_weight > 0.0 and getattr(train_dataset, "sparse_points", None) is None:
+        from thre3d_atom.data.datasets import SPARSE_POINTS_SUFFIX, sparse_points_path
+
+        config = train_dataset.get_config_dict() if hasattr(train_dataset, "get_config_dict") else {}
+        missing = sparse_points_path(config["camera_params_json"]) if "camera_params_json" in config else f"<split>{SPARSE_POINTS_SUFFIX}"
+        raise ValueError(f"depth_weight > 0 needs the dataset's sparse points, and {missing} does not exist: "
+                         f"tools/convert_from_colmap_text.py writes it next to the camera parameters when the model has a "
+                         f"points3D.txt")
+    if depth_weight > 0.0 and train_dataset.sparse_points.xy.shape[0] == 0:
+        raise ValueError("depth_weight > 0, and the dataset's sparse points hold no observation")
     if background_resolution < 0 or background_resolution == 1:
         raise ValueError(f"background_resolution must be 0 (off) or at least 2; got {background_resolution}")
     if background_resolution > 0:
@@ -218,6 +268,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 log.info("background_resolution > 0: the iterations render, composite the background and step separately (no "
                          "one-call iteration)")
             one_call = False
+        if depth_weight > 0.0:
+            if one_call and stage == 1:
+                log.info("depth_weight > 0: the iterations render, cast the keypoint rays, add the term and step separately (no "
+                         "one-call iteration)")
+            one_call = False
         patch = 0   # side of this stage's SSIM patches; 0: the term is off and the batch is the random pixel set
         if ssim_weight > 0.0:
             if one_call and stage == 1:
@@ -301,6 +356,16 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         #  densities.grad, which step() adds; under VoxeAdam plain autograd sums both)
                         distortion = vol_mod.distortion_loss(rays_batch)
                         loss = loss + distortion_weight * distortion
+                    if depth_weight > 0.0:
+                        # (keypoint rays of the picked cameras, through the same poses and intrinsics as the batch's; the
+                        #  gradient reaches the densities as the distortion term's does)
+                        config = vol_mod.render_config
+                        bounds = config.camera_bounds
+                        depth_rays, depth_target, depth_sigma, depth_omega = _depth_batch(
+                            data, intr, poses_batch, picks, depth_ray_batch_size, depth_sigma_scale,
+                            (bounds.far - bounds.near) / config.num_samples_per_ray, refine)
+                        depth = vol_mod.depth_loss(depth_rays, depth_target, depth_sigma, ray_weight=depth_omega)
+                        loss = loss + depth_weight * depth
                     if patch:
                         # (the batch is patch-major, row, column: the render's colour viewed as channel-last patches)
                         shape = (num_patches, patch, patch, specular.shape[-1])
@@ -327,7 +392,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                     log.info(f"Stage: {stage} Global Iteration: {global_step} Stage Iteration: {it} "
                              f"loss: {float(loss.detach()): .3f} psnr: {float(psnr): .3f}"
                              + (f" distortion: {float(distortion.detach()): .6f}" if distortion_weight > 0.0 else "")
-                             + (f" ssim: {float(ssim.detach()): .4f}" if patch else ""))
+                             + (f" ssim: {float(ssim.detach()): .4f}" if patch else "")
+                             + (f" depth: {float(depth.detach()): .6f}" if depth_weight > 0.0 else ""))
                 if it % lr_decay_steps_per_stage == 0:
                     scheduler.step()
                     if background_scheduler is not None:

@@ -141,6 +141,15 @@ class VolumetricModel:
 
         return distortion_loss_on_rays(self._thre3d_repr, rays, self._update_render_config(self._render_config, kwargs))
 
+    def depth_loss(self, rays: Rays, target_depth: torch.Tensor, target_sigma: torch.Tensor,
+                   ray_weight: Optional[torch.Tensor] = None, eps: float = 1e-5, **kwargs) -> torch.Tensor:
+        """mean ray-termination loss of flat `rays` towards per-ray depth targets (thre3d_reprs.depth.depth_loss_on_rays)
+        under the model's render config with `kwargs` applied; differentiable w.r.t. the grid's densities"""
+        from thre3d_atom.thre3d_reprs.depth import depth_loss_on_rays
+
+        return depth_loss_on_rays(self._thre3d_repr, rays, target_depth, target_sigma,
+                                  self._update_render_config(self._render_config, kwargs), ray_weight=ray_weight, eps=eps)
+
     # -- whole-camera, no grad --------------------------------------------------------------------
     def _render_camera(self, render_chunk, collate, reshape, camera_pose, camera_intrinsics,
                        parallel_rays_chunk_size, gpu_render, verbose):

@@ -1,5 +1,5 @@
-"""Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss on rays, SSIM) and Adam
-on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
+"""Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss and the depth
+supervision on rays, SSIM) and Adam on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
 import ctypes as C
 from typing import Optional, Tuple
 
@@ -180,6 +180,99 @@ def distortion_loss(spec: GridSpec, params: RenderParams, densities: torch.Tenso
     forward, only when it is needed); return_ray_loss=True: (loss, L_r [R], not differentiable)."""
     rng = resolve_rng(params, jitter, rng)
     return _DistortionFn.apply(densities, spec, params, rays_o, rays_d, jitter, rng, bool(return_ray_loss), int(_lanes))
+
+
+# ------------------------------------------------------------------------------------------------
+# depth supervision: ray-termination loss towards per-ray depth targets (DESIGN.md section 4.19): reads the raw densities only,
+# no workspace; differentiable w.r.t. the densities
+# ------------------------------------------------------------------------------------------------
+DEPTH_EPS = 1e-5   # DS-NeRF's
+
+
+def _per_ray(entry: str, name: str, t: Optional[torch.Tensor], R: int, device) -> Optional[torch.Tensor]:
+    """a per-ray input [R] as dense float32 on the rays' device"""
+    if t is None:
+        return None
+    require_device(t, f"{entry} ({name})")
+    if t.numel() != R or t.device != device:
+        raise VoxeError(f"{entry}: {name} must hold one value per ray ({R}) on {device}; got {tuple(t.shape)} on {t.device}")
+    return f32c(t.detach().reshape(R))
+
+
+def depth_fwd_bwd(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                  target_depth: torch.Tensor, target_sigma: torch.Tensor, ray_weight: Optional[torch.Tensor] = None,
+                  jitter: Optional[torch.Tensor] = None, rng: Tuple[int, int] = (0, 0), eps: float = DEPTH_EPS,
+                  grad_scale: float = 1.0, want_loss: bool = True, want_ray_loss: bool = False,
+                  d_densities: Optional[torch.Tensor] = None, accumulate: bool = False, lanes: int = 0):
+    """voxe_depth_fwd_bwd as it stands: (loss [] or None, ray_loss [R] or None); `d_densities` (contiguous float32 of the
+    densities' shape, or None) receives grad_scale * dloss/draw, added to its contents when `accumulate`.  `lanes` (test aid):
+    1 / 2 / 4 / 8 pins the kernel's lanes per ray for this call, 0 = chosen by R."""
+    _check_densities(densities, "depth_loss")
+    _check_rays("depth_loss", rays_o, rays_d, jitter, params.num_samples)
+    device = densities.device
+    if d_densities is not None:
+        _require_buffer("depth_loss", "d_densities", d_densities, shape=densities.shape, device=device)
+    g, c, dens, ro, rd, jit = _sampling_inputs(spec, params, densities, rays_o, rays_d, jitter, rng)
+    R = ro.shape[0]
+    td, ts, rw = (_per_ray("depth_loss", n, t, R, device) for n, t in (("target_depth", target_depth), ("target_sigma", target_sigma),
+                                                                       ("ray_weight", ray_weight)))
+    if td is None or ts is None:
+        raise VoxeError("depth_loss: target_depth and target_sigma are required")
+    L = lib()
+    with torch.cuda.device(device):
+        loss = torch.zeros((), dtype=torch.float32, device=device) if want_loss else None
+        ray_loss = torch.empty((R,), dtype=torch.float32, device=device) if want_ray_loss else None
+        sc = _scratch_for(device, L.voxe_depth_scratch_bytes(R)) if want_loss else None
+        if lanes:
+            check(L.voxe_depth_debug_lanes(int(lanes)), "voxe_depth_debug_lanes")
+        try:
+            check(L.voxe_depth_fwd_bwd(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), ptr(td), ptr(ts), ptr(rw), float(eps),
+                                       float(grad_scale), ptr(loss), ptr(ray_loss), ptr(d_densities), 1 if accumulate else 0,
+                                       ptr(sc), sc.numel() if sc is not None else 0, stream_ptr(device)), "voxe_depth_fwd_bwd")
+        finally:
+            if lanes:
+                L.voxe_depth_debug_lanes(0)
+    wrote(d_densities)
+    return loss, ray_loss
+
+
+class _DepthFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, densities, spec, params, rays_o, rays_d, target_depth, target_sigma, ray_weight, jitter, rng, eps,
+                return_ray_loss, lanes):
+        d_d = torch.empty_like(f32c(densities.detach())) if ctx.needs_input_grad[0] else None
+        loss, ray_loss = depth_fwd_bwd(spec, params, densities, rays_o, rays_d, target_depth, target_sigma, ray_weight, jitter, rng,
+                                       eps=eps, want_ray_loss=return_ray_loss, d_densities=d_d, lanes=lanes)
+        ctx.save_for_backward(d_d)
+        if return_ray_loss:
+            ctx.mark_non_differentiable(ray_loss)
+            return loss, ray_loss
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (d_d,) = ctx.saved_tensors
+        return (None if d_d is None else d_d * g,) + (None,) * 12
+
+
+def depth_loss(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+               target_depth: torch.Tensor, target_sigma: torch.Tensor, ray_weight: Optional[torch.Tensor] = None,
+               jitter: Optional[torch.Tensor] = None, rng: Optional[Tuple[int, int]] = None, eps: float = DEPTH_EPS,
+               return_ray_loss: bool = False, _lanes: int = 0):
+    """Ray-termination loss of flat rays towards depth targets (DS-NeRF): the mean over rays of
+    omega_r L_r, L_r = -sum_k exp(-(z_k - D_r)^2 / (2 s_r^2)) dz_k log(w_k + eps), with the samples and weights `render` uses for
+    the same params, jitter and rng (`rng` follows render's rule).  target_depth D, target_sigma s > 0 (both in the units of the
+    sample depths) and ray_weight omega >= 0 (None = 1) hold one value per ray and receive no gradient.  A scalar tensor,
+    differentiable w.r.t. `densities` (the gradient is computed in the forward, only when it is needed);
+    return_ray_loss=True: (loss, L_r [R], not differentiable)."""
+    for name, t in (("target_depth", target_depth), ("target_sigma", target_sigma), ("ray_weight", ray_weight)):
+        if t is not None and t.requires_grad:
+            raise VoxeError(f"depth_loss: {name} receives no gradient; detach it")
+    if not (eps > 0.0 and eps < float("inf")):
+        raise VoxeError(f"depth_loss: eps must be finite and > 0; got {eps}")
+    rng = resolve_rng(params, jitter, rng)
+    return _DepthFn.apply(densities, spec, params, rays_o, rays_d, target_depth, target_sigma, ray_weight, jitter, rng, float(eps),
+                          bool(return_ray_loss), int(_lanes))
 
 
 # ------------------------------------------------------------------------------------------------
