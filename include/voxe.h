@@ -829,6 +829,49 @@ int voxe_depth_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
 int voxe_depth_debug_lanes(int32_t lanes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Orientation loss on rays (additive; still ABI v13), DESIGN.md section 4.20.  Ref-NeRF's regulariser (Verbin et al., CVPR 2022,
+ * eq. 11) against weight on samples whose normal faces away from the viewer; no voxe_cpu_ twin, the float64 restatement is
+ * tests/orientation_ref.py.
+ *   The samples z_k, the inside test, sigma_k, delta_k = dl_k |d| (last dl = 1e10), T_k and w_k = T_k alpha_k are those of
+ *   voxe_distortion_fwd_bwd for the same rays, cfg and jitter / (seed, rng_offset), and so are the cfg fields honoured and
+ *   ignored.  The field of the normals is voxe_render_normals's: v_i = pre(density_scale * raw_i), V its trilinear interpolant
+ *   with zero padding, G_k the world-space gradient of V in the cell of sample k (a face cell uses the slope with the padded
+ *   0).  With u_r = d_r / |d_r| and a guard normal_eps >= 0 in the units of G:
+ *       rho_k = sqrt(|G_k|^2 + normal_eps^2)
+ *       c_k   = max(0, -(G_k . u_r)) / rho_k                (0 where rho_k == 0)
+ *       L_r   = sum_k w_k c_k^2
+ *       loss  = (1/R) sum_r omega_r L_r                     (omega = ray_weight, 1 when NULL)
+ *   At normal_eps == 0, c_k = max(0, n_k . u_r) with n_k = -G_k / |G_k|, the normal voxe_render_normals composites.  A sample
+ *   that fails the AABB test, or lies behind the point where T reaches 0, has w = 0 and contributes nothing.  |G|^2 neither
+ *   overflows nor underflows for finite corner values.  normal_eps must be finite and >= 0 (VOXE_ERR_BAD_SHAPE otherwise).
+ *   Gradient w.r.t. the raw densities [X,Y,Z,1], two parts on the same 8 footprint corners (one float atomic per corner and
+ *   sample):
+ *     through the weights:  dL_r/dsigma_k = delta_k [c_k^2 (T_k - w_k) - sum_{i>k} c_i^2 w_i], and from there through
+ *       post_activate', the gather weights and pre_activate' * density_scale as in voxe_distortion_fwd_bwd;
+ *     through the normals:  dL_r/dG_k = 2 w_k c_k (-u_r / rho_k - c_k G_k / rho_k^2) for c_k > 0, exactly 0 for c_k == 0 or
+ *       rho_k == 0;  dG_a/dv_q = (N_a scale_a / 2) * (slope coefficient of corner q on axis a) * (the two other axes' cell
+ *       weights), then pre_activate' * density_scale.  post_activate is not on this path.  In a face cell the slope coefficients
+ *       are not the gather weights' differences: the padded 0 has a slope but no weight.
+ *   Derivative conventions at the kinks of abs / ReLU: voxe_render_bwd's.  The sum is scaled by grad_scale * omega_r / R.  No
+ *   gradient flows to the rays, to z or to omega.  The caller guarantees finite omega >= 0; ray_weight is read for [R] only.
+ *   Outputs (each may be NULL): loss_out  device float[1], the weighted mean above (grad_scale does not apply to it);
+ *                               ray_loss  device [R], L_r (without omega_r);
+ *                               d_densities [X,Y,Z,1], accumulate as in voxe_distortion_fwd_bwd (0: the buffer is zeroed
+ *                               first, so untouched voxels hold an exact 0).
+ *   loss_out and ray_loss are the same bits from run to run (fixed-order sums); the gradient goes through float atomics.
+ *   scratch (voxe_orientation_scratch_bytes(R), read only when loss_out != NULL), R == 0, all outputs NULL, validation, limits,
+ *   error codes, stream and the "no workspace, no forward record, no voxe_recon_prefetch hint is touched" clause: as
+ *   voxe_distortion_fwd_bwd.  voxe_orientation_debug_lanes: test aid, as voxe_distortion_debug_lanes.                         */
+size_t voxe_orientation_scratch_bytes(int64_t R);
+int voxe_orientation_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                             const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                             const float* ray_weight    /* [R] or NULL (= 1) */,
+                             float normal_eps, float grad_scale,
+                             float* loss_out, float* ray_loss, float* d_densities, int32_t accumulate,
+                             void* scratch, size_t scratch_bytes, void* stream);
+int voxe_orientation_debug_lanes(int32_t lanes);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM of two image batches, value and gradient in one call (additive; still ABI v13), DESIGN.md section 4.18 "SSIM".  No
  * voxe_cpu_ twin; the float64 restatement is tests/ssim_ref.py.
  *   x, y: device float, channel-last [N,H,W,C], C in 1..4 (a render's colour viewed as patches or as an image).  Wang et al.

@@ -90,6 +90,11 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
               help="keypoint rays of the depth term per iteration")
 @click.option("--depth_sigma_scale", type=click.FloatRange(min=0.0, min_open=True), default=1.0, show_default=True,
               help="multiplies the width of each depth measurement (its reprojection error at its depth)")
+@click.option("--orientation_weight", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
+              help="weight of the orientation loss on each ray batch (penalises weight on samples whose normal faces away from "
+                   "the viewer); 0 = off")
+@click.option("--orientation_normal_eps", type=click.FloatRange(min=0.0), default=1e-2, show_default=True,
+              help="guard under the length of the density gradient in the orientation loss, in the gradient's units")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -129,7 +134,8 @@ def main(**kwargs) -> None:
         num_workers=cfg.num_workers, distortion_weight=cfg.distortion_weight, pose_learning_rate=cfg.pose_learning_rate,
         intrinsics_learning_rate=cfg.intrinsics_learning_rate, background_resolution=cfg.background_resolution,
         background_learning_rate=cfg.background_learning_rate, ssim_weight=cfg.ssim_weight, ssim_patch_size=cfg.ssim_patch_size,
-        depth_weight=cfg.depth_weight, depth_ray_batch_size=cfg.depth_ray_batch_size, depth_sigma_scale=cfg.depth_sigma_scale)
+        depth_weight=cfg.depth_weight, depth_ray_batch_size=cfg.depth_ray_batch_size, depth_sigma_scale=cfg.depth_sigma_scale,
+        orientation_weight=cfg.orientation_weight, orientation_normal_eps=cfg.orientation_normal_eps)
 
 
 if __name__ == "__main__":

@@ -1613,6 +1613,34 @@ int voxe_depth_debug_lanes(int32_t lanes) {
   return VOXE_OK;
 }
 
+// ---- orientation loss on rays -----------------------------------------------------------------------------
+size_t voxe_orientation_scratch_bytes(int64_t R) { return orientation_scratch_bytes(R); }
+
+int voxe_orientation_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d,
+                             int64_t R, const float* jitter, const float* ray_weight, float normal_eps, float grad_scale,
+                             float* loss_out, float* ray_loss, float* d_densities, int32_t accumulate, void* scratch,
+                             size_t scratch_bytes, void* stream) {
+  DevGrid dg;
+  DevCfg dc;
+  const int st = sampling_call(grid, cfg, R, rays_o, rays_d, &dg, &dc);
+  if (st) return st;
+  if (!(normal_eps >= 0.0f) || !std::isfinite(normal_eps)) return VOXE_ERR_BAD_SHAPE;
+  if (R > 0 && loss_out && (!scratch || scratch_bytes < orientation_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
+  const bool clear = d_densities && !accumulate;
+  if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
+    return VOXE_ERR_LAUNCH;
+  if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
+  launch_orientation(dg, dc, grid->densities, rays_o, rays_d, jitter, ray_weight, normal_eps, grad_scale, loss_out, ray_loss,
+                     d_densities, scratch, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_orientation_debug_lanes(int32_t lanes) {
+  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
+  tl_orientation_lanes = lanes;
+  return VOXE_OK;
+}
+
 // ---- SSIM of channel-last images --------------------------------------------------------------------------
 namespace {
 bool ssim_shape_ok(int32_t N, int32_t H, int32_t W, int32_t C) { return N >= 1 && H >= 11 && W >= 11 && C >= 1 && C <= 4; }

@@ -245,7 +245,7 @@ size_t distortion_scratch_bytes(long long R);
 void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                        const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
                        hipStream_t st);
-// *loss_out = (sum of `nb` per-block partials, fixed order) / R  (distortion and depth)
+// *loss_out = (sum of `nb` per-block partials, fixed order) / R  (distortion, depth and orientation)
 void launch_partial_mean(const double* partial, long long nb, long long R, float* loss_out, hipStream_t st);
 
 // voxe_depth.hip: ray-termination loss towards per-ray depth targets, value + density gradient; reads the raw
@@ -255,6 +255,14 @@ size_t depth_scratch_bytes(long long R);
 void launch_depth(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                   const float* jitter, const float* target_depth, const float* target_sigma, const float* ray_weight, float eps,
                   float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch, hipStream_t st);
+
+// voxe_orientation.hip: orientation loss on rays, value + density gradient through the weights and the normals (DESIGN.md
+// 4.20); reads the raw densities only
+extern thread_local int tl_orientation_lanes;   // test aid (voxe_orientation_debug_lanes): != 0 pins the lanes per ray
+size_t orientation_scratch_bytes(long long R);
+void launch_orientation(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
+                        const float* jitter, const float* ray_weight, float normal_eps, float grad_scale, float* loss_out,
+                        float* ray_loss, float* d_dens, void* scratch, hipStream_t st);
 
 // voxe_render_rays_bwd.hip: gradient of a render w.r.t. its rays; reads the raw densities and features, no
 // workspace, no atomics

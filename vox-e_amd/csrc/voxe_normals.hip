@@ -23,29 +23,12 @@ namespace {
 constexpr int kNormThreads = kMarchThreads;
 constexpr int kQueryMaxBlocks = 4096;   // grid-stride beyond this (cdna_hip_programming.md Guideline 11)
 
-// n(p) = -G / |G| from the cell's corner values; `gs` = N_a * scale_a / 2 (index units -> world units).  G is scaled by its
-// largest component first, so no |G|^2 underflows or overflows; exactly (0,0,0) where G == 0.
+// n(p) = -G / |G| from the cell's corner values (cell_gradient()); `gs` = N_a * scale_a / 2 (index units -> world units).  G
+// is scaled by its largest component first, so no |G|^2 underflows or overflows; exactly (0,0,0) where G == 0.
 __device__ __forceinline__ void cell_normal(const DevGrid& g, const Footprint& fp, const Cell& cell, const float (&cv)[8],
                                             const float (&gs)[3], float (&n)[3]) {
-  const int N[3] = {g.X, g.Y, g.Z};
-  float d[3][2];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) slope_coefs(fp.i0[a], N[a], d[a][0], d[a][1]);
-  float G[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {   // p = the corner bits of the two other axes
-    // x: corners (0 | 2y | 4z), y: (x | 0 | 4z), z: (x | 2y | 0)
-    const int b0 = p & 1, b1 = p >> 1;
-    const int kx = 2 * b0 + 4 * b1, ky = b0 + 4 * b1, kz = b0 + 2 * b1;
-    const float ex = fmaf(d[0][1], cv[kx + 1], d[0][0] * cv[kx]);
-    const float ey = fmaf(d[1][1], cv[ky + 2], d[1][0] * cv[ky]);
-    const float ez = fmaf(d[2][1], cv[kz + 4], d[2][0] * cv[kz]);
-    G[0] = fmaf(cell.w[1][b0] * cell.w[2][b1], ex, G[0]);
-    G[1] = fmaf(cell.w[0][b0] * cell.w[2][b1], ey, G[1]);
-    G[2] = fmaf(cell.w[0][b0] * cell.w[1][b1], ez, G[2]);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) G[a] = G[a] * gs[a];
+  float G[3];
+  cell_gradient(g, fp, cell, cv, gs, G);
   const float m = fmaxf(fmaxf(fabsf(G[0]), fabsf(G[1])), fabsf(G[2]));
   if (m > 0.0f) {
     const float inv = fast_rcp(m);

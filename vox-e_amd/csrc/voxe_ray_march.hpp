@@ -1,8 +1,8 @@
 // voxe_ray_march.hpp -- the density-only sample march ("The shared sample march").
 //
-// Six calls walk the forward's exact samples over the RAW densities without rendering colour: voxe_render_normals,
-// voxe_visibility_accumulate, voxe_distortion_fwd_bwd, voxe_render_bwd_rays, voxe_lift_accumulate and voxe_depth_fwd_bwd.  What
-// ties them to the renderer lives here, once:
+// Seven calls walk the forward's exact samples over the RAW densities without rendering colour: voxe_render_normals,
+// voxe_visibility_accumulate, voxe_distortion_fwd_bwd, voxe_render_bwd_rays, voxe_lift_accumulate, voxe_depth_fwd_bwd and
+// voxe_orientation_fwd_bwd.  What ties them to the renderer lives here, once:
 //   depth step : sample k sits at z_k = DepthGen::z(k); its interval is dl_k = z_{k+1} - z_k, kInfinity for the last sample
 //   cell       : p = o + d z, footprint(); a sample outside the box has sigma = 0 -> w = 0, T unchanged (the forward's rule)
 //   density    : 8 raw loads, v = sum_q pre(raw_q) t_q with t_q = (wx * wy) * wz and the corners ascending (gather()'s
@@ -211,7 +211,7 @@ __device__ __forceinline__ void eval_density(const DevGrid& g, const Cell& cell,
 // ---- the march ---------------------------------------------------------------------------------------------------------------
 // Samples k_lo .. k_hi of a ray front to back with the running transmittance T.  body(step, footprint, cell, T) handles one
 // sample inside the box and returns its 1 - alpha.
-// (Visibility, both distortion marches and the three of the depth loss.  Normals, the ray gradients and lifting write their
+// (Visibility, both distortion marches, the three of the depth loss and both of the orientation loss.  Normals, the ray gradients and lifting write their
 // loops out over the same pieces; each says why.)
 template <class RC, class Body>
 __device__ __forceinline__ void march_block(const DevGrid& g, const DevCfg& c, RC& rc, int k_lo, int k_hi, float& T, Body&& body) {
@@ -246,6 +246,33 @@ __device__ __forceinline__ void index_to_world(const DevGrid& g, float (&gs)[3])
   const int N[3] = {g.X, g.Y, g.Z};
 #pragma unroll
   for (int a = 0; a < 3; ++a) gs[a] = ((float)N[a] * g.scale[a]) * 0.5f;
+}
+
+// World-space gradient G of the density field V in the cell of a sample, from the cell's pre-activated corner values `cv`
+// (corner q = x + 2 y + 4 z): per axis the slope along it (slope_coefs) blended bilinearly over the two other axes with the
+// cell's weights, times `gs` = N_a * scale_a / 2 (index_to_world).  The normals kernels and the orientation loss share it.
+__device__ __forceinline__ void cell_gradient(const DevGrid& g, const Footprint& fp, const Cell& cell, const float (&cv)[8],
+                                              const float (&gs)[3], float (&G)[3]) {
+  const int N[3] = {g.X, g.Y, g.Z};
+  float d[3][2];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) slope_coefs(fp.i0[a], N[a], d[a][0], d[a][1]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) G[a] = 0.0f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {   // p = the corner bits of the two other axes
+    // x: corners (0 | 2y | 4z), y: (x | 0 | 4z), z: (x | 2y | 0)
+    const int b0 = p & 1, b1 = p >> 1;
+    const int kx = 2 * b0 + 4 * b1, ky = b0 + 4 * b1, kz = b0 + 2 * b1;
+    const float ex = fmaf(d[0][1], cv[kx + 1], d[0][0] * cv[kx]);
+    const float ey = fmaf(d[1][1], cv[ky + 2], d[1][0] * cv[ky]);
+    const float ez = fmaf(d[2][1], cv[kz + 4], d[2][0] * cv[kz]);
+    G[0] = fmaf(cell.w[1][b0] * cell.w[2][b1], ex, G[0]);
+    G[1] = fmaf(cell.w[0][b0] * cell.w[2][b1], ey, G[1]);
+    G[2] = fmaf(cell.w[0][b0] * cell.w[1][b1], ez, G[2]);
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) G[a] = G[a] * gs[a];
 }
 
 // blocks of a launch whose threads find their ray with map_ray(): a 16x16 pixel tile (8x8 per wave) or 256 consecutive rays

@@ -150,6 +150,13 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                        # `sparse_points` and the iteration is not the one-call one either
     depth_ray_batch_size: int = 4096,  # keypoint rays per iteration, drawn from the observations of the picked cameras
     depth_sigma_scale: float = 1.0,    # multiplies the width s_r = error_r * D_r / fx of each measurement
+    orientation_weight: float = 0.0,   # addition of this build: weight of the orientation loss on the ray batch (Ref-NeRF's
+                                       # regulariser against weight on samples whose density-gradient normal faces away from the
+                                       # viewer, thre3d_reprs/orientation.py); 0 = off, nothing changes.  Above 0
+                                       # the iteration is not the one-call one either
+    orientation_normal_eps: float = 1e-2,   # the guard under the normal's length, in the units of the density gradient.  A guard,
+                                            # not a tuned value: about 2e-4 of a unit density step across one voxel of a 160^3
+                                            # grid over [-1.5, 1.5]
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
@@ -161,6 +168,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     if depth_weight < 0.0 or (depth_weight > 0.0 and (depth_ray_batch_size < 1 or not depth_sigma_scale > 0.0)):
         raise ValueError(f"depth_weight must not be negative, depth_ray_batch_size at least 1 and depth_sigma_scale positive; got "
                          f"{depth_weight}, {depth_ray_batch_size} and {depth_sigma_scale}")
+    if orientation_weight < 0.0 or not (0.0 <= orientation_normal_eps < float("inf")):
+        raise ValueError(f"orientation_weight must not be negative and orientation_normal_eps finite and not negative; got "
+                         f"{orientation_weight} and {orientation_normal_eps}")
     if depth_weight > 0.0 and getattr(train_dataset, "sparse_points", None) is None:
         from thre3d_atom.data.datasets import SPARSE_POINTS_SUFFIX, sparse_points_path
 
@@ -273,6 +283,10 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 log.info("depth_weight > 0: the iterations render, cast the keypoint rays, add the term and step separately (no "
                          "one-call iteration)")
             one_call = False
+        if orientation_weight > 0.0:
+            if one_call and stage == 1:
+                log.info("orientation_weight > 0: the iterations render, add the term and step separately (no one-call iteration)")
+            one_call = False
         patch = 0   # side of this stage's SSIM patches; 0: the term is off and the batch is the random pixel set
         if ssim_weight > 0.0:
             if one_call and stage == 1:
@@ -366,6 +380,10 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                             (bounds.far - bounds.near) / config.num_samples_per_ray, refine)
                         depth = vol_mod.depth_loss(depth_rays, depth_target, depth_sigma, ray_weight=depth_omega)
                         loss = loss + depth_weight * depth
+                    if orientation_weight > 0.0:
+                        # (on the ray batch; the gradient reaches the densities as the distortion term's does)
+                        orientation = vol_mod.orientation_loss(rays_batch, normal_eps=orientation_normal_eps)
+                        loss = loss + orientation_weight * orientation
                     if patch:
                         # (the batch is patch-major, row, column: the render's colour viewed as channel-last patches)
                         shape = (num_patches, patch, patch, specular.shape[-1])
@@ -393,7 +411,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                              f"loss: {float(loss.detach()): .3f} psnr: {float(psnr): .3f}"
                              + (f" distortion: {float(distortion.detach()): .6f}" if distortion_weight > 0.0 else "")
                              + (f" ssim: {float(ssim.detach()): .4f}" if patch else "")
-                             + (f" depth: {float(depth.detach()): .6f}" if depth_weight > 0.0 else ""))
+                             + (f" depth: {float(depth.detach()): .6f}" if depth_weight > 0.0 else "")
+                             + (f" orientation: {float(orientation.detach()): .6f}" if orientation_weight > 0.0 else ""))
                 if it % lr_decay_steps_per_stage == 0:
                     scheduler.step()
                     if background_scheduler is not None:

@@ -150,6 +150,15 @@ class VolumetricModel:
         return depth_loss_on_rays(self._thre3d_repr, rays, target_depth, target_sigma,
                                   self._update_render_config(self._render_config, kwargs), ray_weight=ray_weight, eps=eps)
 
+    def orientation_loss(self, rays: Rays, ray_weight: Optional[torch.Tensor] = None, normal_eps: float = 1e-2,
+                         **kwargs) -> torch.Tensor:
+        """mean orientation loss of flat `rays` (thre3d_reprs.orientation.orientation_loss_on_rays) under the model's render
+        config with `kwargs` applied; differentiable w.r.t. the grid's densities"""
+        from thre3d_atom.thre3d_reprs.orientation import orientation_loss_on_rays
+
+        return orientation_loss_on_rays(self._thre3d_repr, rays, self._update_render_config(self._render_config, kwargs),
+                                        ray_weight=ray_weight, normal_eps=normal_eps)
+
     # -- whole-camera, no grad --------------------------------------------------------------------
     def _render_camera(self, render_chunk, collate, reshape, camera_pose, camera_intrinsics,
                        parallel_rays_chunk_size, gpu_render, verbose):

@@ -258,6 +258,11 @@ HIP_ONLY = {
     "depth_fwd_bwd": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, C.c_int32, _P,
                                 C.c_size_t, _P]),
     "depth_debug_lanes": (C.c_int, [C.c_int32]),
+    # orientation loss on rays (additive, still ABI v13)
+    "orientation_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "orientation_fwd_bwd": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, C.c_float, C.c_float, _P, _P, _P, C.c_int32, _P,
+                                      C.c_size_t, _P]),
+    "orientation_debug_lanes": (C.c_int, [C.c_int32]),
     # ray and camera-pose gradients (additive, still ABI v13)
     "render_bwd_rays": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "render_bwd_rays_debug_lanes": (C.c_int, [C.c_int32]),

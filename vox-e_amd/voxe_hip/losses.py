@@ -1,5 +1,5 @@
-"""Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss and the depth
-supervision on rays, SSIM) and Adam on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
+"""Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss, the depth
+supervision and the orientation loss on rays, SSIM) and Adam on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
 import ctypes as C
 from typing import Optional, Tuple
 
@@ -273,6 +273,87 @@ def depth_loss(spec: GridSpec, params: RenderParams, densities: torch.Tensor, ra
     rng = resolve_rng(params, jitter, rng)
     return _DepthFn.apply(densities, spec, params, rays_o, rays_d, target_depth, target_sigma, ray_weight, jitter, rng, float(eps),
                           bool(return_ray_loss), int(_lanes))
+
+
+# ------------------------------------------------------------------------------------------------
+# orientation loss on rays: reads the raw densities only, no workspace; differentiable w.r.t. the
+# densities
+# ------------------------------------------------------------------------------------------------
+ORIENTATION_NORMAL_EPS = 1e-2   # a guard, not a tuned value (see orientation_loss)
+
+
+def orientation_fwd_bwd(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                        ray_weight: Optional[torch.Tensor] = None, jitter: Optional[torch.Tensor] = None,
+                        rng: Tuple[int, int] = (0, 0), normal_eps: float = ORIENTATION_NORMAL_EPS, grad_scale: float = 1.0,
+                        want_loss: bool = True, want_ray_loss: bool = False, d_densities: Optional[torch.Tensor] = None,
+                        accumulate: bool = False, lanes: int = 0):
+    """voxe_orientation_fwd_bwd as it stands: (loss [] or None, ray_loss [R] or None); `d_densities` (contiguous float32 of the
+    densities' shape, or None) receives grad_scale * dloss/draw, added to its contents when `accumulate`.  `lanes` (test aid):
+    1 / 2 / 4 / 8 pins the kernel's lanes per ray for this call, 0 = chosen by R."""
+    _check_densities(densities, "orientation_loss")
+    _check_rays("orientation_loss", rays_o, rays_d, jitter, params.num_samples)
+    device = densities.device
+    if d_densities is not None:
+        _require_buffer("orientation_loss", "d_densities", d_densities, shape=densities.shape, device=device)
+    g, c, dens, ro, rd, jit = _sampling_inputs(spec, params, densities, rays_o, rays_d, jitter, rng)
+    R = ro.shape[0]
+    rw = _per_ray("orientation_loss", "ray_weight", ray_weight, R, device)
+    L = lib()
+    with torch.cuda.device(device):
+        loss = torch.zeros((), dtype=torch.float32, device=device) if want_loss else None
+        ray_loss = torch.empty((R,), dtype=torch.float32, device=device) if want_ray_loss else None
+        sc = _scratch_for(device, L.voxe_orientation_scratch_bytes(R)) if want_loss else None
+        if lanes:
+            check(L.voxe_orientation_debug_lanes(int(lanes)), "voxe_orientation_debug_lanes")
+        try:
+            check(L.voxe_orientation_fwd_bwd(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), ptr(rw), float(normal_eps),
+                                             float(grad_scale), ptr(loss), ptr(ray_loss), ptr(d_densities), 1 if accumulate else 0,
+                                             ptr(sc), sc.numel() if sc is not None else 0, stream_ptr(device)),
+                  "voxe_orientation_fwd_bwd")
+        finally:
+            if lanes:
+                L.voxe_orientation_debug_lanes(0)
+    wrote(d_densities)
+    return loss, ray_loss
+
+
+class _OrientationFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, densities, spec, params, rays_o, rays_d, ray_weight, jitter, rng, normal_eps, return_ray_loss, lanes):
+        d_d = torch.empty_like(f32c(densities.detach())) if ctx.needs_input_grad[0] else None
+        loss, ray_loss = orientation_fwd_bwd(spec, params, densities, rays_o, rays_d, ray_weight, jitter, rng, normal_eps=normal_eps,
+                                             want_ray_loss=return_ray_loss, d_densities=d_d, lanes=lanes)
+        ctx.save_for_backward(d_d)
+        if return_ray_loss:
+            ctx.mark_non_differentiable(ray_loss)
+            return loss, ray_loss
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (d_d,) = ctx.saved_tensors
+        return (None if d_d is None else d_d * g,) + (None,) * 10
+
+
+def orientation_loss(spec: GridSpec, params: RenderParams, densities: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
+                     ray_weight: Optional[torch.Tensor] = None, jitter: Optional[torch.Tensor] = None,
+                     rng: Optional[Tuple[int, int]] = None, normal_eps: float = ORIENTATION_NORMAL_EPS,
+                     return_ray_loss: bool = False, _lanes: int = 0):
+    """Orientation loss of flat rays (Ref-NeRF): the mean over rays of omega_r L_r, L_r = sum_k w_k max(0, n_k . u_r)^2, with the
+    samples and weights `render` uses for the same params, jitter and rng (`rng` follows render's rule), u_r the unit ray
+    direction and n_k = -G_k / sqrt(|G_k|^2 + normal_eps^2) the density-gradient normal `render_normals` composites, guarded by
+    `normal_eps` >= 0 in the units of the gradient G.  The default 1e-2 is a guard, not a tuned value: about 2e-4 of a unit
+    density step across one voxel of a 160^3 grid over [-1.5, 1.5].  ray_weight omega >= 0 (None = 1) holds one value per ray
+    and receives no gradient, nor do the rays.  A scalar tensor, differentiable w.r.t. `densities` through the weights and
+    through the normals (the gradient is computed in the forward, only when it is needed); return_ray_loss=True:
+    (loss, L_r [R], not differentiable)."""
+    if ray_weight is not None and ray_weight.requires_grad:
+        raise VoxeError("orientation_loss: ray_weight receives no gradient; detach it")
+    if not (normal_eps >= 0.0 and normal_eps < float("inf")):
+        raise VoxeError(f"orientation_loss: normal_eps must be finite and >= 0; got {normal_eps}")
+    rng = resolve_rng(params, jitter, rng)
+    return _OrientationFn.apply(densities, spec, params, rays_o, rays_d, ray_weight, jitter, rng, float(normal_eps),
+                                bool(return_ray_loss), int(_lanes))
 
 
 # ------------------------------------------------------------------------------------------------
