@@ -872,6 +872,64 @@ int voxe_orientation_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
 int voxe_orientation_debug_lanes(int32_t lanes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-image exposure compensation (additive; still ABI v13), DESIGN.md section 4.21 "Exposure".  A learned 3x4 affine colour
+ * transform per training image (3D Gaussian Splatting's exposure optimisation, URF's exposure term) under the photometric loss,
+ * and the sums of the closed-form least-squares affine of the colour-corrected metrics (mip-NeRF 360, RawNeRF).  No grid, no
+ * workspace, no voxe_cpu_ twin; the float64 restatement is tests/exposure_ref.py.
+ *
+ * voxe_exposure_fwd_bwd.  Inputs, device, read only: x [R,3] rendered colours, y [R,3] targets, image_id [R] int32,
+ *   delta [N,12] row-major per image: dA (3x3, row-major) then db (3); ray_weight [R] or NULL (= 1).  kind: VOXE_DREG_L1 or
+ *   VOXE_DREG_L2 (VOXE_ERR_UNSUPPORTED otherwise).  Per ray r with n = image_id[r]:
+ *       A = I + dA_n,  c' = A x_r + db_n,  e = c' - y_r
+ *       loss = (1/3R) sum_r omega_r sum_c |e_c|   (L1)   or   (1/3R) sum_r omega_r sum_c e_c^2   (L2)
+ *       mse  = (1/3R) sum_r sum_c e_c^2                 (without omega, whichever the kind)
+ *       g    = omega_r sign(e)   (L1, sign(0) = 0 as torch's l1_loss)   or   2 omega_r e   (L2)
+ *       d_x_r      = (grad_scale / 3R) A^T g
+ *       d_delta[n] = (grad_scale / 3R) sum_{r: image_id[r] = n} (g x_r^T row-major, g)
+ *   An image_id outside [0, N) is clamped to the nearest end on the device: nothing is read or written out of bounds, and the
+ *   ray counts for image 0 or N - 1.  Callers check their ids once per dataset, not per call.
+ *   Outputs (each may be NULL = skipped): loss_out, mse_out device float[1] (grad_scale does not apply to them);
+ *     corrected [R,3] = c';  d_x [R,3] (always overwritten);  d_delta [N,12]: accumulate == 0 writes every row, rows of images
+ *     that no ray names as exact 0.0; accumulate != 0 adds to the rows that rays name and leaves the others untouched.
+ *   d_delta is reduced without float atomics: each product is rounded to float, then to 64-bit fixed point with 32 fractional
+ *   bits before grad_scale / 3R applies (resolution 2^-33 per product, unscaled sums below 2^31 in magnitude), every add from
+ *   there is an integer add, and one conversion ends it (in double, then float: one float rounding; an unscaled sum of 2^21 or
+ *   more rounds to a double's 53 bits first).  So d_delta, like loss_out and mse_out (double sums in a fixed
+ *   order), holds the same bits from call to call, and d_delta also under any permutation of the rays.
+ *   scratch: voxe_exposure_scratch_bytes(R, N) bytes of device memory (0 for shapes the call refuses), read and written when
+ *   R > 0 and any of loss_out / mse_out / d_delta is given; missing or short: VOXE_ERR_WORKSPACE.  Limits: 0 <= R < 2^31,
+ *   1 <= N < 2^24 (VOXE_ERR_BAD_SHAPE).  NULL delta, or NULL x / y / image_id with R > 0: VOXE_ERR_NULL_POINTER.  All validation
+ *   precedes any device work.  R == 0: loss_out and mse_out that exist are set to 0, d_delta to zeros unless accumulate, and
+ *   nothing else is touched.  All outputs NULL: VOXE_OK, nothing is launched.  Work is enqueued on `stream`.
+ *
+ * voxe_exposure_apply_bwd.  The chain rule of c' = A x + db alone, for a loss on the corrected colours formed outside this call
+ *   (the trainer's SSIM term): with d_corrected [R,3] = dL/dc', device, read only,
+ *       d_x_r = A^T d_corrected_r,   d_delta[n] = sum_{r: image_id[r] = n} (d_corrected_r x_r^T row-major, d_corrected_r)
+ *   x, image_id, delta, N, the clamp of image_id, d_x, d_delta, accumulate, scratch (voxe_exposure_scratch_bytes(R, N), used when
+ *   d_delta is given), limits, error codes and R == 0 as in voxe_exposure_fwd_bwd.  The fixed point's unit is 2^-33 / R',
+ *   R' = R rounded up to a power of two (the gradient of a mean over the batch has entries near 1 / R; sums below 2^31 / R').
+ *
+ * voxe_exposure_fit_sums.  x, y [N,P,3] float32 (N images of P pixels), device, read only.  sums [N,25] float64, device, per
+ *   image with u = (x_0, x_1, x_2, 1):  the 10 entries u_i u_j, i <= j, of sum u u^T in row-major order of the upper triangle
+ *   (the last one is P);  the 12 of sum u y^T, row-major [4,3];  the 3 of sum y o y.  Products and sums are formed in double, in
+ *   a fixed order: the same bits from call to call.  The host solves (sum u u^T) theta_c = (sum u y_c) per channel.
+ *   scratch: voxe_exposure_fit_scratch_bytes(N, P) bytes, always required (VOXE_ERR_WORKSPACE).  Limits: 1 <= N <= 65535,
+ *   1 <= P < 2^31 (VOXE_ERR_BAD_SHAPE).                                                                                        */
+size_t voxe_exposure_scratch_bytes(int64_t R, int64_t N);
+int voxe_exposure_fwd_bwd(const float* x, const float* y, const int32_t* image_id, int64_t R,
+                          const float* delta, int64_t N, int32_t kind,
+                          const float* ray_weight    /* [R] or NULL (= 1) */,
+                          float grad_scale,
+                          float* loss_out, float* mse_out, float* corrected, float* d_x, float* d_delta, int32_t accumulate,
+                          void* scratch, size_t scratch_bytes, void* stream);
+int voxe_exposure_apply_bwd(const float* x, const int32_t* image_id, int64_t R, const float* delta, int64_t N,
+                            const float* d_corrected, float* d_x, float* d_delta, int32_t accumulate,
+                            void* scratch, size_t scratch_bytes, void* stream);
+size_t voxe_exposure_fit_scratch_bytes(int64_t N, int64_t P);
+int voxe_exposure_fit_sums(const float* x, const float* y, int64_t N, int64_t P, double* sums,
+                           void* scratch, size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM of two image batches, value and gradient in one call (additive; still ABI v13), DESIGN.md section 4.18 "SSIM".  No
  * voxe_cpu_ twin; the float64 restatement is tests/ssim_ref.py.
  *   x, y: device float, channel-last [N,H,W,C], C in 1..4 (a render's colour viewed as patches or as an image).  Wang et al.

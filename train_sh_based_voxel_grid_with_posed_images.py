@@ -95,6 +95,12 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
                    "the viewer); 0 = off")
 @click.option("--orientation_normal_eps", type=click.FloatRange(min=0.0), default=1e-2, show_default=True,
               help="guard under the length of the density gradient in the orientation loss, in the gradient's units")
+@click.option("--exposure_learning_rate", type=click.FloatRange(min=0.0), default=0.0, show_default=True,
+              help="Adam rate of a learned 3x4 affine colour transform per training image (exposure / white-balance "
+                   "compensation, applied inside the loss only; needs RGB images); 0 = off")
+@click.option("--exposure_regularization", type=click.FloatRange(min=0.0), default=1e-3, show_default=True,
+              help="weight of mean(delta^2) on the per-image colour transforms: an untuned guard against the gauge that scene "
+                   "colour and one affine common to all images share (nobody has measured it)")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -135,7 +141,8 @@ def main(**kwargs) -> None:
         intrinsics_learning_rate=cfg.intrinsics_learning_rate, background_resolution=cfg.background_resolution,
         background_learning_rate=cfg.background_learning_rate, ssim_weight=cfg.ssim_weight, ssim_patch_size=cfg.ssim_patch_size,
         depth_weight=cfg.depth_weight, depth_ray_batch_size=cfg.depth_ray_batch_size, depth_sigma_scale=cfg.depth_sigma_scale,
-        orientation_weight=cfg.orientation_weight, orientation_normal_eps=cfg.orientation_normal_eps)
+        orientation_weight=cfg.orientation_weight, orientation_normal_eps=cfg.orientation_normal_eps,
+        exposure_learning_rate=cfg.exposure_learning_rate, exposure_regularization=cfg.exposure_regularization)
 
 
 if __name__ == "__main__":

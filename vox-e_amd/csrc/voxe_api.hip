@@ -1641,6 +1641,68 @@ int voxe_orientation_debug_lanes(int32_t lanes) {
   return VOXE_OK;
 }
 
+// ---- per-image exposure compensation ----------------------------------------------------------------------
+namespace {
+bool exposure_shape_ok(int64_t R, int64_t N) { return R >= 0 && R < (1LL << 31) && N >= 1 && N < (1LL << 24); }
+bool exposure_fit_shape_ok(int64_t N, int64_t P) { return N >= 1 && N <= 65535 && P >= 1 && P < (1LL << 31); }
+}  // namespace
+
+size_t voxe_exposure_scratch_bytes(int64_t R, int64_t N) { return exposure_shape_ok(R, N) ? exposure_scratch_bytes(R, N) : 0; }
+
+int voxe_exposure_fwd_bwd(const float* x, const float* y, const int32_t* image_id, int64_t R, const float* delta, int64_t N,
+                          int32_t kind, const float* ray_weight, float grad_scale, float* loss_out, float* mse_out,
+                          float* corrected, float* d_x, float* d_delta, int32_t accumulate, void* scratch, size_t scratch_bytes,
+                          void* stream) {
+  if (!delta || (R > 0 && (!x || !y || !image_id))) return VOXE_ERR_NULL_POINTER;
+  if (!exposure_shape_ok(R, N)) return VOXE_ERR_BAD_SHAPE;
+  if (kind != VOXE_DREG_L1 && kind != VOXE_DREG_L2) return VOXE_ERR_UNSUPPORTED;
+  const bool reduces = loss_out || mse_out || d_delta;
+  if (R > 0 && reduces && (!scratch || scratch_bytes < exposure_scratch_bytes(R, N))) return VOXE_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  if (R == 0) {
+    // outputs that exist are zeroed (d_delta unless it accumulates), nothing else is touched
+    if (loss_out && hipMemsetAsync(loss_out, 0, sizeof(float), s) != hipSuccess) return VOXE_ERR_LAUNCH;
+    if (mse_out && hipMemsetAsync(mse_out, 0, sizeof(float), s) != hipSuccess) return VOXE_ERR_LAUNCH;
+    if (d_delta && !accumulate && hipMemsetAsync(d_delta, 0, sizeof(float) * 12 * (size_t)N, s) != hipSuccess) return VOXE_ERR_LAUNCH;
+    return (loss_out || mse_out || (d_delta && !accumulate)) ? finish() : VOXE_OK;
+  }
+  if (!reduces && !corrected && !d_x) return VOXE_OK;
+  if (!launch_exposure(x, y, image_id, delta, ray_weight, R, (int)N, kind == VOXE_DREG_L1, grad_scale, loss_out, mse_out, corrected,
+                       d_x, d_delta, accumulate, scratch, s))
+    return VOXE_ERR_LAUNCH;
+  return finish();
+}
+
+int voxe_exposure_apply_bwd(const float* x, const int32_t* image_id, int64_t R, const float* delta, int64_t N,
+                            const float* d_corrected, float* d_x, float* d_delta, int32_t accumulate, void* scratch,
+                            size_t scratch_bytes, void* stream) {
+  if (!delta || (R > 0 && (!x || !image_id || !d_corrected))) return VOXE_ERR_NULL_POINTER;
+  if (!exposure_shape_ok(R, N)) return VOXE_ERR_BAD_SHAPE;
+  if (R > 0 && d_delta && (!scratch || scratch_bytes < exposure_scratch_bytes(R, N))) return VOXE_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  if (R == 0) {
+    if (!d_delta || accumulate) return VOXE_OK;
+    return hipMemsetAsync(d_delta, 0, sizeof(float) * 12 * (size_t)N, s) == hipSuccess ? finish() : VOXE_ERR_LAUNCH;
+  }
+  if (!d_x && !d_delta) return VOXE_OK;
+  if (!launch_exposure_apply_bwd(x, image_id, delta, d_corrected, R, (int)N, d_x, d_delta, accumulate, scratch, s))
+    return VOXE_ERR_LAUNCH;
+  return finish();
+}
+
+size_t voxe_exposure_fit_scratch_bytes(int64_t N, int64_t P) {
+  return exposure_fit_shape_ok(N, P) ? exposure_fit_scratch_bytes(N, P) : 0;
+}
+
+int voxe_exposure_fit_sums(const float* x, const float* y, int64_t N, int64_t P, double* sums, void* scratch, size_t scratch_bytes,
+                           void* stream) {
+  if (!x || !y || !sums) return VOXE_ERR_NULL_POINTER;
+  if (!exposure_fit_shape_ok(N, P)) return VOXE_ERR_BAD_SHAPE;
+  if (!scratch || scratch_bytes < exposure_fit_scratch_bytes(N, P)) return VOXE_ERR_WORKSPACE;
+  launch_exposure_fit(x, y, N, P, sums, scratch, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- SSIM of channel-last images --------------------------------------------------------------------------
 namespace {
 bool ssim_shape_ok(int32_t N, int32_t H, int32_t W, int32_t C) { return N >= 1 && H >= 11 && W >= 11 && C >= 1 && C <= 4; }

@@ -264,6 +264,18 @@ void launch_orientation(const DevGrid& g, const DevCfg& c, const float* dens, co
                         const float* jitter, const float* ray_weight, float normal_eps, float grad_scale, float* loss_out,
                         float* ray_loss, float* d_dens, void* scratch, hipStream_t st);
 
+// voxe_exposure.hip: per-image affine colour transform: the photometric loss under it with the gradients to
+// the colours and to the parameters (64-bit fixed-point segmented reduction, no float atomics), and the least-squares sums of
+// the colour-corrected metrics; no grid.  launch_exposure: false when the scratch could not be cleared
+size_t exposure_scratch_bytes(long long R, long long N);
+size_t exposure_fit_scratch_bytes(long long N, long long P);
+bool launch_exposure(const float* x, const float* y, const int* ids, const float* delta, const float* rweight, long long R, int N,
+                     bool l1, float grad_scale, float* loss_out, float* mse_out, float* corrected, float* d_x, float* d_delta,
+                     int accumulate, void* scratch, hipStream_t st);
+bool launch_exposure_apply_bwd(const float* x, const int* ids, const float* delta, const float* d_corrected, long long R, int N,
+                               float* d_x, float* d_delta, int accumulate, void* scratch, hipStream_t st);
+void launch_exposure_fit(const float* x, const float* y, long long N, long long P, double* sums, void* scratch, hipStream_t st);
+
 // voxe_render_rays_bwd.hip: gradient of a render w.r.t. its rays; reads the raw densities and features, no
 // workspace, no atomics
 extern thread_local int tl_rays_bwd_lanes;   // test aid (voxe_render_bwd_rays_debug_lanes): != 0 pins the lanes per ray

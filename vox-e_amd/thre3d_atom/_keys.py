@@ -35,6 +35,8 @@ CHECKPOINT_KEYS = {
     "HEMISPHERICAL_RADIUS": "hemispherical_radius",
     # optional (not in the reference): the environment-map background {state_dict, config_dict}, only when the model has one
     "BACKGROUND": "background",
+    # optional (not in the reference): the per-image exposure compensation {state_dict, config_dict}, only when the model has one
+    "EXPOSURE": "exposure",
 }
 STATE_DICT_NAMES = {"u_DENSITIES": "_densities", "u_FEATURES": "_features", "u_ATTN": "attn"}
 

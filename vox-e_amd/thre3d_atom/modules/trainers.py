@@ -22,6 +22,7 @@ from thre3d_atom.rendering.volumetric.utils.misc import (_cast_and_gather, is_ge
                                                           sample_random_rays_and_pixels_from_cameras)
 from thre3d_atom.thre3d_reprs.background import EnvMapBackground
 from thre3d_atom.thre3d_reprs.depth import depth_targets_on_rays
+from thre3d_atom.thre3d_reprs.exposure import PerImageExposure
 from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, LearnedIntrinsics, write_camera_params
 from thre3d_atom.thre3d_reprs.renderers import _render_params, render_sh_voxel_grid
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid, scale_voxel_grid_with_required_output_size
@@ -157,6 +158,14 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     orientation_normal_eps: float = 1e-2,   # the guard under the normal's length, in the units of the density gradient.  A guard,
                                             # not a tuned value: about 2e-4 of a unit density step across one voxel of a 160^3
                                             # grid over [-1.5, 1.5]
+    exposure_learning_rate: float = 0.0,    # addition of this build: > 0 learns a 3 x 4 affine colour transform per training image
+                                            # with the scene (thre3d_reprs/exposure.py): one PerImageExposure over
+                                            # all training images, shared across the stages, stepped by its own Adam at this rate
+                                            # and saved with the checkpoints; the L1 terms (and the SSIM term) see the transformed
+                                            # render.  0 = off, nothing changes.  Above 0 the iteration is not the one-call one
+                                            # either, and the images must have 3 channels
+    exposure_regularization: float = 1e-3,  # weight of mean(delta^2) on the transforms: a guard against the gauge that scene
+                                            # colour and one affine common to all images share.  Untuned: nobody has measured it
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
@@ -171,6 +180,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     if orientation_weight < 0.0 or not (0.0 <= orientation_normal_eps < float("inf")):
         raise ValueError(f"orientation_weight must not be negative and orientation_normal_eps finite and not negative; got "
                          f"{orientation_weight} and {orientation_normal_eps}")
+    if exposure_learning_rate < 0.0 or exposure_regularization < 0.0:
+        raise ValueError(f"exposure_learning_rate and exposure_regularization must not be negative; got {exposure_learning_rate} "
+                         f"and {exposure_regularization}")
     if depth_weight > 0.0 and getattr(train_dataset, "sparse_points", None) is None:
         from thre3d_atom.data.datasets import SPARSE_POINTS_SUFFIX, sparse_points_path
 
@@ -195,6 +207,16 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
 
     grid_sizes = compute_thre3d_grid_sizes(vol_mod.thre3d_repr.grid_dims, num_stages, scale_factor)
     stage_datasets = [train_dataset.downsampled(scale_factor ** (num_stages - 1 - s)).to(device) for s in range(num_stages)]
+
+    exposure_optimizer = None
+    if exposure_learning_rate > 0.0:
+        if stage_datasets[0].images.shape[1] != 3:
+            raise ValueError(f"exposure_learning_rate > 0 needs images of 3 channels (the transform is 3 x 4); got "
+                             f"{stage_datasets[0].images.shape[1]}")
+        vol_mod.exposure = PerImageExposure(len(train_dataset)).requires_grad_(True)
+        # (once per dataset, not per call: a batch's image ids are drawn from these indices, and the kernel clamps)
+        vol_mod.exposure.check_image_ids(torch.arange(len(train_dataset)))
+        exposure_optimizer = torch.optim.Adam(vol_mod.exposure.parameters(), lr=exposure_learning_rate)
 
     with torch.no_grad():
         vol_mod.thre3d_repr = scale_voxel_grid_with_required_output_size(vol_mod.thre3d_repr, grid_sizes[0])
@@ -287,6 +309,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
             if one_call and stage == 1:
                 log.info("orientation_weight > 0: the iterations render, add the term and step separately (no one-call iteration)")
             one_call = False
+        if exposure_optimizer is not None:
+            if one_call and stage == 1:
+                log.info("exposure_learning_rate > 0: the iterations render, take the losses under the per-image colour transforms "
+                         "and step separately (no one-call iteration)")
+            one_call = False
         patch = 0   # side of this stage's SSIM patches; 0: the term is off and the batch is the random pixel set
         if ssim_weight > 0.0:
             if one_call and stage == 1:
@@ -349,22 +376,33 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         poses_batch, refine = pose_deltas.apply(poses_batch, picks), {"differentiable": True}
                         if learned_intrinsics is not None:
                             refine["intrinsics"] = learned_intrinsics.values / stage_factor
+                    exposed = exposure_optimizer is not None
                     if patch:
                         num_patches = ray_batch_size // (patch * patch)
-                        rays_batch, pixels_batch = sample_random_patches_and_pixels_from_cameras(
-                            intr, poses_batch, data.images, num_patches, patch, image_ids=picks, **refine)
+                        rays_batch, pixels_batch, *ids_batch = sample_random_patches_and_pixels_from_cameras(
+                            intr, poses_batch, data.images, num_patches, patch, image_ids=picks, **refine, return_image_ids=exposed)
                     else:
-                        rays_batch, pixels_batch = sample_random_rays_and_pixels_from_cameras(
+                        rays_batch, pixels_batch, *ids_batch = sample_random_rays_and_pixels_from_cameras(
                             intr, poses_batch, data.images, ray_batch_size, image_ids=picks, **refine,
                             # (sorting the batch by (camera, row, column) helps the ray-ordered gather of small batches; batches of
                             #  16384+ rays take the space-binned render, which does not care about the order: skip the sort)
-                            memory_order=ray_batch_size < 16384, fast_subset=True)
+                            memory_order=ray_batch_size < 16384, fast_subset=True, return_image_ids=exposed)
                     specular = vol_mod.render_rays(rays_batch).colour
-                    loss = torch.nn.functional.l1_loss(specular, pixels_batch)
-                    psnr = mse2psnr(torch.nn.functional.mse_loss(specular.detach(), pixels_batch))
+                    if exposed:
+                        # (value, mse and both gradients of the L1 under each ray's image transform in one call)
+                        loss, mse = vol_mod.exposure(specular, pixels_batch, ids_batch[0])
+                        psnr = mse2psnr(mse)
+                    else:
+                        loss = torch.nn.functional.l1_loss(specular, pixels_batch)
+                        psnr = mse2psnr(torch.nn.functional.mse_loss(specular.detach(), pixels_batch))
                     if apply_diffuse_render_regularization:
                         diffuse = vol_mod.render_rays(rays_batch, render_diffuse=True).colour
-                        loss = loss + torch.nn.functional.l1_loss(diffuse, pixels_batch)
+                        if exposed:
+                            loss = loss + vol_mod.exposure(diffuse, pixels_batch, ids_batch[0])[0]
+                        else:
+                            loss = loss + torch.nn.functional.l1_loss(diffuse, pixels_batch)
+                    if exposed and exposure_regularization > 0.0:
+                        loss = loss + exposure_regularization * vol_mod.exposure.regulariser()
                     if distortion_weight > 0.0:
                         # (under FusedGridAdam the renders' gradient stays in the workspace and this term's arrives as
                         #  densities.grad, which step() adds; under VoxeAdam plain autograd sums both)
@@ -387,19 +425,25 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                     if patch:
                         # (the batch is patch-major, row, column: the render's colour viewed as channel-last patches)
                         shape = (num_patches, patch, patch, specular.shape[-1])
-                        ssim, _ = _ops.ssim(specular.view(shape), pixels_batch.contiguous().view(shape))
+                        # (under exposure compensation the term sees the transformed colours, like the L1 terms)
+                        seen = _ops.exposure_apply(specular, ids_batch[0], vol_mod.exposure.delta) if exposed else specular
+                        ssim, _ = _ops.ssim(seen.view(shape), pixels_batch.contiguous().view(shape))
                         loss = loss + ssim_weight * (1.0 - ssim)
                     optimizer.zero_grad()
                     if pose_optimizer is not None:
                         pose_optimizer.zero_grad()
                     if background_optimizer is not None:
                         background_optimizer.zero_grad()
+                    if exposure_optimizer is not None:
+                        exposure_optimizer.zero_grad()
                     loss.backward()
                     optimizer.step()
                     if pose_optimizer is not None:
                         pose_optimizer.step()
                     if background_optimizer is not None:
                         background_optimizer.step()
+                    if exposure_optimizer is not None:
+                        exposure_optimizer.step()
                 global_step += 1
                 trained += time.perf_counter() - t0
                 if global_step % summary_freq == 0 or it in (1, num_iterations_per_stage):

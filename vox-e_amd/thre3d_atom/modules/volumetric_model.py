@@ -24,6 +24,7 @@ from thre3d_atom.rendering.volumetric.utils.misc import (
 from thre3d_atom.thre3d_reprs.constants import (
     BACKGROUND,
     CONFIG_DICT,
+    EXPOSURE,
     RENDER_CONFIG,
     RENDER_CONFIG_TYPE,
     RENDER_PROCEDURE,
@@ -52,6 +53,18 @@ class VolumetricModel:
         self._device = device
         self._background = None
         self.background = background
+        self._exposure = None   # (set through the property: the trainer and the checkpoint loader do)
+
+    @property
+    def exposure(self) -> Optional[Module]:
+        """the per-image affine colour transforms of the training images (thre3d_reprs.exposure.PerImageExposure; None: the
+        model has none).  It belongs to the photometric loss of the training images, not to the scene: renders are never altered
+        by it"""
+        return self._exposure
+
+    @exposure.setter
+    def exposure(self, exposure: Optional[Module]) -> None:
+        self._exposure = None if exposure is None else exposure.to(self._device)
 
     @property
     def background(self) -> Optional[Module]:
@@ -109,6 +122,11 @@ class VolumetricModel:
             save_info[BACKGROUND] = {
                 STATE_DICT: self._background.state_dict(),
                 CONFIG_DICT: self._background.get_save_config_dict(),
+            }
+        if self._exposure is not None:
+            save_info[EXPOSURE] = {
+                STATE_DICT: self._exposure.state_dict(),
+                CONFIG_DICT: self._exposure.get_save_config_dict(),
             }
         if extra_info is not None:
             save_info[EXTRA_INFO] = extra_info
@@ -222,6 +240,7 @@ def _load_model(model_path: Path, make_repr, device) -> Tuple[VolumetricModel, D
         device=device,
         background=_load_background(model_data),
     )
+    model.exposure = _load_exposure(model_data)
     return model, model_data.get(EXTRA_INFO)
 
 
@@ -234,6 +253,17 @@ def _load_background(model_data: Dict[str, Any]) -> Optional[Module]:
     background = EnvMapBackground(**model_data[BACKGROUND][CONFIG_DICT])
     background.load_state_dict(model_data[BACKGROUND][STATE_DICT])
     return background.requires_grad_(False)
+
+
+def _load_exposure(model_data: Dict[str, Any]) -> Optional[Module]:
+    """the checkpoint's per-image exposure compensation, frozen (None: the checkpoint has none -- every reference checkpoint)"""
+    if EXPOSURE not in model_data:
+        return None
+    from thre3d_atom.thre3d_reprs.exposure import PerImageExposure
+
+    exposure = PerImageExposure(**model_data[EXPOSURE][CONFIG_DICT])
+    exposure.load_state_dict(model_data[EXPOSURE][STATE_DICT])
+    return exposure.requires_grad_(False)
 
 
 def create_volumetric_model_from_saved_model(

@@ -85,7 +85,8 @@ def sample_random_rays_and_pixels_synchronously(rays: Rays, pixels: Tensor, samp
 def sample_random_rays_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsics, poses: Tensor, images: Tensor,
                                                sample_size: int, image_ids: Any = None,
                                                memory_order: bool = False, fast_subset: bool = False,
-                                               differentiable: bool = False, intrinsics: Any = None) -> Tuple[Rays, Tensor]:
+                                               differentiable: bool = False, intrinsics: Any = None,
+                                               return_image_ids: bool = False) -> Tuple[Rays, Tensor]:
     """What the reconstruction loop keeps of `cast_rays` per camera -> `collate_rays` -> pixel concat ->
     `sample_random_rays_and_pixels_synchronously` (modules/trainers.py:290-313), computed for the selected pixels
     only: the same `randperm` draw picks flat (camera, y, x) indices, the HIP kernel casts just those rays and the
@@ -98,7 +99,8 @@ def sample_random_rays_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsi
     pixels; 0.02 ms instead of 0.20 ms for `randperm` over 1.28 M pixels) -- a different random stream than torch's.
     `differentiable=True` casts the same rays (bit for bit) through cast_rays_from_poses: they carry gradients back to `poses`.
     A general camera (is_general_camera) casts through cast_rays_camera / cast_rays_from_camera; `intrinsics` (tensor [4] fx fy cx
-    cy, differentiable only) then replaces the camera's own and receives a gradient."""
+    cy, differentiable only) then replaces the camera's own and receives a gradient.  `return_image_ids=True` returns a third
+    value: the row of `images` each ray's pixel came from ([R] int32; with `image_ids` that is the caller's id of the camera)."""
     height, width, focal = camera_intrinsics
     K = int(poses.shape[0])
     per = int(height) * int(width)
@@ -108,12 +110,14 @@ def sample_random_rays_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsi
         subset = torch.randperm(K * per, dtype=torch.long, device=images.device)[:sample_size]
     if memory_order:
         subset = torch.sort(subset).values
-    return _cast_and_gather(camera_intrinsics, poses, images, subset, image_ids, differentiable, intrinsics)
+    return _cast_and_gather(camera_intrinsics, poses, images, subset, image_ids, differentiable, intrinsics,
+                            **({"return_image_ids": True} if return_image_ids else {}))
 
 
 def _cast_and_gather(camera_intrinsics: CameraIntrinsics, poses: Tensor, images: Tensor, flat_index: Tensor, image_ids: Any,
-                     differentiable: bool, intrinsics: Any) -> Tuple[Rays, Tensor]:
-    """rays and target pixels of flat (camera, row, column) indices: the cast branches and the gather the samplers share"""
+                     differentiable: bool, intrinsics: Any, return_image_ids: bool = False):
+    """rays and target pixels of flat (camera, row, column) indices: the cast branches and the gather the samplers share; with
+    `return_image_ids` also each ray's row of `images` as int32"""
     height, width, focal = camera_intrinsics
     per = int(height) * int(width)
     if intrinsics is not None or is_general_camera(camera_intrinsics):
@@ -128,6 +132,8 @@ def _cast_and_gather(camera_intrinsics: CameraIntrinsics, poses: Tensor, images:
     rem = flat_index - cam * per
     rows = cam if image_ids is None else torch.as_tensor(image_ids, device=images.device, dtype=torch.long)[cam]
     pixels = images[rows, :, torch.div(rem, int(width), rounding_mode="floor"), rem % int(width)]
+    if return_image_ids:
+        return Rays(origins, directions), pixels, rows.to(torch.int32)
     return Rays(origins, directions), pixels
 
 
@@ -143,12 +149,13 @@ def patch_flat_indices(cameras: Tensor, top: Tensor, left: Tensor, patch_size: i
 
 def sample_random_patches_and_pixels_from_cameras(camera_intrinsics: CameraIntrinsics, poses: Tensor, images: Tensor,
                                                   num_patches: int, patch_size: int, image_ids: Any = None,
-                                                  differentiable: bool = False, intrinsics: Any = None) -> Tuple[Rays, Tensor]:
+                                                  differentiable: bool = False, intrinsics: Any = None,
+                                                  return_image_ids: bool = False) -> Tuple[Rays, Tensor]:
     """`num_patches` square patches of `patch_size` pixels a side for a loss that sees neighbourhoods (SSIM): each patch has a
     uniformly random camera among the K of `poses` and a uniformly random top-left corner in [0, H-P] x [0, W-P]; the flat
     indices are built on the device.  Rays and pixels come back flat, [num_patches * P * P, ...], in patch-major, row, column
-    order, so `.view(num_patches, P, P, C)` is the channel-last patch batch.  Casting, `image_ids`, `differentiable` and
-    `intrinsics` are those of sample_random_rays_and_pixels_from_cameras."""
+    order, so `.view(num_patches, P, P, C)` is the channel-last patch batch.  Casting, `image_ids`, `differentiable`,
+    `intrinsics` and `return_image_ids` are those of sample_random_rays_and_pixels_from_cameras."""
     height, width, _ = camera_intrinsics
     height, width, P, n = int(height), int(width), int(patch_size), int(num_patches)
     if not 1 <= P <= min(height, width) or n < 1:
@@ -158,7 +165,8 @@ def sample_random_patches_and_pixels_from_cameras(camera_intrinsics: CameraIntri
     top = torch.randint(0, height - P + 1, (n,), device=device)
     left = torch.randint(0, width - P + 1, (n,), device=device)
     flat_index = patch_flat_indices(cameras, top, left, P, height, width)
-    return _cast_and_gather(camera_intrinsics, poses, images, flat_index, image_ids, differentiable, intrinsics)
+    return _cast_and_gather(camera_intrinsics, poses, images, flat_index, image_ids, differentiable, intrinsics,
+                            **({"return_image_ids": True} if return_image_ids else {}))
 
 
 def sample_rays_and_pixels_synchronously(rays: Rays, pixels: Tensor, indices: Any, sample_size: int):

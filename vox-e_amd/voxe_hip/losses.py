@@ -1,5 +1,5 @@
 """Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss, the depth
-supervision and the orientation loss on rays, SSIM) and Adam on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
+supervision and the orientation loss on rays, the per-image exposure compensation, SSIM) and Adam on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
 import ctypes as C
 from typing import Optional, Tuple
 
@@ -354,6 +354,220 @@ def orientation_loss(spec: GridSpec, params: RenderParams, densities: torch.Tens
     rng = resolve_rng(params, jitter, rng)
     return _OrientationFn.apply(densities, spec, params, rays_o, rays_d, ray_weight, jitter, rng, float(normal_eps),
                                 bool(return_ray_loss), int(_lanes))
+
+
+# ------------------------------------------------------------------------------------------------
+# per-image exposure compensation: no grid, no workspace; differentiable w.r.t. the colours and the
+# parameters
+# ------------------------------------------------------------------------------------------------
+_EXPOSURE_KINDS = {"l1": abi.DREG_L1, "l2": abi.DREG_L2}
+EXPOSURE_FIT_SUMS = 25
+
+
+def _exposure_inputs(entry: str, colour: torch.Tensor, target: Optional[torch.Tensor], image_ids: torch.Tensor, delta: torch.Tensor):
+    """(x [R,3], y [R,3] or None, ids [R] int32, delta [N,12]) as dense tensors on the colours' device"""
+    require_device(colour, f"{entry} (colour)")
+    device = colour.device
+    if colour.dim() != 2 or colour.shape[1] != 3:
+        raise VoxeError(f"{entry}: colour must be [R,3]; got {tuple(colour.shape)}")
+    R = colour.shape[0]
+    if target is not None and (target.shape != colour.shape or target.device != device):
+        raise VoxeError(f"{entry}: target must be {tuple(colour.shape)} on {device}; got {tuple(target.shape)} on {target.device}")
+    if image_ids.dtype not in (torch.int32, torch.int64) or image_ids.numel() != R or image_ids.device != device:
+        raise VoxeError(f"{entry}: image_ids must hold one integer per ray ({R}) on {device}; got {image_ids.dtype} "
+                        f"{tuple(image_ids.shape)} on {image_ids.device}")
+    if delta.dim() != 2 or delta.shape[1] != 12 or delta.shape[0] < 1 or delta.device != device:
+        raise VoxeError(f"{entry}: delta must be [N,12], N >= 1, on {device}; got {tuple(delta.shape)} on {delta.device}")
+    ids = image_ids.detach().reshape(R).to(torch.int32).contiguous()
+    return f32c(colour.detach()), (None if target is None else f32c(target.detach())), ids, f32c(delta.detach())
+
+
+def exposure_fwd_bwd(colour: torch.Tensor, target: torch.Tensor, image_ids: torch.Tensor, delta: torch.Tensor, kind: str = "l1",
+                     ray_weight: Optional[torch.Tensor] = None, grad_scale: float = 1.0, want_loss: bool = True,
+                     want_mse: bool = False, want_corrected: bool = False, d_colour: Optional[torch.Tensor] = None,
+                     d_delta: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """voxe_exposure_fwd_bwd as it stands: (loss [] or None, mse [] or None, corrected [R,3] or None); `d_colour` (contiguous
+    float32 [R,3], or None) receives grad_scale * dloss/dcolour, `d_delta` (contiguous float32 [N,12], or None)
+    grad_scale * dloss/ddelta, added to its contents when `accumulate`.  image_ids outside [0, N) are clamped on the device:
+    check a dataset's ids once, not per call."""
+    if kind not in _EXPOSURE_KINDS:
+        raise VoxeError(f"exposure_loss: kind must be 'l1' or 'l2'; got {kind!r}")
+    x, y, ids, dl = _exposure_inputs("exposure_loss", colour, target, image_ids, delta)
+    device = x.device
+    R, N = x.shape[0], dl.shape[0]
+    if d_colour is not None:
+        _require_buffer("exposure_loss", "d_colour", d_colour, shape=x.shape, device=device)
+    if d_delta is not None:
+        _require_buffer("exposure_loss", "d_delta", d_delta, shape=dl.shape, device=device)
+    rw = _per_ray("exposure_loss", "ray_weight", ray_weight, R, device)
+    ensure_gfx950(device)
+    L = lib()
+    with torch.cuda.device(device):
+        loss = torch.empty((), dtype=torch.float32, device=device) if want_loss else None
+        mse = torch.empty((), dtype=torch.float32, device=device) if want_mse else None
+        corrected = torch.empty((R, 3), dtype=torch.float32, device=device) if want_corrected else None
+        sc = _scratch_for(device, L.voxe_exposure_scratch_bytes(R, N)) if (want_loss or want_mse or d_delta is not None) else None
+        check(L.voxe_exposure_fwd_bwd(ptr(x), ptr(y), ptr(ids), R, ptr(dl), N, _EXPOSURE_KINDS[kind], ptr(rw), float(grad_scale),
+                                      ptr(loss), ptr(mse), ptr(corrected), ptr(d_colour), ptr(d_delta), 1 if accumulate else 0,
+                                      ptr(sc), sc.numel() if sc is not None else 0, stream_ptr(device)),
+              "voxe_exposure_fwd_bwd")
+    wrote(d_colour)
+    wrote(d_delta)
+    return loss, mse, corrected
+
+
+class _ExposureFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colour, delta, target, image_ids, kind, ray_weight, return_corrected):
+        d_c = torch.empty_like(f32c(colour.detach())) if ctx.needs_input_grad[0] else None
+        d_d = torch.empty_like(f32c(delta.detach())) if ctx.needs_input_grad[1] else None
+        loss, mse, corrected = exposure_fwd_bwd(colour, target, image_ids, delta, kind, ray_weight, want_mse=True,
+                                                want_corrected=return_corrected, d_colour=d_c, d_delta=d_d)
+        ctx.save_for_backward(d_c, d_d)
+        if return_corrected:
+            ctx.mark_non_differentiable(mse, corrected)
+            return loss, mse, corrected
+        ctx.mark_non_differentiable(mse)
+        return loss, mse
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        d_c, d_d = ctx.saved_tensors
+        return (None if d_c is None else d_c * g, None if d_d is None else d_d * g) + (None,) * 5
+
+
+def exposure_loss(colour: torch.Tensor, target: torch.Tensor, image_ids: torch.Tensor, delta: torch.Tensor, kind: str = "l1",
+                  ray_weight: Optional[torch.Tensor] = None, return_corrected: bool = False):
+    """Photometric loss under a per-image affine colour transform: with A = I + dA_n, c' = A colour + db_n for the image
+    n = image_ids[r] of ray r and delta[n] = (dA row-major, db), the mean over the 3R elements of omega_r |c' - target| ('l1',
+    sign(0) = 0 like torch's l1_loss) or omega_r (c' - target)^2 ('l2').  Returns (loss [], mse []), with return_corrected
+    (loss, mse, corrected [R,3]): `loss` is differentiable w.r.t. `colour` and `delta` (both gradients are computed in the forward,
+    each only when its input requires one; d_delta is a fixed-point segmented reduction, bit-reproducible); `mse`, the plain mean
+    of (c' - target)^2 for a PSNR line, and `corrected` are not.  target, image_ids and ray_weight (omega >= 0, None = 1) receive
+    no gradient.  image_ids (int32 or int64, [R]) outside [0, N) are clamped on the device."""
+    for name, t in (("target", target), ("image_ids", image_ids), ("ray_weight", ray_weight)):
+        if t is not None and t.requires_grad:
+            raise VoxeError(f"exposure_loss: {name} receives no gradient; detach it")
+    if kind not in _EXPOSURE_KINDS:
+        raise VoxeError(f"exposure_loss: kind must be 'l1' or 'l2'; got {kind!r}")
+    _exposure_inputs("exposure_loss", colour, target, image_ids, delta)
+    return _ExposureFn.apply(colour, delta, target, image_ids, kind, ray_weight, bool(return_corrected))
+
+
+def exposure_apply_bwd(colour: torch.Tensor, image_ids: torch.Tensor, delta: torch.Tensor, d_corrected: torch.Tensor,
+                       d_colour: Optional[torch.Tensor] = None, d_delta: Optional[torch.Tensor] = None,
+                       accumulate: bool = False) -> None:
+    """voxe_exposure_apply_bwd as it stands: `d_colour` [R,3] receives A^T d_corrected, `d_delta` [N,12] the per-image sums of
+    (d_corrected x^T, d_corrected), added to its contents when `accumulate`.  Range of the fixed point: see exposure_apply."""
+    x, g, ids, dl = _exposure_inputs("exposure_apply", colour, d_corrected, image_ids, delta)
+    device = x.device
+    R, N = x.shape[0], dl.shape[0]
+    if d_colour is not None:
+        _require_buffer("exposure_apply", "d_colour", d_colour, shape=x.shape, device=device)
+    if d_delta is not None:
+        _require_buffer("exposure_apply", "d_delta", d_delta, shape=dl.shape, device=device)
+    ensure_gfx950(device)
+    L = lib()
+    with torch.cuda.device(device):
+        sc = _scratch_for(device, L.voxe_exposure_scratch_bytes(R, N)) if d_delta is not None else None
+        check(L.voxe_exposure_apply_bwd(ptr(x), ptr(ids), R, ptr(dl), N, ptr(g), ptr(d_colour), ptr(d_delta), 1 if accumulate else 0,
+                                        ptr(sc), sc.numel() if sc is not None else 0, stream_ptr(device)), "voxe_exposure_apply_bwd")
+    wrote(d_colour)
+    wrote(d_delta)
+
+
+class _ExposureApplyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colour, delta, image_ids):
+        x, _, ids, dl = _exposure_inputs("exposure_apply", colour, None, image_ids, delta)
+        device = x.device
+        ensure_gfx950(device)
+        R = x.shape[0]
+        with torch.cuda.device(device):
+            corrected = torch.empty((R, 3), dtype=torch.float32, device=device)
+            # (the target is read for the residual only; with every reduction skipped the colours stand in for it)
+            check(lib().voxe_exposure_fwd_bwd(ptr(x), ptr(x), ptr(ids), R, ptr(dl), dl.shape[0], abi.DREG_L2, None, 1.0, None, None,
+                                              ptr(corrected), None, None, 0, None, 0, stream_ptr(device)), "voxe_exposure_fwd_bwd")
+        ctx.save_for_backward(x, dl, ids)
+        return corrected
+
+    @staticmethod
+    def backward(ctx, g):
+        x, dl, ids = ctx.saved_tensors
+        d_c = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        d_d = torch.empty_like(dl) if ctx.needs_input_grad[1] else None
+        if d_c is not None or d_d is not None:
+            exposure_apply_bwd(x, ids, dl, g, d_colour=d_c, d_delta=d_d)
+        return d_c, d_d, None
+
+
+def exposure_apply(colour: torch.Tensor, image_ids: torch.Tensor, delta: torch.Tensor) -> torch.Tensor:
+    """c' = (I + dA_n) colour + db_n per ray, n = image_ids[r]: the `corrected` output of voxe_exposure_fwd_bwd alone, [R,3],
+    for a loss that sees the corrected colours themselves (the trainer's SSIM term); differentiable w.r.t. `colour` and `delta`
+    (voxe_exposure_apply_bwd, the same fixed-point reduction).  The backward's fixed point assumes the upstream gradient of a
+    mean over the batch, entries near 1 / R: per image the sums of |dL/dc'| and of |dL/dc' x| must stay below 2^31 / R',
+    R' = R rounded up to a power of two, or d_delta wraps -- a loss summed, not averaged, over 2^20 rays and more does not fit,
+    and entries below 2^-33 / R' are lost."""
+    if image_ids.requires_grad:
+        raise VoxeError("exposure_apply: image_ids receives no gradient")
+    _exposure_inputs("exposure_apply", colour, None, image_ids, delta)
+    return _ExposureApplyFn.apply(colour, delta, image_ids)
+
+
+def exposure_fit_sums(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """voxe_exposure_fit_sums as it stands: x, y [N,P,3] float32 -> sums [N,25] float64 (include/voxe.h names the 25)"""
+    for name, t in (("x", x), ("y", y)):
+        require_device(t, f"fit_affine_colour ({name})")
+    if x.dim() != 3 or x.shape[2] != 3 or x.shape[0] < 1 or x.shape[1] < 1 or x.shape != y.shape or x.device != y.device:
+        raise VoxeError(f"fit_affine_colour: x and y must be [N,P,3] of one shape on one device, N, P >= 1; got {tuple(x.shape)} "
+                        f"and {tuple(y.shape)}")
+    device = x.device
+    ensure_gfx950(device)
+    xd, yd = f32c(x.detach()), f32c(y.detach())
+    N, P = int(x.shape[0]), int(x.shape[1])
+    L = lib()
+    with torch.cuda.device(device):
+        sums = torch.empty((N, EXPOSURE_FIT_SUMS), dtype=torch.float64, device=device)
+        need = L.voxe_exposure_fit_scratch_bytes(N, P)
+        if need == 0:
+            raise VoxeError(f"fit_affine_colour: {tuple(x.shape)} is outside the limits of voxe_exposure_fit_sums")
+        sc = _scratch_for(device, need)
+        check(L.voxe_exposure_fit_sums(ptr(xd), ptr(yd), N, P, ptr(sums), ptr(sc), sc.numel(), stream_ptr(device)),
+              "voxe_exposure_fit_sums")
+    return sums
+
+
+_FIT_UPPER = ((0, 0), (0, 1), (0, 2), (0, 3), (1, 1), (1, 2), (1, 3), (2, 2), (2, 3), (3, 3))
+FIT_RIDGE = 1e-11   # relative to the largest eigenvalue of an image's 4 x 4 system
+
+
+def solve_affine_colour(sums: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(A [N,3,3], b [N,3]) in float64 on the CPU from sums [N,25]: per image the least-squares affine y ~ A x + b.  The 4 x 4
+    system is solved through its eigenvalues w_i as w_i / (w_i^2 + (FIT_RIDGE w_max)^2): a ridge that changes a well-posed image
+    by (FIT_RIDGE cond)^2, below rounding up to cond 1e4, and keeps a degenerate one (constant colour, P < 4) finite, at the
+    solution of least norm."""
+    s = sums.detach().to("cpu", torch.float64)
+    N = s.shape[0]
+    G = torch.zeros((N, 4, 4), dtype=torch.float64)
+    for k, (i, j) in enumerate(_FIT_UPPER):
+        G[:, i, j] = s[:, k]
+        G[:, j, i] = s[:, k]
+    h = s[:, 10:22].reshape(N, 4, 3)
+    w, V = torch.linalg.eigh(G)
+    lam = FIT_RIDGE * w[:, -1:].clamp_min(torch.finfo(torch.float64).tiny)
+    inv = w / (w * w + lam * lam)
+    theta = V @ (inv.unsqueeze(-1) * (V.transpose(1, 2) @ h))   # [N,4,3]: rows A^T then b
+    return theta[:, :3, :].transpose(1, 2).contiguous(), theta[:, 3, :].contiguous()
+
+
+def fit_affine_colour(x: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The least-squares affine colour transform of each image, y ~ A x + b over its P pixels (the colour correction of
+    mip-NeRF 360's and RawNeRF's colour-corrected metrics): x, y [N,P,3] float32 on the device -> (A [N,3,3], b [N,3]) float64 on
+    the device.  The sums are formed on the device in double (voxe_exposure_fit_sums, bit-reproducible), the 4 x 4 systems are
+    solved on the host in float64 (solve_affine_colour); no gradient."""
+    sums = exposure_fit_sums(x, y)
+    A, b = solve_affine_colour(sums)
+    return A.to(x.device), b.to(x.device)
 
 
 # ------------------------------------------------------------------------------------------------
