@@ -930,6 +930,54 @@ int voxe_exposure_fit_sums(const float* x, const float* y, int64_t N, int64_t P,
                            void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Robust photometric loss on pixel patches (additive; still ABI v13), DESIGN.md section 4.22 "Robust loss".  RobustNeRF's
+ * (Sabour et al. 2023) trimmed loss for captures with transient objects: a pixel is an outlier when its residual is above an
+ * order statistic of the batch's residuals, an outlier is forgiven when its 3x3 neighbourhood or its patch is mostly inliers,
+ * and the mask is a constant of the loss.  No grid, no workspace, no voxe_cpu_ twin; the restatement is tests/robust_ref.py.
+ *
+ * Inputs, device, read only: x, y [N,P,P,C] float32, channel-last (x a render's colour viewed as patches, y the photographs).
+ *   Limits: N >= 1, P even, 4 <= P <= 64, C in 1..4, M = N P^2 < 2^31 (VOXE_ERR_BAD_SHAPE).  kind: VOXE_DREG_L1 or VOXE_DREG_L2
+ *   (VOXE_ERR_UNSUPPORTED otherwise).  Integer parameters, so that no float comparison of the host decides a mask bit:
+ *       rank       0 <= rank < M           the 0-based rank of the threshold among the M residuals
+ *                                          (a quantile q: min(M - 1, max(0, ceil(q M) - 1)))
+ *       smooth_min 1..9                    inliers needed in a pixel's 3x3 neighbourhood (5: "at least half of 9")
+ *       patch_min  1 <= patch_min <= P^2+1 forgiven pixels needed in a patch (a fraction f: ceil(f P^2)); P^2 + 1: never
+ *   out of range: VOXE_ERR_BAD_SHAPE.  Per pixel p, every operation rounded to float32:
+ *       d_c = x_c - y_c,   e_p = d_0 d_0, then e_p = e_p + d_c d_c for c = 1 .. C-1 in that order (a sum, not a mean)
+ *   tau = the element of rank `rank` among all M values e: an exact order statistic, no interpolation, selected over the bit
+ *   patterns with integer counters, so the same bits whatever the order of the patches.  Then, all in integers:
+ *       a_p = (e_p <= tau)
+ *       b_p = (#{q in the 3x3 neighbourhood of p inside p's own patch, p included: a_q} >= smooth_min)
+ *       c_p = a_p | b_p,    D_n = (sum_{p in patch n} c_p >= patch_min)
+ *       inner(p): row and column both in [P/4, P/4 + P/2) (integer division)
+ *       w_p = c_p | (D_n & inner(p))
+ *   mask_in [N,P,P] uint8 or NULL: when given, w = (mask_in != 0), no residual statistics are formed, rank / smooth_min /
+ *   patch_min are ignored (and not validated), and tau_out and stats are written as zeros.
+ *       loss = (1/CM) sum_p w_p sum_c |d_c|  (L1)   or   (1/CM) sum_p w_p sum_c d_c^2  (L2)     (divisor C M, not the inliers)
+ *       mse  = (1/CM) sum_p sum_c d_c^2      (without the mask, whichever the kind)
+ *       g = (float)((double)grad_scale / (C M))
+ *       d_x = (w_p g) sign(d_c)  (L1, sign(0) = 0)   or   (w_p 2g) d_c  (L2, one rounded float product); y gets no gradient
+ * Outputs, each may be NULL = skipped: loss_out, mse_out, tau_out device float[1] (grad_scale does not apply to them);
+ *   mask_out [N,P,P] uint8, strictly 0 or 1; stats device int64[3] = (sum a, sum c, sum w); d_x [N,P,P,C], every element written.
+ *   loss_out and mse_out are double sums in a fixed order with one final float rounding; tau_out, mask_out and stats come from
+ *   integer counters: every output holds the same bits from call to call, and tau_out / stats also under any permutation of the
+ *   patches (mask_out is permuted with them).  No float atomic is issued.  mask_out may be the same buffer as mask_in (every
+ *   byte is read before it is written, by the same thread); no other buffers may overlap.
+ * Non-finite inputs: the call returns, nothing is read or written outside the stated extents and mask_out stays 0 / 1; a NaN
+ *   residual orders above +inf; values are otherwise unspecified.  A residual e_p that is a float32 denormal is not part of the
+ *   contract (its place in the order may differ from a host's).
+ * scratch: voxe_robust_scratch_bytes(N, P, C) bytes of device memory (0 for shapes the call refuses), always required: NULL x,
+ *   y or scratch is VOXE_ERR_NULL_POINTER, a short one VOXE_ERR_WORKSPACE.  All validation precedes any device work.  All
+ *   outputs NULL: VOXE_OK, nothing is launched.  Work is enqueued on `stream`; no allocation, no host synchronisation.          */
+size_t voxe_robust_scratch_bytes(int32_t N, int32_t P, int32_t C);
+int voxe_robust_fwd_bwd(const float* x, const float* y, int32_t N, int32_t P, int32_t C, int32_t kind,
+                        int64_t rank, int32_t smooth_min, int32_t patch_min,
+                        const uint8_t* mask_in     /* [N,P,P] or NULL */,
+                        float grad_scale,
+                        float* loss_out, float* mse_out, float* tau_out, uint8_t* mask_out, int64_t* stats, float* d_x,
+                        void* scratch, size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM of two image batches, value and gradient in one call (additive; still ABI v13), DESIGN.md section 4.18 "SSIM".  No
  * voxe_cpu_ twin; the float64 restatement is tests/ssim_ref.py.
  *   x, y: device float, channel-last [N,H,W,C], C in 1..4 (a render's colour viewed as patches or as an image).  Wang et al.

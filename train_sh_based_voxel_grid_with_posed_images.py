@@ -101,6 +101,15 @@ def density_activations(use_relu_field: bool, use_softplus_field: bool, grid_wor
 @click.option("--exposure_regularization", type=click.FloatRange(min=0.0), default=1e-3, show_default=True,
               help="weight of mean(delta^2) on the per-image colour transforms: an untuned guard against the gauge that scene "
                    "colour and one affine common to all images share (nobody has measured it)")
+@click.option("--robust_loss", type=click.BOOL, default=False, show_default=True,
+              help="replace the L1 terms by RobustNeRF's trimmed loss on random pixel patches, for captures with transient objects "
+                   "(a passer-by, a car, a shadow); does not combine with --ssim_weight")
+@click.option("--robust_patch_size", type=click.IntRange(min=4, max=64), default=16, show_default=True,
+              help="side of the robust loss's pixel patches, even (a stage with smaller images uses its smaller side)")
+@click.option("--robust_inlier_quantile", type=click.FloatRange(min=0.0, max=1.0, min_open=True), default=0.5, show_default=True,
+              help="quantile of the batch's residuals at and below which a pixel is an inlier")
+@click.option("--robust_patch_inlier_fraction", type=click.FloatRange(min=0.0, max=1.0), default=0.6, show_default=True,
+              help="share of forgiven pixels at which the inner half of a patch is forgiven as a whole")
 @accepted_options(COMPAT_ONLY)
 def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
@@ -142,7 +151,9 @@ def main(**kwargs) -> None:
         background_learning_rate=cfg.background_learning_rate, ssim_weight=cfg.ssim_weight, ssim_patch_size=cfg.ssim_patch_size,
         depth_weight=cfg.depth_weight, depth_ray_batch_size=cfg.depth_ray_batch_size, depth_sigma_scale=cfg.depth_sigma_scale,
         orientation_weight=cfg.orientation_weight, orientation_normal_eps=cfg.orientation_normal_eps,
-        exposure_learning_rate=cfg.exposure_learning_rate, exposure_regularization=cfg.exposure_regularization)
+        exposure_learning_rate=cfg.exposure_learning_rate, exposure_regularization=cfg.exposure_regularization,
+        robust_loss=cfg.robust_loss, robust_patch_size=cfg.robust_patch_size, robust_inlier_quantile=cfg.robust_inlier_quantile,
+        robust_patch_inlier_fraction=cfg.robust_patch_inlier_fraction)
 
 
 if __name__ == "__main__":

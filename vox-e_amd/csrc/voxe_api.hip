@@ -1703,6 +1703,33 @@ int voxe_exposure_fit_sums(const float* x, const float* y, int64_t N, int64_t P,
   return finish();
 }
 
+// ---- robust photometric loss on pixel patches -------------------------------------------------------------
+namespace {
+bool robust_shape_ok(int32_t N, int32_t P, int32_t C) {
+  return N >= 1 && P >= 4 && P <= 64 && (P & 1) == 0 && C >= 1 && C <= 4 && (int64_t)N * P * P < (1LL << 31);
+}
+}  // namespace
+
+size_t voxe_robust_scratch_bytes(int32_t N, int32_t P, int32_t C) { return robust_shape_ok(N, P, C) ? robust_scratch_bytes(N, P) : 0; }
+
+int voxe_robust_fwd_bwd(const float* x, const float* y, int32_t N, int32_t P, int32_t C, int32_t kind, int64_t rank,
+                        int32_t smooth_min, int32_t patch_min, const uint8_t* mask_in, float grad_scale, float* loss_out,
+                        float* mse_out, float* tau_out, uint8_t* mask_out, int64_t* stats, float* d_x, void* scratch,
+                        size_t scratch_bytes, void* stream) {
+  if (!x || !y || !scratch) return VOXE_ERR_NULL_POINTER;
+  if (!robust_shape_ok(N, P, C)) return VOXE_ERR_BAD_SHAPE;
+  if (!mask_in && (rank < 0 || rank >= (int64_t)N * P * P || smooth_min < 1 || smooth_min > 9 || patch_min < 1 ||
+                   patch_min > P * P + 1))
+    return VOXE_ERR_BAD_SHAPE;
+  if (kind != VOXE_DREG_L1 && kind != VOXE_DREG_L2) return VOXE_ERR_UNSUPPORTED;
+  if (scratch_bytes < robust_scratch_bytes(N, P)) return VOXE_ERR_WORKSPACE;
+  if (!loss_out && !mse_out && !tau_out && !mask_out && !stats && !d_x) return VOXE_OK;
+  if (!launch_robust(x, y, N, P, C, kind == VOXE_DREG_L1, rank, smooth_min, patch_min, mask_in, grad_scale, loss_out, mse_out,
+                     tau_out, mask_out, (long long*)stats, d_x, scratch, (hipStream_t)stream))
+    return VOXE_ERR_LAUNCH;
+  return finish();
+}
+
 // ---- SSIM of channel-last images --------------------------------------------------------------------------
 namespace {
 bool ssim_shape_ok(int32_t N, int32_t H, int32_t W, int32_t C) { return N >= 1 && H >= 11 && W >= 11 && C >= 1 && C <= 4; }

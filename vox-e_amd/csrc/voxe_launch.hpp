@@ -276,6 +276,14 @@ bool launch_exposure_apply_bwd(const float* x, const int* ids, const float* delt
                                float* d_x, float* d_delta, int accumulate, void* scratch, hipStream_t st);
 void launch_exposure_fit(const float* x, const float* y, long long N, long long P, double* sums, void* scratch, hipStream_t st);
 
+// voxe_robust.hip: robust photometric loss on pixel patches [N,P,P,C]: exact order statistic of the residuals by
+// a three-digit counting select, inlier mask smoothed per 3x3 neighbourhood and per patch, loss, mse and d_x under that mask (or
+// under mask_in); integer counters only, no float atomics; no grid.  launch_robust: false when the scratch could not be cleared
+size_t robust_scratch_bytes(long long N, long long P);
+bool launch_robust(const float* x, const float* y, int N, int P, int C, bool l1, long long rank, int smooth_min, int patch_min,
+                   const unsigned char* mask_in, float grad_scale, float* loss_out, float* mse_out, float* tau_out,
+                   unsigned char* mask_out, long long* stats, float* d_x, void* scratch, hipStream_t st);
+
 // voxe_render_rays_bwd.hip: gradient of a render w.r.t. its rays; reads the raw densities and features, no
 // workspace, no atomics
 extern thread_local int tl_rays_bwd_lanes;   // test aid (voxe_render_bwd_rays_debug_lanes): != 0 pins the lanes per ray

@@ -25,6 +25,8 @@ from thre3d_atom.thre3d_reprs.depth import depth_targets_on_rays
 from thre3d_atom.thre3d_reprs.exposure import PerImageExposure
 from thre3d_atom.thre3d_reprs.poses import CameraPoseDeltas, LearnedIntrinsics, write_camera_params
 from thre3d_atom.thre3d_reprs.renderers import _render_params, render_sh_voxel_grid
+from thre3d_atom.thre3d_reprs.robust import (check_robust_options, inlier_fractions, robust_loss_on_patches, robust_mask_on_patches,
+                                             robust_patch_side)
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid, scale_voxel_grid_with_required_output_size
 from thre3d_atom.utils.constants import CAMERA_BOUNDS, CAMERA_INTRINSICS, HEMISPHERICAL_RADIUS
 from thre3d_atom.utils.imaging_utils import CameraPose, to8b
@@ -166,6 +168,16 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                                             # either, and the images must have 3 channels
     exposure_regularization: float = 1e-3,  # weight of mean(delta^2) on the transforms: a guard against the gauge that scene
                                             # colour and one affine common to all images share.  Untuned: nobody has measured it
+    robust_loss: bool = False,              # addition of this build: True replaces the L1 terms by RobustNeRF's trimmed loss
+                                            # (thre3d_reprs/robust.py) for captures with transient objects: the
+                                            # batch is floor(ray_batch_size / P^2) random P x P patches, a pixel above the
+                                            # quantile of the batch's residuals is left out unless its 3 x 3 neighbourhood or its
+                                            # patch is mostly inliers, and the mask gets no gradient.  False = off, nothing
+                                            # changes.  On, the iteration is not the one-call one either, and ssim_weight must be 0
+    robust_patch_size: int = 16,            # P, even, 4..64; a stage whose images are smaller uses min(H, W) rounded down to even,
+                                            # and the plain L1 below 4
+    robust_inlier_quantile: float = 0.5,    # the quantile of the residuals at and below which a pixel is an inlier
+    robust_patch_inlier_fraction: float = 0.6,   # share of forgiven pixels at which a patch's inner half is forgiven as a whole
 ) -> VolumetricModel:
     if not isinstance(vol_mod.thre3d_repr, VoxelGrid) or vol_mod.render_procedure != render_sh_voxel_grid:
         raise AssertionError("this train procedure needs an SH-based VoxelGrid volumetric model")
@@ -183,6 +195,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     if exposure_learning_rate < 0.0 or exposure_regularization < 0.0:
         raise ValueError(f"exposure_learning_rate and exposure_regularization must not be negative; got {exposure_learning_rate} "
                          f"and {exposure_regularization}")
+    if robust_loss:
+        check_robust_options(robust_patch_size, robust_inlier_quantile, robust_patch_inlier_fraction)
+        if ssim_weight > 0.0:
+            raise ValueError("robust_loss and ssim_weight > 0 do not combine: an SSIM term without the mask would let the "
+                             "transient objects back in, and a per-patch-weighted SSIM is not part of this build")
     if depth_weight > 0.0 and getattr(train_dataset, "sparse_points", None) is None:
         from thre3d_atom.data.datasets import SPARSE_POINTS_SUFFIX, sparse_points_path
 
@@ -327,6 +344,17 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 patch = 0
             elif patch * patch > ray_batch_size:
                 raise ValueError(f"ray_batch_size {ray_batch_size} holds no {patch} x {patch} patch")
+        robust_side = 0   # side of this stage's robust-loss patches; 0: the L1 terms are the plain ones
+        if robust_loss:
+            if one_call and stage == 1:
+                log.info("robust_loss: the iterations draw pixel patches, render, take the trimmed L1 and step separately (no "
+                         "one-call iteration)")
+            one_call = False
+            robust_side = robust_patch_side(robust_patch_size, intr.height, intr.width)
+            if robust_side == 0:
+                log.info(f"stage {stage}: images [{intr.height} x {intr.width}] hold no 4 x 4 patch: the plain L1 in this stage")
+            elif robust_side * robust_side > ray_batch_size:
+                raise ValueError(f"ray_batch_size {ray_batch_size} holds no {robust_side} x {robust_side} patch")
         if is_general_camera(intr):
             # voxe_recon_step casts (height, width, focal) cameras only: fx != fy, an off-centre principal point or a lens model
             # takes the composed iteration with voxe_cast_rays_camera
@@ -377,10 +405,12 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                         if learned_intrinsics is not None:
                             refine["intrinsics"] = learned_intrinsics.values / stage_factor
                     exposed = exposure_optimizer is not None
-                    if patch:
-                        num_patches = ray_batch_size // (patch * patch)
+                    if patch or robust_side:
+                        # (the SSIM term and the robust loss exclude each other: one of the two sides is 0)
+                        side = patch or robust_side
+                        num_patches = ray_batch_size // (side * side)
                         rays_batch, pixels_batch, *ids_batch = sample_random_patches_and_pixels_from_cameras(
-                            intr, poses_batch, data.images, num_patches, patch, image_ids=picks, **refine, return_image_ids=exposed)
+                            intr, poses_batch, data.images, num_patches, side, image_ids=picks, **refine, return_image_ids=exposed)
                     else:
                         rays_batch, pixels_batch, *ids_batch = sample_random_rays_and_pixels_from_cameras(
                             intr, poses_batch, data.images, ray_batch_size, image_ids=picks, **refine,
@@ -388,9 +418,22 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                             #  16384+ rays take the space-binned render, which does not care about the order: skip the sort)
                             memory_order=ray_batch_size < 16384, fast_subset=True, return_image_ids=exposed)
                     specular = vol_mod.render_rays(rays_batch).colour
+                    robust_weight = robust_mask = None
+                    if robust_side and exposed:
+                        # (the mask of the colours as the loss sees them, a constant; then the loss under the transforms with the
+                        #  mask as per-ray weights: its normalisation, 1 / 3R sum omega, is the robust loss's)
+                        corrected = vol_mod.exposure.corrected(specular.detach(), ids_batch[0])
+                        robust_mask, robust_info = robust_mask_on_patches(corrected, pixels_batch, num_patches, robust_side,
+                                                                          robust_inlier_quantile, robust_patch_inlier_fraction)
+                        robust_weight = robust_mask.view(-1).to(torch.float32)
                     if exposed:
                         # (value, mse and both gradients of the L1 under each ray's image transform in one call)
-                        loss, mse = vol_mod.exposure(specular, pixels_batch, ids_batch[0])
+                        loss, mse = vol_mod.exposure(specular, pixels_batch, ids_batch[0], ray_weight=robust_weight)
+                        psnr = mse2psnr(mse)
+                    elif robust_side:
+                        # (value, the unmasked mse, the mask and the gradient in one call)
+                        loss, mse, robust_mask, robust_info = robust_loss_on_patches(
+                            specular, pixels_batch, num_patches, robust_side, robust_inlier_quantile, robust_patch_inlier_fraction)
                         psnr = mse2psnr(mse)
                     else:
                         loss = torch.nn.functional.l1_loss(specular, pixels_batch)
@@ -398,7 +441,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                     if apply_diffuse_render_regularization:
                         diffuse = vol_mod.render_rays(rays_batch, render_diffuse=True).colour
                         if exposed:
-                            loss = loss + vol_mod.exposure(diffuse, pixels_batch, ids_batch[0])[0]
+                            loss = loss + vol_mod.exposure(diffuse, pixels_batch, ids_batch[0], ray_weight=robust_weight)[0]
+                        elif robust_side:
+                            # (the diffuse term under the specular term's mask)
+                            loss = loss + robust_loss_on_patches(diffuse, pixels_batch, num_patches, robust_side,
+                                                                 mask=robust_mask)[0]
                         else:
                             loss = loss + torch.nn.functional.l1_loss(diffuse, pixels_batch)
                     if exposed and exposure_regularization > 0.0:
@@ -456,7 +503,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                              + (f" distortion: {float(distortion.detach()): .6f}" if distortion_weight > 0.0 else "")
                              + (f" ssim: {float(ssim.detach()): .4f}" if patch else "")
                              + (f" depth: {float(depth.detach()): .6f}" if depth_weight > 0.0 else "")
-                             + (f" orientation: {float(orientation.detach()): .6f}" if orientation_weight > 0.0 else ""))
+                             + (f" orientation: {float(orientation.detach()): .6f}" if orientation_weight > 0.0 else "")
+                             + (" inliers: {:.3f} / {:.3f} / {:.3f}".format(
+                                 *inlier_fractions(robust_info, num_patches * robust_side * robust_side)) if robust_side else ""))
                 if it % lr_decay_steps_per_stage == 0:
                     scheduler.step()
                     if background_scheduler is not None:

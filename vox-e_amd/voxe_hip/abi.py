@@ -270,6 +270,10 @@ HIP_ONLY = {
     "exposure_apply_bwd": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
     "exposure_fit_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "exposure_fit_sums": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P]),
+    # robust photometric loss on pixel patches (additive, still ABI v13)
+    "robust_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "robust_fwd_bwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_float,
+                                 _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     # ray and camera-pose gradients (additive, still ABI v13)
     "render_bwd_rays": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "render_bwd_rays_debug_lanes": (C.c_int, [C.c_int32]),

@@ -1,6 +1,7 @@
 """Losses over libvoxe_hip.so (the scalar regularisers of the SDS edit, the masked attention L1, the distortion loss, the depth
-supervision and the orientation loss on rays, the per-image exposure compensation, SSIM) and Adam on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
+supervision and the orientation loss on rays, the per-image exposure compensation, the robust loss on patches, SSIM) and Adam on one tensor.  No workspace; reached through voxe_hip.ops, which re-exports every name here."""
 import ctypes as C
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -568,6 +569,133 @@ def fit_affine_colour(x: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, t
     sums = exposure_fit_sums(x, y)
     A, b = solve_affine_colour(sums)
     return A.to(x.device), b.to(x.device)
+
+
+# ------------------------------------------------------------------------------------------------
+# robust photometric loss on pixel patches: no grid, no workspace; differentiable w.r.t. x
+# ------------------------------------------------------------------------------------------------
+ROBUST_MIN_PATCH, ROBUST_MAX_PATCH = 4, 64
+
+
+def robust_parameters(M: int, P: int, inlier_quantile: float = 0.5, smooth_min_count: int = 5,
+                      patch_inlier_fraction: Optional[float] = 0.6) -> Tuple[int, int, int]:
+    """(rank, smooth_min, patch_min) of voxe_robust_fwd_bwd for M = N P^2 pixels in patches of side P: the 0-based rank
+    min(M - 1, max(0, ceil(q M) - 1)) of the quantile q (in double), the 3x3 count as it stands, and ceil(f P^2) of the patch
+    fraction f, at least 1; f = None switches the patch rule off (P^2 + 1)."""
+    q = float(inlier_quantile)
+    if not 0.0 <= q <= 1.0:
+        raise VoxeError(f"robust_loss: inlier_quantile must lie in [0, 1]; got {inlier_quantile}")
+    if int(smooth_min_count) != smooth_min_count or not 1 <= smooth_min_count <= 9:
+        raise VoxeError(f"robust_loss: smooth_min_count must be an integer in 1..9; got {smooth_min_count}")
+    if patch_inlier_fraction is not None and not 0.0 <= float(patch_inlier_fraction) <= 1.0:
+        raise VoxeError(f"robust_loss: patch_inlier_fraction must lie in [0, 1] or be None (off); got {patch_inlier_fraction}")
+    rank = min(M - 1, max(0, math.ceil(q * M) - 1))
+    patch_min = P * P + 1 if patch_inlier_fraction is None else max(1, math.ceil(float(patch_inlier_fraction) * (P * P)))
+    return rank, int(smooth_min_count), patch_min
+
+
+def _check_robust_patches(entry: str, x: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor]) -> None:
+    if x.dim() != 4 or x.shape != y.shape or x.device != y.device:
+        raise VoxeError(f"{entry}: x and y must be [N,P,P,C] of one shape on one device; got {tuple(x.shape)} on {x.device} and "
+                        f"{tuple(y.shape)} on {y.device}")
+    N, P, P2, Cn = x.shape
+    if (N < 1 or P != P2 or P % 2 or not ROBUST_MIN_PATCH <= P <= ROBUST_MAX_PATCH or not 1 <= Cn <= 4
+            or N * P * P >= 1 << 31):
+        raise VoxeError(f"{entry}: needs N >= 1 square patches of an even side in {ROBUST_MIN_PATCH}..{ROBUST_MAX_PATCH}, 1..4 "
+                        f"channels (channel-last) and fewer than 2^31 pixels; got {tuple(x.shape)}")
+    for name, t in (("x", x), ("y", y)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise VoxeError(f"{entry}: {name} must be a contiguous float32 tensor; got {t.dtype}, contiguous={t.is_contiguous()}")
+        require_device(t, f"{entry} ({name})")
+    if mask is not None:
+        _require_buffer(entry, "mask", mask, shape=(N, P, P), device=x.device, dtype=torch.uint8)
+
+
+def robust_fwd_bwd(x: torch.Tensor, y: torch.Tensor, rank: int = 0, smooth_min: int = 5, patch_min: int = 1, kind: str = "l1",
+                   mask: Optional[torch.Tensor] = None, grad_scale: float = 1.0, want_loss: bool = True, want_mse: bool = True,
+                   want_tau: bool = True, want_mask: bool = True, want_stats: bool = True, d_x: Optional[torch.Tensor] = None):
+    """voxe_robust_fwd_bwd as it stands: (loss [] or None, mse [] or None, tau [] or None, mask [N,P,P] uint8 or None,
+    stats [3] int64 or None); `d_x` (contiguous float32 of x's shape, or None) receives grad_scale * dloss/dx.  With `mask`
+    (uint8 [N,P,P]) the weights are (mask != 0), rank / smooth_min / patch_min are ignored and tau and stats are zeros."""
+    if kind not in _EXPOSURE_KINDS:
+        raise VoxeError(f"robust_loss: kind must be 'l1' or 'l2'; got {kind!r}")
+    _check_robust_patches("robust_loss", x, y, mask)
+    device = x.device
+    if d_x is not None:
+        _require_buffer("robust_loss", "d_x", d_x, shape=x.shape, device=device)
+    N, P, _, Cn = (int(v) for v in x.shape)
+    if mask is None and not (0 <= rank < N * P * P and 1 <= smooth_min <= 9 and 1 <= patch_min <= P * P + 1):
+        raise VoxeError(f"robust_loss: needs 0 <= rank < {N * P * P}, smooth_min in 1..9 and 1 <= patch_min <= {P * P + 1}; got "
+                        f"{rank}, {smooth_min}, {patch_min}")
+    ensure_gfx950(device)
+    xd, yd = x.detach(), y.detach()
+    L = lib()
+    with torch.cuda.device(device):
+        loss = torch.empty((), dtype=torch.float32, device=device) if want_loss else None
+        mse = torch.empty((), dtype=torch.float32, device=device) if want_mse else None
+        tau = torch.empty((), dtype=torch.float32, device=device) if want_tau else None
+        mask_out = torch.empty((N, P, P), dtype=torch.uint8, device=device) if want_mask else None
+        stats = torch.empty((3,), dtype=torch.int64, device=device) if want_stats else None
+        sc = _scratch_for(device, L.voxe_robust_scratch_bytes(N, P, Cn))
+        check(L.voxe_robust_fwd_bwd(ptr(xd), ptr(yd), N, P, Cn, _EXPOSURE_KINDS[kind], int(rank), int(smooth_min), int(patch_min),
+                                    ptr(mask), float(grad_scale), ptr(loss), ptr(mse), ptr(tau), ptr(mask_out), ptr(stats), ptr(d_x),
+                                    ptr(sc), sc.numel(), stream_ptr(device)), "voxe_robust_fwd_bwd")
+    wrote(d_x)
+    return loss, mse, tau, mask_out, stats
+
+
+class _RobustFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, rank, smooth_min, patch_min, kind, mask):
+        d_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        loss, mse, tau, mask_out, stats = robust_fwd_bwd(x, y, rank, smooth_min, patch_min, kind, mask, d_x=d_x)
+        ctx.save_for_backward(d_x)
+        ctx.mark_non_differentiable(mse, tau, mask_out, stats)
+        return loss, mse, tau, mask_out, stats
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (d_x,) = ctx.saved_tensors
+        return (None if d_x is None else d_x * g,) + (None,) * 6
+
+
+def _robust_info(tau, stats, rank, smooth_min, patch_min):
+    return {"tau": tau, "stats": stats, "rank": rank, "smooth_min": smooth_min, "patch_min": patch_min}
+
+
+def robust_loss(x: torch.Tensor, y: torch.Tensor, *, inlier_quantile: float = 0.5, smooth_min_count: int = 5,
+                patch_inlier_fraction: Optional[float] = 0.6, kind: str = "l1", mask: Optional[torch.Tensor] = None):
+    """RobustNeRF's trimmed photometric loss (Sabour et al. 2023) of two channel-last batches of patches [N,P,P,C], P even in
+    4..64, C in 1..4, float32 contiguous on the device -- a render's colour viewed as patches against the photographs.  A pixel
+    is an inlier when its squared residual (summed over the channels) is at most the `inlier_quantile` order statistic of the
+    batch; an outlier is forgiven when at least `smooth_min_count` of its 3x3 neighbourhood (inside its patch) are inliers, or,
+    in the inner half of a patch, when at least `patch_inlier_fraction` of the patch is forgiven (None: rule off).  The loss is
+    the mean over all C N P^2 elements of w |x - y| ('l1') or w (x - y)^2 ('l2') with the 0 / 1 mask w a constant.  Returns
+    (loss [], mse [], mask [N,P,P] uint8, info): `loss` is differentiable w.r.t. `x` (the gradient is computed in the forward,
+    only when x requires one); `mse` is the unmasked mean of (x - y)^2 for a PSNR line; info holds "tau" (the threshold, []),
+    "stats" (int64 [3]: the counts of raw inliers, of forgiven pixels, of the mask) and the three integers the call used.  With
+    `mask` (uint8 [N,P,P], another call's) the weights are (mask != 0), nothing is selected and tau and stats are zeros.  `y`
+    and `mask` receive no gradient."""
+    if y.requires_grad:
+        raise VoxeError("robust_loss: the target y receives no gradient; detach it")
+    if kind not in _EXPOSURE_KINDS:
+        raise VoxeError(f"robust_loss: kind must be 'l1' or 'l2'; got {kind!r}")
+    _check_robust_patches("robust_loss", x, y, mask)
+    N, P = int(x.shape[0]), int(x.shape[1])
+    rank, smooth_min, patch_min = robust_parameters(N * P * P, P, inlier_quantile, smooth_min_count, patch_inlier_fraction)
+    loss, mse, tau, mask_out, stats = _RobustFn.apply(x, y, rank, smooth_min, patch_min, kind, mask)
+    return loss, mse, mask_out, _robust_info(tau, stats, rank, smooth_min, patch_min)
+
+
+def robust_mask(x: torch.Tensor, y: torch.Tensor, *, inlier_quantile: float = 0.5, smooth_min_count: int = 5,
+                patch_inlier_fraction: Optional[float] = 0.6):
+    """The mask of robust_loss alone, for composing with other losses: (mask [N,P,P] uint8, info) from the same call with only
+    mask_out, tau_out and stats; no gradient."""
+    _check_robust_patches("robust_mask", x, y, None)
+    N, P = int(x.shape[0]), int(x.shape[1])
+    rank, smooth_min, patch_min = robust_parameters(N * P * P, P, inlier_quantile, smooth_min_count, patch_inlier_fraction)
+    _, _, tau, mask_out, stats = robust_fwd_bwd(x, y, rank, smooth_min, patch_min, want_loss=False, want_mse=False)
+    return mask_out, _robust_info(tau, stats, rank, smooth_min, patch_min)
 
 
 # ------------------------------------------------------------------------------------------------

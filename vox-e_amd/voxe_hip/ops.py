@@ -20,7 +20,8 @@ from .gridops import (LIFT_MERGE_PER_LANE, LIFT_MERGE_SHIPPED, LIFT_MERGE_WAVE, 
 from .losses import (adam_step_, attn_masked_l1, density_correlation_loss, density_diff_loss, depth_fwd_bwd,  # noqa: F401
                      depth_loss, distortion_fwd_bwd, distortion_loss, exposure_apply, exposure_apply_bwd, exposure_fit_sums, exposure_fwd_bwd,
                      exposure_loss, feature_correlation_loss, fit_affine_colour, orientation_fwd_bwd, orientation_loss,
-                     solve_affine_colour, ssim, ssim_fwd_bwd, tv_loss_on_grid)
+                     robust_fwd_bwd, robust_loss, robust_mask, robust_parameters, solve_affine_colour, ssim, ssim_fwd_bwd,
+                     tv_loss_on_grid)
 from .runtime import VoxeError, check, ensure_gfx950, f32c, lib, ptr, require_device, stream_ptr
 from .workspace import DROPPED, DeferredGrad, ReconRecord, Workspace, wrote, _pack_key, _scratch_for, _state_key  # noqa: F401
 
