@@ -1222,6 +1222,50 @@ int voxe_background_bwd(const VoxeEnvMap* env, const float* rays_d, int64_t R, c
                         int32_t accumulate, void* stream);
 int voxe_background_debug_merge(int32_t mode);
 
+/* ---- mesh import: a triangle mesh into a signed-distance band on a voxel lattice (not in the reference) -----------
+ * An added symbol is backward compatible: VOXE_ABI_VERSION stays 13.  No voxe_cpu_ twin; the numpy restatement (integer parity,
+ * float32 distance operation for operation, float64 for bounds) is tests/voxelize_ref.py.
+ *
+ * Lattice: X x Y x Z voxels, centre i at lo + (i + 0.5) (hi - lo) / N per axis (the mesh export's convention), aabb_lo / aabb_hi
+ * HOST float[3].  vertices [V,3] float32 world space, faces [T,3] int32, vertex_colours [V,3] float32 or NULL, all on the device.
+ * h > 0 is the band half-width in world units.  Outputs (device, caller-owned; every one but sdf may be NULL):
+ *   sdf     [X,Y,Z]   float32  signed distance of the voxel centre to the mesh, negative inside, clamped to +-h
+ *   nearest [X,Y,Z]   int32    the triangle that realises it (the lowest id among equal distances), -1 outside the band
+ *   colours [X,Y,Z,3] float32  vertex colours interpolated at the closest point of that triangle; 0 outside the band or
+ *                              without vertex_colours
+ *   inside  [X,Y,Z]   uint8    1 inside
+ *   stats   int64[4]           columns (y, z) with an odd number of crossings (an open mesh); triangles skipped as malformed (an
+ *                              index outside [0, V), a non-finite vertex, a vertex outside the fixed-point range); voxels in the
+ *                              band; work items
+ * Distance: exact closest point of every triangle by Voronoi regions on the world-space vertices (taken in ascending vertex id,
+ * so the result does not depend on how a face lists them), float32 with every operation rounded on its own; the voxel keeps
+ * the minimum of (bits(d^2) << 32 | triangle id) over the triangles with d^2 <= h^2 through one 64-bit integer atomicMin, so the
+ * result is the same bits whatever the order of the faces.  Sign: parity of the crossings of the ray through the column's centre
+ * along +x, in integers: with u = (p - lo) / step - 0.5 (float32) a vertex is snapped to q = rint(256 u); a vertex is admissible
+ * when |u| < 1024 on every axis.  A triangle covers column (y, z) when the centre passes its three edge functions (int64) under a
+ * top-left rule -- a centre on an edge belongs to the side the point (y + eps, z + eps^2) falls on, so an edge or vertex shared
+ * by several triangles counts exactly as a ray next to it would -- and the crossing is charged to the first voxel whose centre
+ * has x >= the plane's x over the centre (an exact ceiling division).  A voxel is inside when the number of crossings charged
+ * to voxels 0..i is odd.  Triangles whose snapped vertices are collinear take no part in either pass (they are not malformed).
+ *
+ * Scratch: voxe_voxelize_scratch_bytes(X, Y, Z, T) = the key grid (8 B per voxel), the counter grid (4 B per voxel and per
+ * column, one plane behind the grid for the crossings there), and 12 B per triangle + 8 B for the work list.  The list is
+ * bounded by T without a read-back because no work item is stored: the list is the exclusive prefix of the items per triangle
+ * (one deterministic one-block scan), and a wave finds its item's triangle by bisection and rebuilds the item's cells from the
+ * triangle's vertices.  0 for dims the call refuses.
+ *
+ * Validation, in this order and before any device work: a NULL sdf, aabb_lo or aabb_hi, NULL vertices with V > 0 or NULL faces
+ * with T > 0: VOXE_ERR_NULL_POINTER; X, Y or Z outside 1..VOXE_VOXELIZE_MAX_DIM, V < 0 or >= 2^31, T < 0 or >= 2^31, an empty or
+ * non-finite aabb, h <= 0 or not finite: VOXE_ERR_BAD_SHAPE; scratch NULL or short: VOXE_ERR_WORKSPACE.  T == 0: VOXE_OK with
+ * sdf = +h, nearest = -1, colours = 0, inside = 0, stats = 0.  Caller's stream, no host synchronisation, no allocation; no
+ * render workspace, forward record or prefetch hint is touched.                                                              */
+#define VOXE_VOXELIZE_MAX_DIM 1024
+size_t voxe_voxelize_scratch_bytes(int32_t X, int32_t Y, int32_t Z, int64_t T);
+int voxe_voxelize_mesh(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const float* vertex_colours,
+                       int32_t X, int32_t Y, int32_t Z, const float* aabb_lo, const float* aabb_hi, float h,
+                       float* sdf, int32_t* nearest, float* colours, uint8_t* inside, int64_t* stats,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.

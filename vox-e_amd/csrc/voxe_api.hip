@@ -1918,4 +1918,24 @@ int voxe_grid_resample(const float* src_densities, const float* src_features, in
   return finish();
 }
 
+// ---- mesh import ----------------------------------------------------------------------------------------------
+size_t voxe_voxelize_scratch_bytes(int32_t X, int32_t Y, int32_t Z, int64_t T) {
+  return voxelize_dims_ok(X, Y, Z, T) ? voxelize_scratch_bytes(X, Y, Z, T) : 0;
+}
+
+int voxe_voxelize_mesh(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const float* vertex_colours,
+                       int32_t X, int32_t Y, int32_t Z, const float* aabb_lo, const float* aabb_hi, float h, float* sdf,
+                       int32_t* nearest, float* colours, uint8_t* inside, int64_t* stats, void* scratch, size_t scratch_bytes,
+                       void* stream) {
+  if (!sdf || !aabb_lo || !aabb_hi || (V > 0 && !vertices) || (T > 0 && !faces)) return VOXE_ERR_NULL_POINTER;
+  if (!voxelize_dims_ok(X, Y, Z, T) || V < 0 || V >= (1ll << 31)) return VOXE_ERR_BAD_SHAPE;
+  for (int d = 0; d < 3; ++d)
+    if (!(aabb_hi[d] > aabb_lo[d]) || !(aabb_hi[d] - aabb_lo[d] < INFINITY)) return VOXE_ERR_BAD_SHAPE;
+  if (!(h > 0.0f) || !(h < INFINITY)) return VOXE_ERR_BAD_SHAPE;
+  if (!scratch || scratch_bytes < voxelize_scratch_bytes(X, Y, Z, T)) return VOXE_ERR_WORKSPACE;
+  launch_voxelize(vertices, V, faces, T, vertex_colours, X, Y, Z, aabb_lo, aabb_hi, h, sdf, nearest, colours, inside, stats,
+                  scratch, (hipStream_t)stream);
+  return finish();
+}
+
 }  // extern "C"

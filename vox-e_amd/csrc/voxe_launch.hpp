@@ -322,4 +322,11 @@ void launch_ssim(const float* x, const float* y, int N, int H, int W, int C, flo
 void launch_grid_resample(const float* src_dens, const float* src_feat, int X, int Y, int Z, int C, float* dst_dens, float* dst_feat,
                           int X2, int Y2, int Z2, const VoxeResample& xf, uint8_t* taken, hipStream_t st);
 
+// voxe_voxelize.hip: mesh import (signed-distance band of a triangle mesh; arguments validated by the API)
+bool voxelize_dims_ok(int X, int Y, int Z, long long T);
+size_t voxelize_scratch_bytes(int X, int Y, int Z, long long T);
+void launch_voxelize(const float* vertices, long long V, const int32_t* faces, long long T, const float* vertex_colours, int X,
+                     int Y, int Z, const float* aabb_lo, const float* aabb_hi, float h, float* sdf, int32_t* nearest,
+                     float* colours, uint8_t* inside, int64_t* stats, void* scratch, hipStream_t st);
+
 }  // namespace voxe

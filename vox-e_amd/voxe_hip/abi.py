@@ -299,6 +299,10 @@ HIP_ONLY = {
     "ssim_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "ssim_fwd_bwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int32,
                                _P, C.c_size_t, _P]),
+    # mesh import: signed-distance band of a triangle mesh (additive, still ABI v13)
+    "voxelize_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "voxelize_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                C.POINTER(C.c_float), C.c_float, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 
 CPU_ONLY = {

@@ -141,6 +141,52 @@ def extract_mesh(spec: GridSpec, densities: torch.Tensor, level: float,
 
 
 # ------------------------------------------------------------------------------------------------
+# mesh import (signed-distance band of a triangle mesh): no workspace, not differentiable
+# ------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def voxelize_mesh(vertices: torch.Tensor, faces: torch.Tensor, colours: Optional[torch.Tensor], dims: Sequence[int], aabb,
+                  band: float):
+    """voxe_voxelize_mesh (include/voxe.h): vertices [V,3] float32 (world space), faces [T,3] int32 and optional vertex colours
+    [V,3] on the device; `dims` (X, Y, Z) and `aabb` ((lo, hi) per axis) the lattice, `band` the half-width h > 0 in world units.
+    -> (sdf [X,Y,Z] float32, negative inside, clamped to +-h; nearest [X,Y,Z] int32, -1 outside the band; colours [X,Y,Z,3];
+    inside [X,Y,Z] uint8; stats: python ints (odd columns, malformed triangles, voxels in the band, work items), read back
+    once).  The same bits whatever the order of the faces."""
+    require_device(vertices, "voxelize_mesh (vertices)")
+    require_device(faces, "voxelize_mesh (faces)")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise VoxeError(f"voxelize_mesh: vertices must be [V,3] and faces [T,3]; got {tuple(vertices.shape)}, {tuple(faces.shape)}")
+    device = vertices.device
+    v = f32c(vertices.detach())
+    f = faces.detach().to(device=device, dtype=torch.int32).contiguous()
+    c = None
+    if colours is not None:
+        require_device(colours, "voxelize_mesh (colours)")
+        if tuple(colours.shape) != tuple(v.shape):
+            raise VoxeError(f"voxelize_mesh: colours must be [V,3]={tuple(v.shape)}; got {tuple(colours.shape)}")
+        c = f32c(colours.detach())
+    X, Y, Z = (int(d) for d in dims)
+    lo = (C.c_float * 3)(*[float(a[0]) for a in aabb])
+    hi = (C.c_float * 3)(*[float(a[1]) for a in aabb])
+    ensure_gfx950(device)
+    L = lib()
+    V, T = int(v.shape[0]), int(f.shape[0])
+    with torch.cuda.device(device):
+        nbytes = int(L.voxe_voxelize_scratch_bytes(X, Y, Z, T))
+        if nbytes == 0:
+            raise VoxeError(f"voxelize_mesh: a {X}x{Y}x{Z} lattice / {T} triangles are outside the limits of voxe_voxelize_mesh")
+        sc = _scratch_for(device, nbytes)
+        sdf = torch.empty((X, Y, Z), dtype=torch.float32, device=device)
+        nearest = torch.empty((X, Y, Z), dtype=torch.int32, device=device)
+        cols = torch.empty((X, Y, Z, 3), dtype=torch.float32, device=device)
+        inside = torch.empty((X, Y, Z), dtype=torch.uint8, device=device)
+        stats = torch.empty(4, dtype=torch.int64, device=device)
+        check(L.voxe_voxelize_mesh(ptr(v), V, ptr(f), T, ptr(c), X, Y, Z, lo, hi, float(band), ptr(sdf), ptr(nearest), ptr(cols),
+                                   ptr(inside), ptr(stats), ptr(sc), sc.numel(), stream_ptr(device)), "voxe_voxelize_mesh")
+        stats = tuple(int(s) for s in stats.cpu())
+    return sdf, nearest, cols, inside, stats
+
+
+# ------------------------------------------------------------------------------------------------
 # density-gradient normals (DESIGN.md section 4 "Normals"): read the raw densities only, no workspace, not differentiable
 # ------------------------------------------------------------------------------------------------
 def _normals_grid_desc(spec: GridSpec, dens: torch.Tensor):
