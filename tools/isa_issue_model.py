@@ -213,8 +213,10 @@ def model(src_file, kernel_filter):
     return out, blocks, loops
 
 
-# the kernels of the headline step: the planned instantiations and the unplanned kernels of launches without a plan
-HEADLINE = [("voxe_render_tile4.hip", "render_bwd_tile4_plan_kernel"), ("voxe_render_tile4.hip", "render_fwd_tile4w_plan_kernel"),
+# the kernels of the headline step: the planned instantiations specialised for its launch-uniform configuration,
+# the planned instantiations of every other configuration (4.7) and the unplanned kernels of launches without a plan
+HEADLINE = [("voxe_render_tile4.hip", "render_bwd_tile4_plan_sw_kernel"), ("voxe_render_tile4.hip", "render_fwd_tile4w_plan_sw_kernel"),
+            ("voxe_render_tile4.hip", "render_bwd_tile4_plan_kernel"), ("voxe_render_tile4.hip", "render_fwd_tile4w_plan_kernel"),
             ("voxe_render_tile4.hip", "render_bwd_tile4_kernel<8, false, 0>"), ("voxe_render_tile4.hip", "render_fwd_tile4w_kernel<false>")]
 
 

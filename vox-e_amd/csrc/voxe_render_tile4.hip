@@ -58,8 +58,14 @@ namespace voxe {
 #ifndef VOXE_T4_REMAT
 #define VOXE_T4_REMAT 0   // r06 experiment: the deposit's lane constants re-derived from the lane index per sample instead of living in ~14 VGPRs
 #endif
+#ifndef VOXE_T4_UNI
+#define VOXE_T4_UNI 1     // 0 (A/B builds): launches of the headline configuration run the planned kernels that read the launch-uniform switches at run time
+#endif
+#ifndef VOXE_T4_FLUSH32
+#define VOXE_T4_FLUSH32 1 // 0 (A/B builds): the specialised planned backward keeps the 64-bit scalar address arithmetic of the flush
+#endif
 #ifndef VOXE_T4_DEBUG
-#define VOXE_T4_DEBUG 0   // debugging builds (tools/variants.py): 1 every sample through the per-corner path | 2 ... and no corner in the window
+#define VOXE_T4_DEBUG 0  // debugging builds (tools/variants.py): 1 every sample through the per-corner path | 2 ... and no corner in the window
 #endif
 
 struct Tile4Args {
@@ -81,6 +87,44 @@ struct Tile4Args {
   const int* sched;       // cost-ordered block list of this launch (build_tile_sched), or null: blocks run in launch order
   const int2* plan;       // planned kernel only: the launch's per-tile plan in list order (build_tile_sched)
 };
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Launch-uniform switches of the planned kernels: the density post-activation, the background, which gradients
+// are wanted and the gradient truncation are the same for every block of a launch, and the host knows them -- but read at run
+// time they are decided per SAMPLE (s_cmp / s_cbranch pairs around the activation, v_cndmask re-materialising want_f, a k_hi
+// that is not loop invariant because of the term_eps test).  The march and body templates take the switches through a tag:
+// UniGeneric reads them from the launch arguments (the kernels as they were, every configuration), UniHeadline states the one
+// configuration the planned kernels are specialised for -- softplus, white background, both gradients, no truncation -- as
+// constants.  One copy of the text; no floating-point expression differs (x * 1.0f and x - 0.0f of the run-time forms are exact).
+// ------------------------------------------------------------------------------------------------------------------------
+struct UniGeneric {
+  static constexpr bool kFixed = false;
+  static constexpr bool kFlush32 = false;
+  static __device__ __forceinline__ int post_act(const DevGrid& g) { return g.post_act; }
+  static __device__ __forceinline__ bool white(const DevCfg& c) { return c.white != 0; }
+  static __device__ __forceinline__ float term_eps(const DevCfg& c) { return c.term_eps; }
+  static __device__ __forceinline__ bool want_d(const Tile4Args& a) { return a.want_d != 0; }
+  static __device__ __forceinline__ bool want_f(const Tile4Args& a) { return a.want_f != 0; }
+};
+struct UniHeadline {
+  static constexpr bool kFixed = true;
+  // the flush addresses the gradient as (a.gpacked + 32-bit lane offset), the layer's origin voxel a byte offset out of the
+  // per-layer table (Tab4<true>): gradient buffers up to 4 GiB -- the launcher checks
+  static constexpr bool kFlush32 = VOXE_T4_FLUSH32 != 0;
+  static __device__ __forceinline__ int post_act(const DevGrid&) { return VOXE_ACT_SOFTPLUS; }
+  static __device__ __forceinline__ bool white(const DevCfg&) { return true; }
+  static __device__ __forceinline__ float term_eps(const DevCfg&) { return 0.0f; }
+  static __device__ __forceinline__ bool want_d(const Tile4Args&) { return true; }
+  static __device__ __forceinline__ bool want_f(const Tile4Args&) { return true; }
+};
+// does a launch have UniHeadline's configuration?  (the forward reads the post-activation alone: its launcher passes true for
+// the gradients and asks nothing of the background or the truncation, which it never sees)
+static bool uni_headline_bwd(const DevGrid& g, const DevCfg& c, bool want_d, bool want_f) {
+  // (kFlush32: every voxel of the gradient buffer within a 32-bit byte offset of its base)
+  if (UniHeadline::kFlush32 && (unsigned long long)g.X * (unsigned long long)g.Y * (unsigned long long)g.Z * 16ull > (1ull << 32)) return false;
+  return g.post_act == VOXE_ACT_SOFTPLUS && c.white != 0 && !(c.term_eps > 0.0f) && want_d && want_f;
+}
+static bool uni_headline_fwd(const DevGrid& g) { return g.post_act == VOXE_ACT_SOFTPLUS; }
 
 // Orientation of a tile in its wave (wave-uniform): do the 8 consecutive lanes of a row run along the image rows (false) or down
 // the image columns (true)?  The texel gathers are bound by the texture-address / L1 path (~45 clk per divergent 16-byte wave
@@ -554,7 +598,18 @@ struct DepCtx {
   long long src_base;    // slot of (tile, segment, sample 0, lane) in the source buffer (render_bwd_tile_kernel's layout)
 };
 
-constexpr int kTabKeys = 64;     // layer keys tabulated per pass (re-based when the window has moved 32 layers)
+// The per-layer table of a pass: (origin u | origin v << 16, ring-slot term of the LDS address) per layer key, re-based when the
+// window has moved half the table.  F32 (UNI::kFlush32): 16-byte entries that also hold the byte offset of the layer's origin
+// voxel relative to the gradient's base (mod 2^32; the origin of a border layer may lie in front of the buffer, the voxels a
+// lane flushes never do) -- half as many keys in the same 512 bytes, so the kernel keeps its ten LDS granules.  The sample
+// loop reads the first 8 bytes of an entry either way.
+template <bool F32>
+struct Tab4 {
+  typedef typename std::conditional<F32, int4, int2>::type Entry;
+  static constexpr int kKeys = F32 ? 32 : 64;
+  static __device__ __forceinline__ int2 xy(const Entry* tab, int i) { return *reinterpret_cast<const int2*>(tab + i); }
+};
+static_assert(Tab4<true>::kKeys / 2 + kRing <= Tab4<true>::kKeys, "every layer of the ring is tabulated between two re-bases");
 
 // byte strides of the parity-class banked window (WinMap<KL, 4>): index (doubles) = kSS (slot >> 1) + 4 (slot & 1) + kSA (a >> 1)
 // + 2 (a & 1) + kSB (b >> 1) + (b & 1) + 8 ch
@@ -627,9 +682,9 @@ __device__ __forceinline__ void global_add_f32(gchar* base, unsigned voff, float
 // shift `sh` -- the layers a ray is ahead of the pass's reference ray, rounded to samples -- lane l works on sample kb + koff,
 // koff = phase - sh, and the wave's footprint along the march axis is that of ONE ray (+ rounding) whatever the view.  The
 // strata then come through the LDS crossbar (the stratum index differs from lane to lane: no v_readlane).
-template <int MA, int KL, bool PREC, bool DEP, int NP = 1, bool LK = (NP > 1)>
+template <int MA, int KL, bool PREC, bool DEP, class UNI, int NP = 1, bool LK = (NP > 1)>
 __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, const Tile4Args& a, RayCtx<3, 1, 1>& rc,
-                                           double* __restrict__ win, int2* __restrict__ tab, const int lane, const long long r,
+                                           double* __restrict__ win, typename Tab4<UNI::kFlush32>::Entry* __restrict__ tab, const int lane, const long long r,
                                            bool has, const int k_lo, int k_hi, const int kmin, const int kmax, const int seg,
                                            const int ks, const Geo4 geo, const float strat_lo, const float strat_sp,
                                            const DepCtx& dep, const int phase = 0, const int xm1 = 0, const int xm2 = 0, const int koff = 0) {
@@ -641,6 +696,10 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
   typedef Pcb<KL> P;
   static_assert(!(DEP && PREC), "deposit passes carry no suffix sums");
   constexpr unsigned TB = 16u;   // bytes of a texel of the gradient the window is flushed into (DEP: the group's plane, see DepCtx)
+  constexpr bool F32 = UNI::kFlush32;
+  typedef Tab4<F32> TT;
+  constexpr int kTabKeys = TT::kKeys;
+  static_assert(!F32 || KL == 8, "32-bit flush offsets: the 8-wide window only");
 
   // ---- per-ray constants of the backward (render_bwd_kernel, voxe_render.hip) ----------------------------------------
   float gc[COUT] = {0.0f, 0.0f, 0.0f}, gsum = 0.0f;
@@ -650,7 +709,7 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
   }
   const float gdep = (!DEP && a.d_depth) ? a.d_depth[r] : 0.0f;
   const float gacc = (!DEP && a.d_acc) ? a.d_acc[r] : 0.0f;
-  const bool white = c.white != 0;
+  const bool white = UNI::white(c);
   float T = 1.0f, suffix0 = 0.0f;
   if constexpr (!DEP) {
     const float asum = a.acc[r];
@@ -703,8 +762,8 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
   const float gsumw = white ? gsum : 0.0f;                      // (x - 0 == x: the white-background term without a branch)
   float gcf[COUT];                                               // d rad_c = (w g_c) (col (1 - col)) C0, C0 folded into g_c's copy
 #pragma unroll
-  for (int ch = 0; ch < COUT; ++ch) gcf[ch] = a.want_f ? gc[ch] : 0.0f;
-  const float dmask = a.want_d ? 1.0f : 0.0f;
+  for (int ch = 0; ch < COUT; ++ch) gcf[ch] = UNI::want_f(a) ? gc[ch] : 0.0f;
+  const float dmask = UNI::want_d(a) ? 1.0f : 0.0f;
   float run = 0.0f;
 
   // ---- lane constants of the parity-class banked deposit (WinMap) ----------------------------------------------------
@@ -742,7 +801,10 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
   auto build_tab = [&](int key0) {
     const int key = key0 + lane, im = sgn * key;
     const int ou = (int)floorf(geo.Au + geo.Bu * (float)im) - kCtr, ov = (int)floorf(geo.Av + geo.Bv * (float)im) - kCtr;
-    tab[lane] = make_int2((ou & 0xffff) | (ov << 16), P::mterm(ring_slot(key)));
+    if constexpr (F32) {
+      const unsigned org = ((unsigned)im * (unsigned)stride_m + (unsigned)ou * (unsigned)stride_u + (unsigned)ov * (unsigned)stride_v) * TB;
+      if (lane < kTabKeys) tab[lane] = make_int4((ou & 0xffff) | (ov << 16), P::mterm(ring_slot(key)), (int)org, 0);
+    } else tab[lane] = make_int2((ou & 0xffff) | (ov << 16), P::mterm(ring_slot(key)));
   };
 
   // depth of sample k: stratum (lower, span) of the segment's table (wave-uniform: every lane is at the same k) + this ray's jitter
@@ -834,7 +896,7 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
   unsigned long long pend[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) pend[j] = 0ull;
-  unsigned long long pend_vb = 0ull;     // scalar: global byte address of the pending layer's origin voxel
+  unsigned long long pend_vb = 0ull;     // scalar: global byte address of the pending layer's origin voxel (F32: its byte offset)
   int npend = 0;                         // wave-uniform: pending layers (0 / 1; kPair: up to 2)
   // (kPair) the second pending layer, the keys' parities, this lane's voxel offsets under both lane maps
   unsigned long long pendB[kPair ? NJ : 1];
@@ -842,14 +904,24 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
   int oddA = 0, oddB = 0;
   const bool lane_hi = lane >= 32;
   const unsigned step4 = (unsigned)(4 * stride_v) * TB;
+  const unsigned gs32 = 2u * (unsigned)stride_u * TB;     // (F32) byte step from one instruction group of a layer to the next
   const unsigned vox_b03 = kPair ? fl_vox[0] - (lane_hi ? step4 : 0u) : 0u;   // this lane's voxel with b reduced to 0..3
   auto flush_issue = [&](int key) __attribute__((always_inline)) {      // key wave-uniform
     if (VOXE_T4_EXP & 4) return;
-    const int2 e = tab[key - key0];      // (broadcast read)
-    const int ex = rfl(e.x), mt = rfl(e.y);
-    const int ou = (int)(short)(ex & 0xffff), ov = ex >> 16;
-    const int im = sgn * key;
-    const unsigned long long vb = gaddr + (unsigned long long)((long long)im * sm16 + (long long)ou * su16 + (long long)ov * sv16);   // scalar
+    unsigned long long vb;               // scalar
+    int mt;
+    if constexpr (F32) {
+      const int4 e = tab[key - key0];    // (broadcast read)
+      mt = rfl(e.y);
+      vb = (unsigned)rfl(e.z);
+    } else {
+      const int2 e = TT::xy(tab, key - key0);      // (broadcast read)
+      const int ex = rfl(e.x);
+      mt = rfl(e.y);
+      const int ou = (int)(short)(ex & 0xffff), ov = ex >> 16;
+      const int im = sgn * key;
+      vb = gaddr + (unsigned long long)((long long)im * sm16 + (long long)ou * su16 + (long long)ov * sv16);
+    }
     char* const wb = reinterpret_cast<char*>(win);
     if constexpr (kPair) {
       const int odd = key & 1;
@@ -892,7 +964,9 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
     for (int j = 0; j < NJ; ++j) {
       const double val = __longlong_as_double((long long)pv[j]);
       if (!(VOXE_T4_EXP & 8) && val != 0.0) {
-        if constexpr (KL == 8)
+        if constexpr (F32)
+          global_add_f32(scalar_ptr(gaddr), vox + ((unsigned)vb + (unsigned)j * gs32), (float)val);   // fixed base, group term in the offset
+        else if constexpr (KL == 8)
           global_add_f32(scalar_ptr(vb + (unsigned long long)((long long)j * 2ll * su16)), vox, (float)val);   // scalar base of group j
         else
           global_add_f32(scalar_ptr(vb), fl_vox[j], (float)val);
@@ -916,16 +990,18 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
         // lanes with m set carry layer A in the instruction of b 0..3 and layer B in the instruction of b 4..7 (the others
         // the other way round): A's lanes of b 0..3 are the low half when its key is even, the high half when it is odd
         const bool m = lane_hi == (oddA != 0);
-        const unsigned long long vmin = pend_vb < pendB_vb ? pend_vb : pendB_vb;
-        const unsigned dA = (unsigned)(pend_vb - vmin), dB = (unsigned)(pendB_vb - vmin);     // scalar, small
+        // F32: the layers' own offsets (mod 2^32) go into the lane offsets, the base stays a.gpacked
+        const unsigned long long vmin = F32 ? gaddr : (pend_vb < pendB_vb ? pend_vb : pendB_vb);
+        const unsigned dA = F32 ? (unsigned)pend_vb : (unsigned)(pend_vb - vmin), dB = F32 ? (unsigned)pendB_vb : (unsigned)(pendB_vb - vmin);     // scalar
         const unsigned off1 = vox_b03 + (m ? dA : dB), off2 = vox_b03 + step4 + (m ? dB : dA);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const float fA = (float)__longlong_as_double((long long)pend[j]), fB = (float)__longlong_as_double((long long)pendB[j]);
           const float v1 = m ? fA : fB, v2 = m ? fB : fA;
-          gchar* const gb = scalar_ptr(vmin + (unsigned long long)((long long)j * 2ll * su16));
-          if (!(VOXE_T4_EXP & 8) && v1 != 0.0f) global_add_f32(gb, off1, v1);
-          if (!(VOXE_T4_EXP & 8) && v2 != 0.0f) global_add_f32(gb, off2, v2);
+          gchar* const gb = scalar_ptr(F32 ? vmin : vmin + (unsigned long long)((long long)j * 2ll * su16));
+          const unsigned gj = F32 ? (unsigned)j * gs32 : 0u;
+          if (!(VOXE_T4_EXP & 8) && v1 != 0.0f) global_add_f32(gb, off1 + gj, v1);
+          if (!(VOXE_T4_EXP & 8) && v2 != 0.0f) global_add_f32(gb, off2 + gj, v2);
         }
       }
       npend = 0;
@@ -941,7 +1017,8 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
   const char* const pbytes = reinterpret_cast<const char*>(a.packed);
   char* const gbytes = reinterpret_cast<char*>(a.gpacked);
   const int Sm1 = c.S - 1;
-  const float term_eps = c.term_eps;
+  const float term_eps = UNI::term_eps(c);
+  const int post_act = UNI::post_act(g);
   const int nk0 = -key0;   // (re-based with the table)
   int nkey0 = nk0;
 
@@ -992,7 +1069,7 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
     const int tm = (cell.i[MA] ^ hm) & 1;
     const int imA = cell.i[MA] + tm, imB = cell.i[MA] + 1 - tm;
     const int relA = ((imA ^ smask) - smask) + nkey0, relB = ((imB ^ smask) - smask) + nkey0;   // sgn * im - key0
-    const int2 eA = tab[relA & (kTabKeys - 1)], eB = tab[relB & (kTabKeys - 1)];
+    const int2 eA = TT::xy(tab, relA & (kTabKeys - 1)), eB = TT::xy(tab, relB & (kTabKeys - 1));
     float f0, f1, f2, v;
     if constexpr (DEP) { f0 = t[0].x; f1 = t[0].y; f2 = t[0].z; v = t[0].w; }
     else interp_texels4(t, cell, f0, f1, f2, v);
@@ -1031,7 +1108,7 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
       const int xB0 = PU0 - ouB, xB1 = PU1 - ouB, yB0 = PV0 - ovB, yB1 = PV1 - ovB;
       // window test: both layers inside the ring, every lateral coordinate inside [0, KL)
       const int klrel = min(relA, relB);
-      bool fits = (unsigned)(klrel - (base + nkey0)) < (unsigned)(kRing - 1);   // (base - key0 <= 32: both entries are tabulated)
+      bool fits = (unsigned)(klrel - (base + nkey0)) < (unsigned)(kRing - 1);   // (base - key0 <= kTabKeys / 2: both entries are tabulated)
       if constexpr (KL == 8) fits = fits && ((unsigned)(xA0 | xA1 | yA0 | yA1 | xB0 | xB1 | yB0 | yB1) < 8u);
       else fits = fits && (max(max(max((unsigned)xA0, (unsigned)xA1), max((unsigned)yA0, (unsigned)yA1)),
                                max(max((unsigned)xB0, (unsigned)xB1), max((unsigned)yB0, (unsigned)yB1))) < (unsigned)KL);
@@ -1112,7 +1189,7 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
       if (act) {
         const float rad[COUT] = {kC0 * f0, kC0 * f1, kC0 * f2};
         float sigma;
-        post_activate_vg(g.post_act, v, sigma, dpost);
+        post_activate_vg(post_act, v, sigma, dpost);
         const float dl = last ? kInfinity : (z_n1 - z);
         const float delta = dl * rc.dnorm;
         const float e = fast_exp(-(sigma * delta));
@@ -1199,7 +1276,7 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
         } else {
         const float rad[COUT] = {kC0 * f0, kC0 * f1, kC0 * f2};
         float sigma, dpost;
-        post_activate_vg(g.post_act, v, sigma, dpost);
+        post_activate_vg(post_act, v, sigma, dpost);
         const float dl = last ? kInfinity : (z_next - z);
         const float delta = dl * rc.dnorm;
         const float e = fast_exp(-(sigma * delta));
@@ -1288,12 +1365,12 @@ __device__ __forceinline__ void bwd4_march(const DevGrid& g, const DevCfg& c, co
 // the launch geometry.  Same decisions (tile_turns_lanes / tile_split_decision, taken by the schedule pass), same passes.
 // The body is shared by the kernels below it: render_bwd_tile4_kernel<KL, PREC, NCU_DEP>, unplanned as ever, and
 // render_bwd_tile4_plan_kernel, the planned instantiation of <8, false, 0> for launches that built a list and a plan.
-template <int KL, bool PREC, int NCU_DEP, bool PLAN>
+template <int KL, bool PREC, int NCU_DEP, bool PLAN, class UNI = UniGeneric>
 __device__ __forceinline__ void render_bwd_tile4_body(const DevGrid g, const DevCfg c, const Tile4Args a_in) {
   constexpr bool DEP = NCU_DEP > 0;
   static_assert(!PLAN || (KL == 8 && !PREC && !DEP), "planned instantiation: the SH-0 float kernel of the 8-wide window only");
   __shared__ double win[WinMap<KL, 4>::kDoubles];
-  __shared__ int2 tab[kTabKeys];
+  __shared__ typename Tab4<UNI::kFlush32>::Entry tab[Tab4<UNI::kFlush32>::kKeys];
   const int lane = threadIdx.x;
   // cost-ordered launches (Tile4Args::sched): this block does the work of launch-order block sched[blockIdx.x]; a block without
   // a sample inside the volume has nothing to do
@@ -1407,8 +1484,8 @@ __device__ __forceinline__ void render_bwd_tile4_body(const DevGrid g, const Dev
     int k_lo, k_hi;
     seg_sample_range(rc, alive_q, ks, ke, k_lo, k_hi);
     bool has = k_lo <= k_hi;
-    if (has && seg > 0 && c.term_eps > 0.0f) {   // gradient truncation: nothing behind T < term_eps receives a gradient
-      if (a.ray_state[ray_state_index(seg, 0, 6, c.R, r)] < c.term_eps) { has = false; k_hi = k_lo - 1; }
+    if (has && seg > 0 && UNI::term_eps(c) > 0.0f) {   // gradient truncation: nothing behind T < term_eps receives a gradient
+      if (a.ray_state[ray_state_index(seg, 0, 6, c.R, r)] < UNI::term_eps(c)) { has = false; k_hi = k_lo - 1; }
     }
     const int kmin = wave_min_i32(has ? k_lo : INT_MAX);
     const int kmax = wave_max_i32(has ? k_hi : -1);
@@ -1466,16 +1543,16 @@ __device__ __forceinline__ void render_bwd_tile4_body(const DevGrid g, const Dev
 #define VOXE_T4_MARCH(AX)                                                                                                           \
     do {                                                                                                                            \
       if constexpr (PH > 1)                                                                                                         \
-        bwd4_march<AX, KL, PREC, DEP, PH, true>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, \
+        bwd4_march<AX, KL, PREC, DEP, UNI, PH, true>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, \
                                                 strat_sp, dep, phase, xm1, xm2, phase - sh);                                   \
       else if constexpr (VOXE_T4_SKEW == 1 && !PREC && !DEP) {                                                                           \
         if (skew)                                                                                                                   \
-          bwd4_march<AX, KL, PREC, DEP, 1, true>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, \
+          bwd4_march<AX, KL, PREC, DEP, UNI, 1, true>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, \
                                                  strat_sp, dep, 0, 0, 0, -sh);                                                      \
         else                                                                                                                        \
-          bwd4_march<AX, KL, PREC, DEP>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, strat_sp, dep); \
+          bwd4_march<AX, KL, PREC, DEP, UNI>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, strat_sp, dep); \
       } else                                                                                                                        \
-        bwd4_march<AX, KL, PREC, DEP>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, strat_sp, dep); \
+        bwd4_march<AX, KL, PREC, DEP, UNI>(g, c, a, rc, win, tab, lane, r, has, k_lo, k_hi, kmin, kmax, seg, ks, geo, strat_lo, strat_sp, dep); \
     } while (0)
     if (m == 0) VOXE_T4_MARCH(0);
     else if (m == 1) VOXE_T4_MARCH(1);
@@ -1549,6 +1626,11 @@ __global__ __launch_bounds__(64, KL >= 9 ? 2 : (PREC ? VOXE_TILE4_LB_PREC : VOXE
 }
 __global__ __launch_bounds__(64, VOXE_TILE4_LB) void render_bwd_tile4_plan_kernel(const DevGrid g, const DevCfg c, const Tile4Args a_in) {
   render_bwd_tile4_body<8, false, 0, kPlanBuild>(g, c, a_in);
+}
+// ... and the planned kernel of launches with UniHeadline's configuration (softplus, white background, both gradients, no
+// truncation): the same body, the launch-uniform switches resolved at compile time
+__global__ __launch_bounds__(64, VOXE_TILE4_LB) void render_bwd_tile4_plan_sw_kernel(const DevGrid g, const DevCfg c, const Tile4Args a_in) {
+  render_bwd_tile4_body<8, false, 0, kPlanBuild, UniHeadline>(g, c, a_in);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1764,7 +1846,7 @@ __global__ __launch_bounds__(64, VOXE_FWD4_LB) void render_fwd_tile4_kernel(cons
 constexpr int kF4Ring = VOXE_FWD4W_RING;   // layers of the texel ring (6 KB)
 constexpr int kF4Table = 64;               // layers tabulated per block: keys key0 .. key0 + 63
 
-template <int M, bool WIN, bool PREC>
+template <int M, bool WIN, bool PREC, class UNI>
 __device__ __forceinline__ void fwd4w_march(const DevGrid& g, const DevCfg& c, const float* __restrict__ packed, RayCtx<3, 1, 1>& rc,
                                             const int lane, const bool has, const int k_lo, const int k_hi, const int kmin,
                                             const int kmax, const int ks, const int ke, const int ref, float4* __restrict__ tex,
@@ -1791,6 +1873,7 @@ __device__ __forceinline__ void fwd4w_march(const DevGrid& g, const DevCfg& c, c
   const unsigned sxi = (unsigned)(g.Y * g.Z) * TB, syi = (unsigned)g.Z * TB;
   const char* const pbytes = reinterpret_cast<const char*>(packed);
   const int Sm1 = c.S - 1;
+  const int post_act = UNI::post_act(g);
   // ---- window geometry from the reference ray, per-layer table, first layers (as fwd_window_march) ----
   int sgn = 1, key0 = 0, base = 0, up0 = 0;
   const int N[3] = {g.X, g.Y, g.Z};
@@ -1936,7 +2019,7 @@ __device__ __forceinline__ void fwd4w_march(const DevGrid& g, const DevCfg& c, c
       float rad[COUT];
 #pragma unroll
       for (int ch = 0; ch < COUT; ++ch) rad[ch] = kC0 * fch[ch];
-      const float sigma = post_activate(g.post_act, v);
+      const float sigma = post_activate(post_act, v);
       const float dl = last ? kInfinity : (z_next - z);
       const float delta = dl * rc.dnorm;
       const float e = fast_exp(-(sigma * delta));
@@ -1962,7 +2045,7 @@ __device__ __forceinline__ void fwd4w_march(const DevGrid& g, const DevCfg& c, c
 // the schedule pass); the rays are loaded once, in the tile's final orientation.
 // The body is shared by the kernels below it: render_fwd_tile4w_kernel<PREC>, unplanned as ever, and render_fwd_tile4w_plan_kernel,
 // the planned instantiation of <false>.
-template <bool PREC, bool PLAN>
+template <bool PREC, bool PLAN, class UNI = UniGeneric>
 __device__ __forceinline__ void render_fwd_tile4w_body(const DevGrid g, const DevCfg c, const float* __restrict__ packed,
                                                        const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                        float* __restrict__ segbuf, double* __restrict__ segsum, const float fit_lat,
@@ -2035,10 +2118,10 @@ __device__ __forceinline__ void render_fwd_tile4w_body(const DevGrid g, const De
   float asum = 0.0f, dsum = 0.0f, T = 1.0f;
   double asum_d = 0.0, dsum_d = 0.0;
   if (kmin <= kmax) {   // wave-uniform
-    if (m == 0) fwd4w_march<0, true, PREC>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
-    else if (m == 1) fwd4w_march<1, true, PREC>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
-    else if (m == 2) fwd4w_march<2, true, PREC>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
-    else fwd4w_march<0, false, PREC>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
+    if (m == 0) fwd4w_march<0, true, PREC, UNI>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
+    else if (m == 1) fwd4w_march<1, true, PREC, UNI>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
+    else if (m == 2) fwd4w_march<2, true, PREC, UNI>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
+    else fwd4w_march<0, false, PREC, UNI>(g, c, packed, rc, lane, has, k_lo, k_hi, kmin, kmax, ks, ke, ref, tex, org, csum, csum_d, asum, dsum, T, asum_d, dsum_d);
   }
   if (!alive) return;
   if constexpr (PREC) {
@@ -2075,6 +2158,15 @@ __global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_plan_kern
                                                                                    const int2* __restrict__ plan) {
   render_fwd_tile4w_body<false, true>(g, c, packed, rays_o, rays_d, segbuf, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, nullptr, plan);
 }
+// ... and of softplus grids (UniHeadline: the post-activation is all of it the forward reads)
+__global__ __launch_bounds__(64, VOXE_FWD4W_LB) void render_fwd_tile4w_plan_sw_kernel(const DevGrid g, const DevCfg c,
+                                                                                      const float* __restrict__ packed,
+                                                                                      const float* __restrict__ rays_o,
+                                                                                      const float* __restrict__ rays_d,
+                                                                                      float* __restrict__ segbuf,
+                                                                                      const int2* __restrict__ plan) {
+  render_fwd_tile4w_body<false, true, UniHeadline>(g, c, packed, rays_o, rays_d, segbuf, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, nullptr, plan);
+}
 
 // the lean forward takes what the lean backward takes (the window width does not matter to it)
 bool fwd_tile4_supported(const DevGrid& g, const HostCfg& c, const FwdArgs& a, int cout, int ncm) {
@@ -2099,7 +2191,8 @@ void launch_fwd_tile4(const DevGrid& g, const HostCfg& c, const FwdArgs& a, hipS
     if (a.segsum_d) render_fwd_tile4w_kernel<true><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, a.segsum_d, fit_lat, fit_m, zdom, max_adv, sched);
     else if (plist) {   // a list and its plan were built: the planned instantiation
       g_plan_launches[0].fetch_add(1, std::memory_order_relaxed);
-      render_fwd_tile4w_plan_kernel<<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, plist);
+      if (VOXE_T4_UNI && uni_headline_fwd(g)) render_fwd_tile4w_plan_sw_kernel<<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, plist);
+      else render_fwd_tile4w_plan_kernel<<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, plist);
     } else render_fwd_tile4w_kernel<false><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, nullptr, fit_lat, fit_m, zdom, max_adv, sched);
   }
   else if (a.segsum_d) render_fwd_tile4_kernel<3, true><<<nb, 64, 0, st>>>(g, c, a.packed, a.rays_o, a.rays_d, a.segbuf, a.segsum_d);
@@ -2206,7 +2299,8 @@ void launch_bwd_tile4(const DevGrid& g, const HostCfg& c, const BwdArgs& a, int 
     if (kPlanBuild && t.sched && a.plan && tile_plan_bytes(c) > 0 && plan_fit_m == fit_m && plan_fit_lat == fit_lat) {
       t.plan = a.plan;
       g_plan_launches[1].fetch_add(1, std::memory_order_relaxed);
-      render_bwd_tile4_plan_kernel<<<nb, 64, 0, st>>>(g, c, t);
+      if (VOXE_T4_UNI && uni_headline_bwd(g, c, a.want_d, a.want_f)) render_bwd_tile4_plan_sw_kernel<<<nb, 64, 0, st>>>(g, c, t);
+      else render_bwd_tile4_plan_kernel<<<nb, 64, 0, st>>>(g, c, t);
     } else render_bwd_tile4_kernel<8, false><<<nb, 64, 0, st>>>(g, c, t);
   }
 }
