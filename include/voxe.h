@@ -1267,6 +1267,44 @@ int voxe_voxelize_mesh(const float* vertices, int64_t V, const int32_t* faces, i
                        void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-voxel Fisher information: how well a set of rays pins down each voxel's raw density.
+ * An added symbol is backward compatible: VOXE_ABI_VERSION stays 13.  No voxe_cpu_ twin; the float64 restatement is
+ * tests/fisher_ref.py.
+ *
+ * voxe_fisher_rays: the diagonal of J^T J of the rendered colours with respect to the raw densities, and its contraction with
+ *   a per-voxel variance.  The samples z_k, the inside test, sigma_k = post(v_k), delta_k = dl_k |d| (last dl = 1e10), T_k,
+ *   w_k = T_k alpha_k and rad_{k,ch} are those of voxe_render_fwd for the same rays, cfg and jitter / (seed, rng_offset) AT
+ *   term_eps = 0 (the whole ray is marched whatever cfg->term_eps says: a forward that cuts its march short has fewer samples):
+ *   SH evaluation on the ray direction, render_diffuse and every sh_degree 0 - 3 included.  With
+ *   q_{k,ch} = rad_{k,ch} - (white_bkgd ? 1 : 0), per ray r and colour channel ch:
+ *       E_{k,ch}    = q_{k,ch} (T_k - w_k) - sum_{i>k} w_i q_{i,ch}
+ *       J_{r,ch}[c] = pre'(scale raw_c) scale * sum_k delta_k E_{k,ch} post'(v_k) t_c(k)
+ *       fisher[c]  += sum_ch J_{r,ch}[c]^2                          once per ray
+ *       ray_var[r]  = sum_c P[c] sum_ch J_{r,ch}[c]^2               P = voxel_var, 1 when NULL
+ *   t_c = (wx * wy) * wz is the gather weight of corner c in sample k's cell, corners inside the grid only.  J_{r,ch} is the
+ *   d_densities of voxe_render_bwd for d_colour = e_ch on ray r alone, d_depth = d_acc = 0: the derivative conventions are
+ *   voxe_render_bwd's (post', pre' = sign for abs with sign(0) = 0, no suffix at the last sample and where 1 - alpha_k == 0).
+ *   The square sits INSIDE the sum over rays: no number of backward passes over several rays yields it.
+ *   Only white_bkgd is a background here; a learned environment map is ignored.  The features get no Fisher term.
+ *   fisher [X,Y,Z] ACCUMULATES (zero it before the first call) through float atomics: the order of the additions, and so the
+ *   last bits, may differ from run to run; a voxel no sample weighs keeps an exact 0.  ray_var [R] is OVERWRITTEN, summed per ray
+ *   in double by the ray's one lane without atomics: the same bits on every run, whatever the other rays of the launch, and
+ *   exactly 0 for a ray that misses the grid.  voxel_var is read only when ray_var is given.
+ *   cfg: term_eps (see above; voxe_render_bwd_rays' rule), deterministic, reuse_packed_grid, ray_state_valid and dispatch are
+ *   ignored; image_width / image_height only choose the ray -> thread mapping.  VOXE_FEAT_ATTN grids: VOXE_ERR_UNSUPPORTED.
+ *   Validation, the limits on R and the voxel count and the error codes are those of voxe_render_normals, plus
+ *   F == 3 (sh_degree + 1)^2 (VOXE_ERR_BAD_SHAPE) and a non-NULL grid->features (VOXE_ERR_NULL_POINTER).  R == 0 or both outputs
+ *   NULL: VOXE_OK with no launch.
+ *   The RAW API tensors (grid->densities, grid->features) are read: no workspace; no forward record or voxe_recon_prefetch hint
+ *   is read or dropped.  Caller's stream, no host synchronisation, no allocation.                                            */
+int voxe_fisher_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
+                     const float* rays_o, const float* rays_d, int64_t R, const float* jitter,
+                     float*       fisher     /* [X,Y,Z] or NULL: ACCUMULATES H (caller zeroes first) */,
+                     const float* voxel_var  /* [X,Y,Z] or NULL: P, read only for ray_var; NULL = 1 */,
+                     float*       ray_var    /* [R] or NULL: sum_c P[c] sum_ch J_{r,ch}[c]^2, overwritten */,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CPU twin == the oracle (oracle/voxe_cpu.c). Same semantics, HOST pointers, no stream/workspace.
  * TEST INFRASTRUCTURE ONLY: never linked into libvoxe_hip.so, never called by the product path.
  * ---------------------------------------------------------------------------------------------- */

@@ -1821,6 +1821,24 @@ int voxe_render_bwd_rays_debug_lanes(int32_t lanes) {
   return VOXE_OK;
 }
 
+// ---- per-voxel Fisher information ---------------------------------------------------------------------------
+int voxe_fisher_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
+                     const float* jitter, float* fisher, const float* voxel_var, float* ray_var, void* stream) {
+  if (const int st = sampling_call_shape(grid, cfg, R)) return st;
+  if (grid->feature_kind != VOXE_FEAT_SH || cfg->sh_degree < 0 || cfg->sh_degree > 3) return VOXE_ERR_UNSUPPORTED;
+  if (grid->F != 3 * (cfg->sh_degree + 1) * (cfg->sh_degree + 1)) return VOXE_ERR_BAD_SHAPE;
+  if (const int se = grid_extent_status(grid, grid->F + 1)) return se;
+  if (!grid->features) return VOXE_ERR_NULL_POINTER;
+  DevGrid dg;
+  DevCfg dc;
+  if (const int st = sampling_call_rays(grid, cfg, R, rays_o, rays_d, &dg, &dc)) return st;
+  if (R == 0 || (!fisher && !ray_var)) return VOXE_OK;
+  dc.white = cfg->white_bkgd;
+  launch_fisher_rays(dg, dc, cfg->sh_degree, cfg->render_diffuse, grid->densities, grid->features, rays_o, rays_d, jitter, fisher,
+                     voxel_var, ray_var, (hipStream_t)stream);
+  return finish();
+}
+
 size_t voxe_cast_rays_bwd_scratch_bytes(int32_t K) { return cast_rays_bwd_scratch_bytes(K); }
 
 int voxe_cast_rays_bwd(int32_t H, int32_t W, float focal, const float* poses, int32_t K, const int64_t* flat_index, int64_t B,

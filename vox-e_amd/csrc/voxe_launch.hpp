@@ -290,6 +290,11 @@ extern thread_local int tl_rays_bwd_lanes;   // test aid (voxe_render_bwd_rays_d
 void launch_render_rays_bwd(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const float* dens, const float* feat,
                             const float* rays_o, const float* rays_d, const float* jitter, const float* g_col,
                             const float* g_depth, const float* g_acc, float* d_o, float* d_d, int accumulate, hipStream_t st);
+// voxe_fisher.hip: per-voxel Fisher information of the rendered colours w.r.t. the raw densities; reads the raw
+// densities and features, no workspace; float atomics into `fisher`, none for `ray_var`
+void launch_fisher_rays(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const float* dens, const float* feat,
+                        const float* rays_o, const float* rays_d, const float* jitter, float* fisher, const float* voxel_var,
+                        float* ray_var, hipStream_t st);
 // voxe_grid_ops.hip: chain rule of the ray casting into the poses and the focal length (13 doubles per camera in `scratch`)
 size_t cast_rays_bwd_scratch_bytes(int K);
 hipError_t launch_cast_rays_bwd(int H, int W, float focal, const float* poses, int K, const long long* flat_index, long long B,

@@ -303,6 +303,8 @@ HIP_ONLY = {
     "voxelize_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "voxelize_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                 C.POINTER(C.c_float), C.c_float, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    # per-voxel Fisher information of the rendered colours (additive, still ABI v13)
+    "fisher_rays": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
 }
 
 CPU_ONLY = {

@@ -690,3 +690,34 @@ def render_bwd_rays(spec: GridSpec, params: RenderParams, densities: torch.Tenso
     wrote(d_rays_o, d_rays_d)
     return d_o, d_d
 
+
+# ------------------------------------------------------------------------------------------------
+# per-voxel Fisher information: reads the raw grid tensors only, no workspace, not differentiable
+# ------------------------------------------------------------------------------------------------
+def fisher_rays_(spec: GridSpec, params: RenderParams, densities: torch.Tensor, features: torch.Tensor, rays_o: torch.Tensor,
+                 rays_d: torch.Tensor, fisher: Optional[torch.Tensor] = None, voxel_var: Optional[torch.Tensor] = None,
+                 want_ray_var: bool = False, jitter: Optional[torch.Tensor] = None, rng: Tuple[int, int] = (0, 0)):
+    """voxe_fisher_rays: add, in place, to `fisher` ([X,Y,Z] or [X,Y,Z,1] float32, contiguous; zero it before the first call)
+    the diagonal Fisher information sum_rays sum_ch (d colour_{r,ch} / d raw density)^2 of the flat rays, with the samples,
+    weights and SH colours `render` uses for the same params, jitter and rng.  want_ray_var: also return ray_var [R] =
+    sum_c voxel_var[c] sum_ch J_{r,ch}[c]^2 (voxel_var [X,Y,Z] or [X,Y,Z,1]; None = 1), bit-reproducible; otherwise None.
+    With neither output nothing is launched."""
+    _validate_inputs(densities, features, rays_o, rays_d, jitter, params)
+    device = densities.device
+    ensure_gfx950(device)
+    for name, t in (("fisher", fisher), ("voxel_var", voxel_var)):
+        if t is not None:
+            _require_buffer("fisher_rays_", name, t, shape=densities.shape if t.dim() == 4 else densities.shape[:3],
+                            numel=densities.numel(), device=device)
+    dens, feat = f32c(densities.detach()), f32c(features.detach())
+    ro, rd = f32c(rays_o.detach()), f32c(rays_d.detach())
+    jit = None if jitter is None else f32c(jitter.detach())
+    R = ro.shape[0]
+    g, c = _descs(spec, params, dens, feat, rng[0], rng[1], False)
+    with torch.cuda.device(device):
+        ray_var = torch.empty((R,), dtype=torch.float32, device=device) if want_ray_var else None
+        check(lib().voxe_fisher_rays(C.byref(g), C.byref(c), ptr(ro), ptr(rd), R, ptr(jit), ptr(fisher),
+                                     ptr(voxel_var) if want_ray_var else None, ptr(ray_var), stream_ptr(device)),
+              "voxe_fisher_rays")
+    wrote(fisher)
+    return ray_var
