@@ -1,22 +1,27 @@
 #!/usr/bin/env python3
-"""Bit digests of the five calls that share the density-only sample march (voxe_ray_march.hpp):
-render_normals, visibility_accumulate_, lift_accumulate_, distortion_fwd_bwd and render_bwd_rays on seeded inputs, one
-`sha256 name` line per output tensor.  Two trees whose kernels compute the same bits print the same lines, so a change of the
+"""Bit digests of calls that share the density-only sample march (voxe_ray_march.hpp lists them all):
+render_normals, visibility_accumulate_, lift_accumulate_, render_bwd_rays and the three ray losses distortion_fwd_bwd,
+depth_fwd_bwd and orientation_fwd_bwd on seeded inputs, one `sha256 name` line per output tensor.  Two trees whose kernels compute the same bits print the same lines, so a change of the
 shared march is checked by running this file in both trees and comparing the outputs line for line.
 
 Inputs: a 26 x 20 x 23 grid (identity / softplus, scale 2.0), three ray sets -- (a) 21 x 13 pixels x 3 views in image order with
 image_height set (no side a multiple of a tile side), (b) the same rays without image fields, (c) (a)'s rays shuffled -- each at
-S = 33 and S = 96 under five depth modes (plain, hash jitter, caller jitter, aabb_clip, linear disparity).  Distortion and the
+S = 33 and S = 96 under five depth modes (plain, hash jitter, caller jitter, aabb_clip, linear disparity).  The ray losses and the
 ray gradients run at every pinned lanes-per-ray split, lifting in both merge modes with C in {0, 1, 3, 8}; normals add one launch
-at 400^2 / 600^2 / 800^2 / 1040^2 pixels (8 / 4 / 2 / 1 lanes per ray).  Only outputs that are bit-stable are digested: the
-distortion gradient goes through float atomics, so it is taken from 64 single-ray calls at one lane per ray that accumulate on
-one stream.  The sets (a), (b), (c) are also compared with each other per ray (exit status 1 on a difference).
+at 400^2 / 600^2 / 800^2 / 1040^2 pixels (8 / 4 / 2 / 1 lanes per ray).  The depth loss has target depths in [NEAR, FAR] and
+widths in [0.02, 0.2]; it and the orientation loss (normal_eps 0 and 1e-2) run with ray weights in [0, 2), every seventh exactly
+0, and without.  Only outputs that are bit-stable are digested: a loss's gradient goes through float atomics, so it is taken from
+64 single-ray calls at one lane per ray that accumulate on one stream.  The sets (a), (b), (c) are also compared with each other per ray (exit status 1 on a difference).
 
-    python tools/ray_march_digest.py [--out FILE]
+--fold: FILE gets one line per call and input set, `sha256 name (n tensors)`, the sha256 of that group's per-tensor lines (which
+are printed either way).
+
+    python tools/ray_march_digest.py [--out FILE] [--fold]
 """
 import argparse
 import hashlib
 import os
+import re
 import sys
 
 import torch
@@ -32,6 +37,8 @@ DIMS = (26, 20, 23)
 AABB = ((-1.3, 1.2), (-1.0, 1.1), (-1.4, 1.0))
 W, H, VIEWS = 21, 13, 3
 LANES = (1, 2, 4, 8)
+# the group of a line under --fold: call, S, mode and ray set (and, for a loss that takes ray weights, whether it got them)
+GROUP = re.compile(r"(.+?_S\d+(_[a-z]+_[abc](_(un)?weighted)?)?)_")
 # name -> (RenderParams fields, jitter kind): caller jitter follows a ray through the shuffle, the hash stream follows the index
 MODES = {
     "plain": (dict(), None),
@@ -55,6 +62,7 @@ def cameras(h, w, n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fold", action="store_true")
     a = ap.parse_args()
     lines, unequal = [], []
 
@@ -71,6 +79,22 @@ def main():
     perm = torch.randperm(R, generator=g).to(DEV)
     values = torch.empty((R, 8)).uniform_(-1, 1, generator=g).to(DEV)
     g_col, g_dep, g_acc = (torch.randn((R, n), generator=g).to(DEV) for n in (3, 1, 1))
+    # the depth and orientation losses: their per-ray inputs from a copy of the generator (the draws of the calls above stay as
+    # they were), and call(params, o, d, jit, rng, target_depth, target_sigma, ray_weight, **kw) per loss
+    gl = torch.Generator()
+    gl.set_state(g.get_state())
+    t_depth = torch.empty(R).uniform_(workload.NEAR, workload.FAR, generator=gl).to(DEV)
+    t_sigma = torch.empty(R).uniform_(0.02, 0.2, generator=gl).to(DEV)
+    r_weight = torch.empty(R).uniform_(0, 2, generator=gl)
+    r_weight[::7] = 0.0
+    r_weight = r_weight.to(DEV)
+    ray_losses = {
+        "depth": lambda P, o, d, jit, rng, td, ts, w, **kw: ops.depth_fwd_bwd(spec, P, dens, o, d, td, ts, w, jit, rng, **kw),
+        "orientation_eps0": lambda P, o, d, jit, rng, td, ts, w, **kw: ops.orientation_fwd_bwd(spec, P, dens, o, d, w, jit, rng,
+                                                                                              normal_eps=0.0, **kw),
+        "orientation_eps1e-2": lambda P, o, d, jit, rng, td, ts, w, **kw: ops.orientation_fwd_bwd(spec, P, dens, o, d, w, jit, rng,
+                                                                                                 normal_eps=1e-2, **kw),
+    }
     # per-ray tensors of a set: (a) and (b) as they are, (c) permuted
     sets = {"a": (dict(image_width=W, image_height=H), None), "b": (dict(), None), "c": (dict(), perm)}
 
@@ -92,7 +116,7 @@ def main():
         jit_rows = torch.rand((R, S), generator=g).to(DEV)
         for mode, (fields, jkind) in MODES.items():
             rng = (1234, 77) if jkind == "hash" else (0, 0)
-            out = {k: {} for k in ("normals", "distortion", "rays")}
+            out = {k: {} for k in ("normals", "distortion", "rays", *ray_losses)}
             for sname, (image, p) in sets.items():
                 if jkind == "hash" and sname == "c":
                     continue      # (the hash stream follows the ray's index: a shuffled ray is another ray)
@@ -135,14 +159,32 @@ def main():
                     out["distortion"].setdefault(sname, []).append(ray)
                     out["rays"].setdefault(sname, []).extend([d_o, d_d])
                 # the distortion gradient where float adds cannot race: one ray per call, one lane per ray, one stream
+                one = ops.RenderParams(**{**vars(params), "image_width": 0, "image_height": 0})
+
+                def row(t, r):
+                    return None if t is None else t[r:r + 1].contiguous()
+
                 if sname == "a":
-                    one = ops.RenderParams(**{**vars(params), "image_width": 0, "image_height": 0})
                     dd = torch.zeros_like(dens)
                     for r in range(64):      # (to the hash stream every one of them is ray 0 of its launch)
-                        ops.distortion_fwd_bwd(spec, one, dens, o[r:r + 1].contiguous(), d[r:r + 1].contiguous(),
-                                               None if jit is None else jit[r:r + 1].contiguous(), rng, want_loss=False,
+                        ops.distortion_fwd_bwd(spec, one, dens, row(o, r), row(d, r), row(jit, r), rng, want_loss=False,
                                                d_densities=dd, accumulate=True, lanes=1)
                     emit(f"distortion_{tag}_G1_d_densities_64_single_ray_calls", dd)
+                # the depth and orientation losses the same way, with the ray weights and without
+                td, ts, rw = (of_set(t, p) for t in (t_depth, t_sigma, r_weight))
+                for lname, call in ray_losses.items():
+                    for wname, w in (("weighted", rw), ("unweighted", None)):
+                        for lanes in LANES:
+                            loss, ray = call(params, o, d, jit, rng, td, ts, w, want_loss=True, want_ray_loss=True, lanes=lanes)
+                            emit(f"{lname}_{tag}_{wname}_G{lanes}_loss", loss)
+                            emit(f"{lname}_{tag}_{wname}_G{lanes}_ray_loss", ray)
+                            out[lname].setdefault(sname, []).append(ray)
+                        if sname == "a":
+                            dd = torch.zeros_like(dens)
+                            for r in range(64):
+                                call(one, row(o, r), row(d, r), row(jit, r), rng, row(td, r), row(ts, r), row(w, r), want_loss=False,
+                                     d_densities=dd, accumulate=True, lanes=1)
+                            emit(f"{lname}_{tag}_{wname}_G1_d_densities_64_single_ray_calls", dd)
             if jkind != "hash":
                 for call, per_set in out.items():
                     same_per_ray(f"{call}_S{S}_{mode}", per_set)
@@ -158,6 +200,11 @@ def main():
         for n, t in zip(("normals", "depth", "acc"), ops.render_normals(spec, params, dens, o, d, rng=(0, 0))):
             emit(f"normals_{hw}x{hw}_S64_{n}", t)
     torch.cuda.synchronize()
+    if a.fold:
+        groups = {}
+        for line in lines:
+            groups.setdefault(GROUP.match(line.split(" ", 1)[1]).group(1), []).append(line)
+        lines = [f"{hashlib.sha256(chr(10).join(m).encode()).hexdigest()} {name} ({len(m)} tensors)" for name, m in groups.items()]
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:

@@ -1467,7 +1467,7 @@ static void sampling_cfg_to_dev(const VoxeRenderCfg* cfg, int64_t R, DevCfg* out
   }
 }
 
-// The prologue of the five calls that march the forward's samples over the raw densities (voxe_ray_march.hpp), in two steps
+// The prologue of the calls that march the forward's samples over the raw densities (voxe_ray_march.hpp lists them), in two steps
 // so that a call can put checks of its own between them: the grid, cfg and the R / num_samples range ...
 static int sampling_call_shape(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int64_t R) {
   const int st = validate_normals_grid(grid);
@@ -1489,8 +1489,12 @@ static int sampling_call(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, int
   const int st = sampling_call_shape(grid, cfg, R);
   return st ? st : sampling_call_rays(grid, cfg, R, rays_o, rays_d, dg, dc);
 }
-// lanes per ray a *_debug_lanes test aid may pin (0: the library's choice)
-static bool lanes_ok(int32_t lanes) { return lanes == 0 || lanes == 1 || lanes == 2 || lanes == 4 || lanes == 8; }
+// a *_debug_lanes test aid: the lanes per ray it may pin (0: the library's choice) into that call's pin
+static int pin_lanes(int* pin, int32_t lanes) {
+  if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8) return VOXE_ERR_BAD_SHAPE;
+  *pin = lanes;
+  return VOXE_OK;
+}
 
 int voxe_query_normals(const VoxeGridDesc* grid, const float* points, int64_t N, float* normals, void* stream) {
   const int st = validate_normals_grid(grid);
@@ -1558,8 +1562,24 @@ int voxe_lift_debug_merge(int32_t mode) {
   return VOXE_OK;
 }
 
+// ---- the density ray losses ("What the ray losses share") ---------------------------------------------------
+// The common tail of their entries, behind an entry's own checks: the scratch of the mean, the clear of d_densities when the
+// call does not accumulate, and the call that has nothing to launch.  *done: the entry returns the status
+static int ray_loss_outputs_ready(const VoxeGridDesc* grid, int64_t R, const float* loss_out, const float* ray_loss,
+                                  float* d_densities, int32_t accumulate, const void* scratch, size_t scratch_bytes, void* stream,
+                                  bool* done) {
+  *done = true;
+  if (R > 0 && loss_out && (!scratch || scratch_bytes < ray_loss_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
+  const bool clear = d_densities && !accumulate;
+  if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
+    return VOXE_ERR_LAUNCH;
+  if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
+  *done = false;
+  return VOXE_OK;
+}
+
 // ---- distortion loss on rays -----------------------------------------------------------------------
-size_t voxe_distortion_scratch_bytes(int64_t R) { return distortion_scratch_bytes(R); }
+size_t voxe_distortion_scratch_bytes(int64_t R) { return ray_loss_scratch_bytes(R); }
 
 int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
                             const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_densities,
@@ -1568,24 +1588,18 @@ int voxe_distortion_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, 
   DevCfg dc;
   const int st = sampling_call(grid, cfg, R, rays_o, rays_d, &dg, &dc);
   if (st) return st;
-  if (R > 0 && loss_out && (!scratch || scratch_bytes < distortion_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
-  const bool clear = d_densities && !accumulate;
-  if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
-    return VOXE_ERR_LAUNCH;
-  if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
+  bool done;
+  const int sr = ray_loss_outputs_ready(grid, R, loss_out, ray_loss, d_densities, accumulate, scratch, scratch_bytes, stream, &done);
+  if (done) return sr;
   launch_distortion(dg, dc, grid->densities, rays_o, rays_d, jitter, grad_scale, loss_out, ray_loss, d_densities, scratch,
                     (hipStream_t)stream);
   return finish();
 }
 
-int voxe_distortion_debug_lanes(int32_t lanes) {
-  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
-  tl_distortion_lanes = lanes;
-  return VOXE_OK;
-}
+int voxe_distortion_debug_lanes(int32_t lanes) { return pin_lanes(&tl_lane_pins.distortion, lanes); }
 
 // ---- ray-termination loss towards depth targets --------------------------------------------------------
-size_t voxe_depth_scratch_bytes(int64_t R) { return depth_scratch_bytes(R); }
+size_t voxe_depth_scratch_bytes(int64_t R) { return ray_loss_scratch_bytes(R); }
 
 int voxe_depth_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,
                        const float* jitter, const float* target_depth, const float* target_sigma, const float* ray_weight, float eps,
@@ -1597,24 +1611,18 @@ int voxe_depth_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const
   if (st) return st;
   if (!(eps > 0.0f) || !std::isfinite(eps)) return VOXE_ERR_BAD_SHAPE;
   if (R > 0 && (!target_depth || !target_sigma)) return VOXE_ERR_NULL_POINTER;
-  if (R > 0 && loss_out && (!scratch || scratch_bytes < depth_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
-  const bool clear = d_densities && !accumulate;
-  if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
-    return VOXE_ERR_LAUNCH;
-  if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
+  bool done;
+  const int sr = ray_loss_outputs_ready(grid, R, loss_out, ray_loss, d_densities, accumulate, scratch, scratch_bytes, stream, &done);
+  if (done) return sr;
   launch_depth(dg, dc, grid->densities, rays_o, rays_d, jitter, target_depth, target_sigma, ray_weight, eps, grad_scale, loss_out,
                ray_loss, d_densities, scratch, (hipStream_t)stream);
   return finish();
 }
 
-int voxe_depth_debug_lanes(int32_t lanes) {
-  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
-  tl_depth_lanes = lanes;
-  return VOXE_OK;
-}
+int voxe_depth_debug_lanes(int32_t lanes) { return pin_lanes(&tl_lane_pins.depth, lanes); }
 
 // ---- orientation loss on rays -----------------------------------------------------------------------------
-size_t voxe_orientation_scratch_bytes(int64_t R) { return orientation_scratch_bytes(R); }
+size_t voxe_orientation_scratch_bytes(int64_t R) { return ray_loss_scratch_bytes(R); }
 
 int voxe_orientation_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d,
                              int64_t R, const float* jitter, const float* ray_weight, float normal_eps, float grad_scale,
@@ -1625,21 +1633,15 @@ int voxe_orientation_fwd_bwd(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
   const int st = sampling_call(grid, cfg, R, rays_o, rays_d, &dg, &dc);
   if (st) return st;
   if (!(normal_eps >= 0.0f) || !std::isfinite(normal_eps)) return VOXE_ERR_BAD_SHAPE;
-  if (R > 0 && loss_out && (!scratch || scratch_bytes < orientation_scratch_bytes(R))) return VOXE_ERR_WORKSPACE;
-  const bool clear = d_densities && !accumulate;
-  if (clear && hipMemsetAsync(d_densities, 0, sizeof(float) * (size_t)grid->X * grid->Y * grid->Z, (hipStream_t)stream) != hipSuccess)
-    return VOXE_ERR_LAUNCH;
-  if (R == 0 || (!loss_out && !ray_loss && !d_densities)) return clear ? finish() : VOXE_OK;
+  bool done;
+  const int sr = ray_loss_outputs_ready(grid, R, loss_out, ray_loss, d_densities, accumulate, scratch, scratch_bytes, stream, &done);
+  if (done) return sr;
   launch_orientation(dg, dc, grid->densities, rays_o, rays_d, jitter, ray_weight, normal_eps, grad_scale, loss_out, ray_loss,
                      d_densities, scratch, (hipStream_t)stream);
   return finish();
 }
 
-int voxe_orientation_debug_lanes(int32_t lanes) {
-  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
-  tl_orientation_lanes = lanes;
-  return VOXE_OK;
-}
+int voxe_orientation_debug_lanes(int32_t lanes) { return pin_lanes(&tl_lane_pins.orientation, lanes); }
 
 // ---- per-image exposure compensation ----------------------------------------------------------------------
 namespace {
@@ -1815,11 +1817,7 @@ int voxe_render_bwd_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, con
   return finish();
 }
 
-int voxe_render_bwd_rays_debug_lanes(int32_t lanes) {
-  if (!lanes_ok(lanes)) return VOXE_ERR_BAD_SHAPE;
-  tl_rays_bwd_lanes = lanes;
-  return VOXE_OK;
-}
+int voxe_render_bwd_rays_debug_lanes(int32_t lanes) { return pin_lanes(&tl_lane_pins.rays_bwd, lanes); }
 
 // ---- per-voxel Fisher information ---------------------------------------------------------------------------
 int voxe_fisher_rays(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg, const float* rays_o, const float* rays_d, int64_t R,

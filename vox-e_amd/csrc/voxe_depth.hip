@@ -27,8 +27,7 @@
 // Running sums are double (the suffix is a difference of sums), the per-sample work is float, as in voxe_distortion.hip.
 #include <hip/hip_runtime.h>
 
-#include "voxe_launch.hpp"
-#include "voxe_ray_march.hpp"
+#include "voxe_ray_loss.hpp"
 
 namespace voxe {
 namespace {
@@ -129,11 +128,7 @@ __global__ __launch_bounds__(kDepthThreads) void depth_kernel(DevGrid g, DevCfg 
     v = __shfl_down(v, 1, G);
     GWbehind = j == G - 1 ? 0.0 : v;
   }
-  if (valid && j == 0 && ray_loss) ray_loss[r] = (float)Ltot;
-  if (partial) {
-    const double s = block_sum((valid && j == 0) ? (double)omega * Ltot : 0.0);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
-  }
+  ray_loss_outputs(valid, j, r, Ltot, omega, ray_loss, partial);
   if constexpr (GRAD) {
     const float gs = gscale * omega;
     if (!reached || !(Ctot > 0.0) || gs == 0.0f) return;   // (no c_k, or no weight: the ray's gradient is exactly 0)
@@ -155,52 +150,25 @@ __global__ __launch_bounds__(kDepthThreads) void depth_kernel(DevGrid g, DevCfg 
       const double suffix = (st.last || !(s.om > 0.0f)) ? 0.0 : (GWbehind + (GW - GWrun));
       const float dsig = s.delta * (float)((double)(gk * (T * s.e)) - suffix);   // T e = T - w
       const float dv = (dsig * s.dpost) * gs;
-      if (dv != 0.0f) {   // adding exact zeros is skipped
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const float gq = (dv * s.t[q]) * pre_activate_grad(g.pre_act, tp.raw[q], g.density_scale);
-          if (gq != 0.0f) atomicAdd(d_dens + tp.idx[q], gq);
-        }
-      }
+      if (dv != 0.0f) deposit_corners(g, tp, d_dens, [&](int q) { return dv * s.t[q]; });   // adding exact zeros is skipped
       return s.om;   // (T ends: every later term is 0)
     });
   }
 }
 
-template <int G>
-void launch_depth_t(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
-                    const float* jitter, const float* tdepth, const float* tsigma, const float* rweight, float eps, float gscale,
-                    float* loss_out, float* ray_loss, float* d_dens, void* scratch, hipStream_t st) {
-  const long long nb = group_blocks<WaveRectTile<G>>(c);
-  double* partial = loss_out ? (double*)scratch : nullptr;
-  const float inv_eps = 1.0f / eps;
-  const double neg_log_eps = -log((double)eps);
-  if (d_dens)
-    depth_kernel<G, true><<<(unsigned)nb, kDepthThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, tdepth, tsigma, rweight, eps,
-                                                                  inv_eps, neg_log_eps, gscale, ray_loss, partial, d_dens);
-  else
-    depth_kernel<G, false><<<(unsigned)nb, kDepthThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, tdepth, tsigma, rweight, eps,
-                                                                   inv_eps, neg_log_eps, gscale, ray_loss, partial, d_dens);
-  if (loss_out) launch_partial_mean(partial, nb, c.R, loss_out, st);
-}
-
 }  // namespace
-
-thread_local int tl_depth_lanes = 0;
-
-// one partial per block, and a launch never has more blocks than rays (every pixel tile holds at least one pixel)
-size_t depth_scratch_bytes(long long R) { return sizeof(double) * (size_t)(R > 0 ? R : 0) + 256; }
 
 void launch_depth(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                   const float* jitter, const float* tdepth, const float* tsigma, const float* rweight, float eps, float grad_scale,
                   float* loss_out, float* ray_loss, float* d_dens, void* scratch, hipStream_t st) {
-  const float gscale = (float)((double)grad_scale / (double)c.R);
-  switch (lanes_per_ray(c.R, tl_depth_lanes)) {
-    case 1: launch_depth_t<1>(g, c, dens, rays_o, rays_d, jitter, tdepth, tsigma, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    case 2: launch_depth_t<2>(g, c, dens, rays_o, rays_d, jitter, tdepth, tsigma, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    case 4: launch_depth_t<4>(g, c, dens, rays_o, rays_d, jitter, tdepth, tsigma, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    default: launch_depth_t<8>(g, c, dens, rays_o, rays_d, jitter, tdepth, tsigma, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-  }
+  const float inv_eps = 1.0f / eps;
+  const double neg_log_eps = -log((double)eps);
+  launch_ray_loss(c, tl_lane_pins.depth, grad_scale, loss_out, d_dens, scratch, st,
+                  [&](auto G, auto GRAD, long long nb, float gscale, double* partial) {
+                    depth_kernel<G(), GRAD()><<<(unsigned)nb, kDepthThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, tdepth, tsigma,
+                                                                                      rweight, eps, inv_eps, neg_log_eps, gscale,
+                                                                                      ray_loss, partial, d_dens);
+                  });
 }
 
 }  // namespace voxe

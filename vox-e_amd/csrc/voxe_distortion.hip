@@ -25,8 +25,7 @@
 // per-sample work (gather, activations, fast_exp, T) is float, as in the renderer.
 #include <hip/hip_runtime.h>
 
-#include "voxe_launch.hpp"
-#include "voxe_ray_march.hpp"
+#include "voxe_ray_loss.hpp"
 
 namespace voxe {
 namespace {
@@ -90,11 +89,7 @@ __global__ __launch_bounds__(kDistThreads) void distortion_kernel(DevGrid g, Dev
     WMtot = __shfl(bi, G - 1, G);
     Ltot = __shfl(li, G - 1, G);
   }
-  if (valid && j == 0 && ray_loss) ray_loss[r] = (float)Ltot;
-  if (partial) {
-    const double s = block_sum((valid && j == 0) ? Ltot : 0.0);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
-  }
+  ray_loss_outputs(valid, j, r, Ltot, 1.0f, ray_loss, partial);
   if constexpr (GRAD) {
     if (!valid || k_lo > k_hi || !(Ts > 0.0f)) return;
     T = Ts;
@@ -114,19 +109,13 @@ __global__ __launch_bounds__(kDistThreads) void distortion_kernel(DevGrid g, Dev
       const double suffix = (st.last || !(s.om > 0.0f)) ? 0.0 : (total - GW);
       const float dsig = s.delta * (float)(gi * (double)(T * s.e) - suffix);   // T e = T - w
       const float dv = (dsig * s.dpost) * gscale;
-      if (dv != 0.0f) {   // adding exact zeros is skipped
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const float gq = (dv * s.t[q]) * pre_activate_grad(g.pre_act, tp.raw[q], g.density_scale);
-          if (gq != 0.0f) atomicAdd(d_dens + tp.idx[q], gq);
-        }
-      }
+      if (dv != 0.0f) deposit_corners(g, tp, d_dens, [&](int q) { return dv * s.t[q]; });   // adding exact zeros is skipped
       return s.om;   // (T ends: every later term is 0)
     });
   }
 }
 
-// loss = (sum of the per-block partials, fixed order) / R
+// loss = (sum of the per-block partials, fixed order) / R; launch_partial_mean() below serves every ray loss (voxe_ray_loss.hpp)
 __global__ __launch_bounds__(kDistThreads) void distortion_finalize_kernel(const double* __restrict__ partial, long long nb,
                                                                            double inv_R, float* __restrict__ loss_out) {
   double s = 0.0;
@@ -135,42 +124,23 @@ __global__ __launch_bounds__(kDistThreads) void distortion_finalize_kernel(const
   if (threadIdx.x == 0) *loss_out = (float)(tot * inv_R);
 }
 
-template <int G>
-void launch_distortion_t(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
-                         const float* jitter, float gscale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
-                         hipStream_t st) {
-  const long long nb = group_blocks<WaveRectTile<G>>(c);
-  double* partial = loss_out ? (double*)scratch : nullptr;
-  if (d_dens)
-    distortion_kernel<G, true><<<(unsigned)nb, kDistThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, gscale, ray_loss,
-                                                                      partial, d_dens);
-  else
-    distortion_kernel<G, false><<<(unsigned)nb, kDistThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, gscale, ray_loss,
-                                                                       partial, d_dens);
-  if (loss_out) launch_partial_mean(partial, nb, c.R, loss_out, st);
-}
-
 }  // namespace
 
 void launch_partial_mean(const double* partial, long long nb, long long R, float* loss_out, hipStream_t st) {
   distortion_finalize_kernel<<<1, kDistThreads, 0, st>>>(partial, nb, 1.0 / (double)R, loss_out);
 }
 
-thread_local int tl_distortion_lanes = 0;
-
 // one partial per block, and a launch never has more blocks than rays (every pixel tile holds at least one pixel)
-size_t distortion_scratch_bytes(long long R) { return sizeof(double) * (size_t)(R > 0 ? R : 0) + 256; }
+size_t ray_loss_scratch_bytes(long long R) { return sizeof(double) * (size_t)(R > 0 ? R : 0) + 256; }
 
 void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                        const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
                        hipStream_t st) {
-  const float gscale = (float)((double)grad_scale / (double)c.R);
-  switch (lanes_per_ray(c.R, tl_distortion_lanes)) {
-    case 1: launch_distortion_t<1>(g, c, dens, rays_o, rays_d, jitter, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    case 2: launch_distortion_t<2>(g, c, dens, rays_o, rays_d, jitter, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    case 4: launch_distortion_t<4>(g, c, dens, rays_o, rays_d, jitter, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    default: launch_distortion_t<8>(g, c, dens, rays_o, rays_d, jitter, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-  }
+  launch_ray_loss(c, tl_lane_pins.distortion, grad_scale, loss_out, d_dens, scratch, st,
+                  [&](auto G, auto GRAD, long long nb, float gscale, double* partial) {
+                    distortion_kernel<G(), GRAD()><<<(unsigned)nb, kDistThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, gscale,
+                                                                                          ray_loss, partial, d_dens);
+                  });
 }
 
 }  // namespace voxe

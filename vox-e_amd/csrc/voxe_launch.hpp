@@ -222,8 +222,14 @@ void launch_mesh_count(const VoxeGridDesc* g, float L, const uint8_t* mask, int6
 void launch_mesh_emit(const VoxeGridDesc* g, float L, const uint8_t* mask, float* vertices, long long max_vertices,
                       int32_t* faces, long long max_faces, void* scratch, hipStream_t st);
 
-// The five calls below that take a DevCfg march the forward's samples over the raw densities with voxe_ray_march.hpp
-// (DESIGN.md 4.17); lanes per ray, where a call splits its rays, are lanes_per_ray() there.
+// The calls below that take a DevCfg march the forward's samples over the raw densities with voxe_ray_march.hpp (DESIGN.md
+// 4.17, the list is there); lanes per ray, where a call splits its rays, are lanes_per_ray() there.
+// Test aids (voxe_*_debug_lanes): != 0 pins the lanes per ray of that call on this thread; one pin per call, so that pinning
+// one call does not pin another
+struct LanePins {
+  int distortion, depth, orientation, rays_bwd;
+};
+inline thread_local LanePins tl_lane_pins{};
 // voxe_normals.hip: density-gradient normals; both read the raw densities only, no workspace
 void launch_query_normals(const DevGrid& g, const float* dens, const float* points, long long N, float* normals, hipStream_t st);
 void launch_render_normals(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
@@ -239,27 +245,20 @@ extern thread_local int tl_lift_merge;   // test aid (voxe_lift_debug_merge): 1 
 void launch_lift_accumulate(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                             const float* jitter, const float* values, int C, long long* sum_wv, long long* sum_w, hipStream_t st);
 
-// voxe_distortion.hip: distortion loss on rays, value + density gradient; reads the raw densities only
-extern thread_local int tl_distortion_lanes;   // test aid (voxe_distortion_debug_lanes): != 0 pins the lanes per ray
-size_t distortion_scratch_bytes(long long R);
+// The three density ray losses, value + density gradient in one call; each reads the raw densities only.  What they share is
+// voxe_ray_loss.hpp: `scratch` holds ray_loss_scratch_bytes(R) when loss_out is given
+size_t ray_loss_scratch_bytes(long long R);
+// *loss_out = (sum of `nb` per-block partials, fixed order) / R
+void launch_partial_mean(const double* partial, long long nb, long long R, float* loss_out, hipStream_t st);
+// voxe_distortion.hip: distortion loss on rays
 void launch_distortion(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                        const float* jitter, float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch,
                        hipStream_t st);
-// *loss_out = (sum of `nb` per-block partials, fixed order) / R  (distortion, depth and orientation)
-void launch_partial_mean(const double* partial, long long nb, long long R, float* loss_out, hipStream_t st);
-
-// voxe_depth.hip: ray-termination loss towards per-ray depth targets, value + density gradient; reads the raw
-// densities only
-extern thread_local int tl_depth_lanes;   // test aid (voxe_depth_debug_lanes): != 0 pins the lanes per ray
-size_t depth_scratch_bytes(long long R);
+// voxe_depth.hip: ray-termination loss towards per-ray depth targets
 void launch_depth(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                   const float* jitter, const float* target_depth, const float* target_sigma, const float* ray_weight, float eps,
                   float grad_scale, float* loss_out, float* ray_loss, float* d_dens, void* scratch, hipStream_t st);
-
-// voxe_orientation.hip: orientation loss on rays, value + density gradient through the weights and the normals (DESIGN.md
-// 4.20); reads the raw densities only
-extern thread_local int tl_orientation_lanes;   // test aid (voxe_orientation_debug_lanes): != 0 pins the lanes per ray
-size_t orientation_scratch_bytes(long long R);
+// voxe_orientation.hip: orientation loss on rays, the gradient through the weights and the normals
 void launch_orientation(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                         const float* jitter, const float* ray_weight, float normal_eps, float grad_scale, float* loss_out,
                         float* ray_loss, float* d_dens, void* scratch, hipStream_t st);
@@ -286,7 +285,6 @@ bool launch_robust(const float* x, const float* y, int N, int P, int C, bool l1,
 
 // voxe_render_rays_bwd.hip: gradient of a render w.r.t. its rays; reads the raw densities and features, no
 // workspace, no atomics
-extern thread_local int tl_rays_bwd_lanes;   // test aid (voxe_render_bwd_rays_debug_lanes): != 0 pins the lanes per ray
 void launch_render_rays_bwd(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const float* dens, const float* feat,
                             const float* rays_o, const float* rays_d, const float* jitter, const float* g_col,
                             const float* g_depth, const float* g_acc, float* d_o, float* d_d, int accumulate, hipStream_t st);

@@ -125,13 +125,6 @@ __global__ __launch_bounds__(kNormThreads) void render_normals_kernel(DevGrid g,
   if (acc) acc[r] = asum;
 }
 
-template <int G>
-void launch_render_normals_t(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
-                             const float* jitter, float* normals, float* depth, float* acc, hipStream_t st) {
-  const long long nb = group_blocks<BlockRectTile<G>>(c);
-  render_normals_kernel<G><<<(unsigned)nb, kNormThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, normals, depth, acc);
-}
-
 }  // namespace
 
 void launch_query_normals(const DevGrid& g, const float* dens, const float* points, long long N, float* normals,
@@ -142,12 +135,10 @@ void launch_query_normals(const DevGrid& g, const float* dens, const float* poin
 
 void launch_render_normals(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                            const float* jitter, float* normals, float* depth, float* acc, hipStream_t st) {
-  switch (lanes_per_ray(c.R, 0)) {
-    case 1: launch_render_normals_t<1>(g, c, dens, rays_o, rays_d, jitter, normals, depth, acc, st); break;
-    case 2: launch_render_normals_t<2>(g, c, dens, rays_o, rays_d, jitter, normals, depth, acc, st); break;
-    case 4: launch_render_normals_t<4>(g, c, dens, rays_o, rays_d, jitter, normals, depth, acc, st); break;
-    default: launch_render_normals_t<8>(g, c, dens, rays_o, rays_d, jitter, normals, depth, acc, st); break;
-  }
+  for_lanes(lanes_per_ray(c.R, 0), [&](auto G) {
+    const long long nb = group_blocks<BlockRectTile<G()>>(c);
+    render_normals_kernel<G()><<<(unsigned)nb, kNormThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, normals, depth, acc);
+  });
 }
 
 }  // namespace voxe

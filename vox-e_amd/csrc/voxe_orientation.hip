@@ -26,8 +26,7 @@
 // Running sums are double (the suffix is a difference of sums), the per-sample work is float, as in voxe_distortion.hip.
 #include <hip/hip_runtime.h>
 
-#include "voxe_launch.hpp"
-#include "voxe_ray_march.hpp"
+#include "voxe_ray_loss.hpp"
 
 namespace voxe {
 namespace {
@@ -115,11 +114,7 @@ __global__ __launch_bounds__(kOrientThreads) void orientation_kernel(DevGrid g, 
     v = __shfl_down(v, 1, G);
     Abehind = j == G - 1 ? 0.0 : v;
   }
-  if (valid && j == 0 && ray_loss) ray_loss[r] = (float)Ltot;
-  if (partial) {
-    const double s = block_sum((valid && j == 0) ? (double)omega * Ltot : 0.0);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
-  }
+  ray_loss_outputs(valid, j, r, Ltot, omega, ray_loss, partial);
   if constexpr (GRAD) {
     const float gsc = gscale * omega;
     // (no sample of the ray faces away with weight: both parts are exactly 0)
@@ -164,8 +159,7 @@ __global__ __launch_bounds__(kOrientThreads) void orientation_kernel(DevGrid g, 
             h[a][1] = dG * d1;
           }
         }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
+        deposit_corners(g, tp, d_dens, [&](int q) {
           const int bx = q & 1, by = (q >> 1) & 1, bz = q >> 2;
           float gq = dv * s.t[q];
           if (turned) {
@@ -173,47 +167,24 @@ __global__ __launch_bounds__(kOrientThreads) void orientation_kernel(DevGrid g, 
             gq = fmaf(h[1][by], cell.w[0][bx] * cell.w[2][bz], gq);
             gq = fmaf(h[2][bz], cell.w[0][bx] * cell.w[1][by], gq);
           }
-          gq = gq * pre_activate_grad(g.pre_act, tp.raw[q], g.density_scale);
-          if (gq != 0.0f) atomicAdd(d_dens + tp.idx[q], gq);
-        }
+          return gq;
+        });
       }
       return s.om;   // (T ends: every later term is 0)
     });
   }
 }
 
-template <int G>
-void launch_orientation_t(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
-                          const float* jitter, const float* rweight, float eps, float gscale, float* loss_out, float* ray_loss,
-                          float* d_dens, void* scratch, hipStream_t st) {
-  const long long nb = group_blocks<WaveRectTile<G>>(c);
-  double* partial = loss_out ? (double*)scratch : nullptr;
-  if (d_dens)
-    orientation_kernel<G, true><<<(unsigned)nb, kOrientThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, rweight, eps, gscale,
-                                                                         ray_loss, partial, d_dens);
-  else
-    orientation_kernel<G, false><<<(unsigned)nb, kOrientThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, rweight, eps, gscale,
-                                                                          ray_loss, partial, d_dens);
-  if (loss_out) launch_partial_mean(partial, nb, c.R, loss_out, st);
-}
-
 }  // namespace
-
-thread_local int tl_orientation_lanes = 0;
-
-// one partial per block, and a launch never has more blocks than rays (every pixel tile holds at least one pixel)
-size_t orientation_scratch_bytes(long long R) { return sizeof(double) * (size_t)(R > 0 ? R : 0) + 256; }
 
 void launch_orientation(const DevGrid& g, const DevCfg& c, const float* dens, const float* rays_o, const float* rays_d,
                         const float* jitter, const float* rweight, float eps, float grad_scale, float* loss_out, float* ray_loss,
                         float* d_dens, void* scratch, hipStream_t st) {
-  const float gscale = (float)((double)grad_scale / (double)c.R);
-  switch (lanes_per_ray(c.R, tl_orientation_lanes)) {
-    case 1: launch_orientation_t<1>(g, c, dens, rays_o, rays_d, jitter, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    case 2: launch_orientation_t<2>(g, c, dens, rays_o, rays_d, jitter, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    case 4: launch_orientation_t<4>(g, c, dens, rays_o, rays_d, jitter, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-    default: launch_orientation_t<8>(g, c, dens, rays_o, rays_d, jitter, rweight, eps, gscale, loss_out, ray_loss, d_dens, scratch, st); break;
-  }
+  launch_ray_loss(c, tl_lane_pins.orientation, grad_scale, loss_out, d_dens, scratch, st,
+                  [&](auto G, auto GRAD, long long nb, float gscale, double* partial) {
+                    orientation_kernel<G(), GRAD()><<<(unsigned)nb, kOrientThreads, 0, st>>>(g, c, dens, rays_o, rays_d, jitter, rweight,
+                                                                                             eps, gscale, ray_loss, partial, d_dens);
+                  });
 }
 
 }  // namespace voxe

@@ -1,8 +1,10 @@
 // voxe_ray_march.hpp -- the density-only sample march ("The shared sample march").
 //
-// Seven calls walk the forward's exact samples over the RAW densities without rendering colour: voxe_render_normals,
-// voxe_visibility_accumulate, voxe_distortion_fwd_bwd, voxe_render_bwd_rays, voxe_lift_accumulate, voxe_depth_fwd_bwd and
-// voxe_orientation_fwd_bwd.  What ties them to the renderer lives here, once:
+// These calls walk the forward's exact samples over the RAW densities outside the renderer (their entries share the
+// sampling_call_* prologue of voxe_api.hip; this is the one list of them):
+//   voxe_render_normals, voxe_visibility_accumulate, voxe_lift_accumulate, voxe_render_bwd_rays, voxe_fisher_rays and the
+//   three ray losses voxe_distortion_fwd_bwd, voxe_depth_fwd_bwd, voxe_orientation_fwd_bwd (voxe_ray_loss.hpp)
+// What ties them to the renderer lives here, once:
 //   depth step : sample k sits at z_k = DepthGen::z(k); its interval is dl_k = z_{k+1} - z_k, kInfinity for the last sample
 //   cell       : p = o + d z, footprint(); a sample outside the box has sigma = 0 -> w = 0, T unchanged (the forward's rule)
 //   density    : 8 raw loads, v = sum_q pre(raw_q) t_q with t_q = (wx * wy) * wz and the corners ascending (gather()'s
@@ -14,6 +16,7 @@
 #pragma once
 
 #include <climits>
+#include <type_traits>
 
 #include "voxe_render_common.hpp"
 
@@ -76,6 +79,17 @@ inline int lanes_per_ray(long long R, int pinned) {
   for (int G = 1; G < 8; G <<= 1)
     if (R * G >= (1ll << 20)) return G;
   return 8;
+}
+
+// the launch of a lanes-per-ray kernel: f(std::integral_constant<int, G>) for G in {1, 2, 4, 8}
+template <class F>
+inline void for_lanes(int G, F&& f) {
+  switch (G) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
 }
 
 // lane j's contiguous block of the ray's S samples, cut to the samples inside the box (empty: k_lo > k_hi)

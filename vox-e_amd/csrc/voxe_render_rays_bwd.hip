@@ -298,31 +298,21 @@ __global__ __launch_bounds__(kRayThreads) void render_rays_bwd_kernel(DevGrid g,
   }
 }
 
-template <int G, int NCU>
-void launch_t(const DevGrid& g, const DevCfg& c, const RayBwdArgs& a, hipStream_t st) {
-  render_rays_bwd_kernel<G, NCU><<<(unsigned)group_blocks<WaveRectTile<G>>(c), kRayThreads, 0, st>>>(g, c, a);
-}
-
 template <int NCU>
 void launch_g(int G, const DevGrid& g, const DevCfg& c, const RayBwdArgs& a, hipStream_t st) {
-  switch (G) {
-    case 1: launch_t<1, NCU>(g, c, a, st); break;
-    case 2: launch_t<2, NCU>(g, c, a, st); break;
-    case 4: launch_t<4, NCU>(g, c, a, st); break;
-    default: launch_t<8, NCU>(g, c, a, st); break;
-  }
+  for_lanes(G, [&](auto L) {
+    render_rays_bwd_kernel<L(), NCU><<<(unsigned)group_blocks<WaveRectTile<L()>>(c), kRayThreads, 0, st>>>(g, c, a);
+  });
 }
 
 }  // namespace
-
-thread_local int tl_rays_bwd_lanes = 0;
 
 void launch_render_rays_bwd(const DevGrid& g, const DevCfg& c, int deg, int diffuse, const float* dens, const float* feat,
                             const float* rays_o, const float* rays_d, const float* jitter, const float* g_col,
                             const float* g_depth, const float* g_acc, float* d_o, float* d_d, int accumulate, hipStream_t st) {
   const int ncm = (deg + 1) * (deg + 1);
   const RayBwdArgs a{dens, feat, rays_o, rays_d, jitter, g_col, g_depth, g_acc, d_o, d_d, accumulate, ncm};
-  const int G = lanes_per_ray(c.R, tl_rays_bwd_lanes);
+  const int G = lanes_per_ray(c.R, tl_lane_pins.rays_bwd);
   switch (diffuse ? 1 : ncm) {
     case 1: launch_g<1>(G, g, c, a, st); break;
     case 4: launch_g<4>(G, g, c, a, st); break;
