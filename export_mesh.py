@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "vox-e_amd"))
 
 from thre3d_atom.modules.volumetric_model import create_volumetric_model_from_saved_model_attn  # noqa: E402
+from thre3d_atom.thre3d_reprs.compression import load_uncompressed_checkpoint  # noqa: E402
 from thre3d_atom.thre3d_reprs.constants import STATE_DICT, THRE3D_REPR, u_ATTN  # noqa: E402
 from thre3d_atom.thre3d_reprs.geometry import vertex_normals  # noqa: E402
 from thre3d_atom.thre3d_reprs.mesh import default_level, extract_mesh, save_ply  # noqa: E402
@@ -43,7 +44,7 @@ def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
     device = torch.device("cuda")
     path = Path(cfg.model_path)
-    has_attn = u_ATTN in torch.load(path, map_location="cpu", weights_only=False)[THRE3D_REPR][STATE_DICT]
+    has_attn = u_ATTN in load_uncompressed_checkpoint(path)[THRE3D_REPR][STATE_DICT]
     if cfg.edit_region_only and not has_attn:
         raise click.UsageError(f"{path} holds no keep grid (attn): --edit_region_only needs a refined model")
     vol_mod, extra = create_volumetric_model_from_saved_model_attn(path, create_voxel_grid_from_saved_info_dict_attn,

@@ -749,6 +749,45 @@ int voxe_lift_accumulate(const VoxeGridDesc* grid, const VoxeRenderCfg* cfg,
 int voxe_lift_debug_merge(int32_t mode);
 
 /* ------------------------------------------------------------------------------------------------
+ * Vector quantisation of feature vectors against a codebook (additive; still ABI v13), DESIGN.md section 4.25 "Compression".
+ *   Both calls: N points of F channels, K codewords; F in 1..64, K in 1..65536, 0 <= N < 2^31 (VOXE_ERR_BAD_SHAPE otherwise,
+ *   checked first); N == 0: VOXE_OK, no launch, no pointer is looked at; otherwise a NULL pointer other than `dist` gives
+ *   VOXE_ERR_NULL_POINTER.  All inputs finite.  Caller's stream, no host synchronisation, no allocation, no workspace.
+ *   voxe_vq_assign: index[n] (int32 [N]) is a codeword k that minimises the float32 score
+ *           s(n, k) = |c_k|^2 - 2 x_n . c_k
+ *       evaluated on the matrix cores as the chain  s = fma(-2 c_kj, x_nj, s)  over ascending channel j, started at
+ *       code_norm[k] = sum_j c_kj^2 (plain float32 sum of the rounded squares, ascending j), which a pre-pass of the same call
+ *       writes into code_norm (f32 [K], every element).  Among codewords whose float32 scores are bit-equal the lowest k wins;
+ *       the scores of duplicated codewords are bit-equal, so the first copy wins.  The arg-min is taken inside the kernel: no
+ *       N x K intermediate exists and nothing but code_norm, index and dist is written.  The result does not depend on N, on the
+ *       point's position in the batch or on what the outputs held before: two calls return the same bits.
+ *       dist[n] (f32 [N], or NULL), is recomputed after the choice for k = index[n] as the plain float32 sum
+ *           d = 0;  for j = 0 .. F-1:  u = x_nj - c_kj;  d = d + u * u        each operation rounded, no FMA
+ *       so a float32 loop on the host reproduces it bit for bit given the index.  It is exactly 0 for a point equal to its
+ *       codeword, which the score s (a difference of large terms) cannot promise.
+ *   voxe_vq_accumulate: the weighted centroid sums in the fixed point of voxe_lift_accumulate.  For every point n with
+ *       k = index[n] in 0..K-1:
+ *           sum_w[k]     += q(w_n)
+ *           sum_wx[k, j] += q(w_n * x_nj)       j = 0 .. F-1, the product rounded to float32
+ *           q(x) = (int64) round-to-nearest-even(x * 2^32)
+ *       with 64-bit integer atomics: integer addition is associative, so the result is the same bit for bit whatever the order
+ *       of points, lanes, waves and launches -- shuffled points, the call split in two and both kernel variants agree exactly.
+ *       A contribution whose q is 0 is skipped (an exact no-op).  Requirements: |x| <= 1 and 0 <= w <= 1 (a codeword then has
+ *       room for 2^31 full-size contributions).  The call ACCUMULATES into sum_wx (int64 [K,F]) and sum_w (int64 [K]); the
+ *       caller zeroes them first.  A point whose index lies outside 0..K-1 deposits nothing and no memory outside the sums is
+ *       touched; the call has no status word to report it through, so it is the caller who validates the index (the Python
+ *       wrapper does, and answers with VOXE_ERR_BAD_SHAPE).
+ *   voxe_vq_debug_merge: a test aid.  The accumulate kernel has two variants that return identical bits: one atomic per lane
+ *       and channel (1), and one that first sums, inside a wave, each run of consecutive lanes with the same index (2): on
+ *       points sorted by index a wave then issues one atomic per run.  0 = the shipped choice (DESIGN.md 4.25 holds the
+ *       measurement).  Pins the calling thread's later calls; any other value: VOXE_ERR_BAD_SHAPE.                            */
+int voxe_vq_assign(const float* points /* [N,F] */, int64_t N, int32_t F, const float* codebook /* [K,F] */, int32_t K,
+                   float* code_norm /* [K], written */, int32_t* index /* [N] */, float* dist /* [N] or NULL */, void* stream);
+int voxe_vq_accumulate(const float* points /* [N,F] */, const float* weights /* [N] */, const int32_t* index /* [N] */,
+                       int64_t N, int32_t F, int32_t K, int64_t* sum_wx /* [K,F] */, int64_t* sum_w /* [K] */, void* stream);
+int voxe_vq_debug_merge(int32_t mode);
+
+/* ------------------------------------------------------------------------------------------------
  * Distortion loss on rays (additive; still ABI v13), DESIGN.md section 4.11 "Distortion".
  *   The samples z_k, the inside test, sigma_k, delta_k and the weights w_k = T_k alpha_k (last dl = 1e10) are those of
  *   voxe_render_fwd / voxe_render_normals / voxe_visibility_accumulate for the same rays, cfg and jitter / (seed, rng_offset);

@@ -14,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "vox-e_amd"))
 
 from thre3d_atom.modules.volumetric_model import create_volumetric_model_from_saved_model  # noqa: E402
+from thre3d_atom.thre3d_reprs.compression import load_uncompressed_checkpoint  # noqa: E402
 from thre3d_atom.thre3d_reprs.constants import STATE_DICT, THRE3D_REPR, u_DENSITIES  # noqa: E402
 from thre3d_atom.thre3d_reprs.visibility import accumulate_visibility, prune_voxel_grid_, visibility_cameras  # noqa: E402
 from thre3d_atom.thre3d_reprs.voxels import create_voxel_grid_from_saved_info_dict  # noqa: E402
@@ -32,6 +33,9 @@ def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
     device = torch.device("cuda")
     path = Path(cfg.model_path)
+    # the checkpoint as it is on disk: its densities are replaced below and every other entry (features, keep grid, configs,
+    # extra info) is written back untouched (a compressed checkpoint is refused here, before any work)
+    data = load_uncompressed_checkpoint(path)
     vol_mod, extra = create_volumetric_model_from_saved_model(path, create_voxel_grid_from_saved_info_dict, device=device)
     poses, intrinsics = visibility_cameras(extra, cfg.data_path, cfg.num_views)
     overrides = {}
@@ -46,9 +50,6 @@ def main(**kwargs) -> None:
     grid = vol_mod.thre3d_repr
     changed = prune_voxel_grid_(grid, keep)
     kept = int(keep.sum())
-    # the checkpoint as it was loaded, with the densities replaced: every other entry (features, keep grid, configs, extra
-    # info) is written back untouched
-    data = torch.load(path, map_location="cpu", weights_only=False)
     state = data[THRE3D_REPR][STATE_DICT]
     state[u_DENSITIES] = grid.densities.detach().to(device="cpu", dtype=state[u_DENSITIES].dtype)
     out = Path(cfg.output_path)

@@ -15,6 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "vox-e_amd"))
 
+from thre3d_atom.thre3d_reprs.compression import load_uncompressed_checkpoint  # noqa: E402
 from thre3d_atom.thre3d_reprs.constants import CONFIG_DICT, STATE_DICT, THRE3D_REPR, u_ATTN, u_DENSITIES, u_FEATURES  # noqa: E402
 from thre3d_atom.thre3d_reprs.transform import compose_voxel_grids_, default_output_lattice, transform_voxel_grid  # noqa: E402
 from thre3d_atom.thre3d_reprs.voxels import VoxelGrid  # noqa: E402
@@ -87,13 +88,13 @@ def main(**kwargs) -> None:
     cfg = type("Config", (), kwargs)
     device = torch.device("cuda")
     R = rotation_from_options(cfg.rotate_axis, cfg.rotate_degrees, cfg.quarter_turns, cfg.mirror)
-    data = torch.load(Path(cfg.model_path), map_location="cpu", weights_only=False)
+    data = load_uncompressed_checkpoint(Path(cfg.model_path))
     grid = _grid_of(data, device)
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     if cfg.into is not None:
         if cfg.output_dims is not None:
             raise click.UsageError("--output_dims does not apply with --into: the other checkpoint's lattice is kept")
-        data = torch.load(Path(cfg.into), map_location="cpu", weights_only=False)
+        data = load_uncompressed_checkpoint(Path(cfg.into))
         out_grid = _grid_of(data, device)
         start.record()
         taken = compose_voxel_grids_(out_grid, grid, R, cfg.translate, cfg.scale)

@@ -1562,6 +1562,36 @@ int voxe_lift_debug_merge(int32_t mode) {
   return VOXE_OK;
 }
 
+// ---- vector quantisation against a codebook ----------------------------------------------------------------
+static bool vq_shape_ok(int64_t N, int32_t F, int32_t K) {
+  return N >= 0 && N < (1LL << 31) && F >= 1 && F <= 64 && K >= 1 && K <= 65536;
+}
+
+int voxe_vq_assign(const float* points, int64_t N, int32_t F, const float* codebook, int32_t K, float* code_norm, int32_t* index,
+                   float* dist, void* stream) {
+  if (!vq_shape_ok(N, F, K)) return VOXE_ERR_BAD_SHAPE;
+  if (N == 0) return VOXE_OK;
+  if (!points || !codebook || !code_norm || !index) return VOXE_ERR_NULL_POINTER;
+  launch_vq_assign(points, N, F, codebook, K, code_norm, index, dist, (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_vq_accumulate(const float* points, const float* weights, const int32_t* index, int64_t N, int32_t F, int32_t K,
+                       int64_t* sum_wx, int64_t* sum_w, void* stream) {
+  if (!vq_shape_ok(N, F, K)) return VOXE_ERR_BAD_SHAPE;
+  if (N == 0) return VOXE_OK;
+  if (!points || !weights || !index || !sum_wx || !sum_w) return VOXE_ERR_NULL_POINTER;
+  launch_vq_accumulate(points, weights, index, N, F, K, reinterpret_cast<long long*>(sum_wx), reinterpret_cast<long long*>(sum_w),
+                       (hipStream_t)stream);
+  return finish();
+}
+
+int voxe_vq_debug_merge(int32_t mode) {
+  if (mode < 0 || mode > 2) return VOXE_ERR_BAD_SHAPE;
+  tl_vq_merge = mode;
+  return VOXE_OK;
+}
+
 // ---- the density ray losses ("What the ray losses share") ---------------------------------------------------
 // The common tail of their entries, behind an entry's own checks: the scratch of the mean, the clear of d_densities when the
 // call does not accumulate, and the call that has nothing to launch.  *done: the entry returns the status

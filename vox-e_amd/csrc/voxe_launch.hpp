@@ -332,4 +332,11 @@ void launch_voxelize(const float* vertices, long long V, const int32_t* faces, l
                      int Y, int Z, const float* aabb_lo, const float* aabb_hi, float h, float* sdf, int32_t* nearest,
                      float* colours, uint8_t* inside, int64_t* stats, void* scratch, hipStream_t st);
 
+// voxe_vq.hip: vector quantisation against a codebook; arguments validated by the API
+extern thread_local int tl_vq_merge;   // test aid (voxe_vq_debug_merge): 1 = one atomic per lane, 2 = run merge, 0 = shipped
+void launch_vq_assign(const float* points, long long N, int F, const float* codebook, int K, float* code_norm, int32_t* index,
+                      float* dist, hipStream_t st);
+void launch_vq_accumulate(const float* points, const float* weights, const int32_t* index, long long N, int F, int K,
+                          long long* sum_wx, long long* sum_w, hipStream_t st);
+
 }  // namespace voxe

@@ -31,6 +31,7 @@ from thre3d_atom.thre3d_reprs.constants import (
     STATE_DICT,
     THRE3D_REPR,
 )
+from thre3d_atom.thre3d_reprs.compression import COMPRESSED, expand_checkpoint_
 from thre3d_atom.thre3d_reprs.renderers import RenderConfig, RenderProcedure, render_sh_voxel_grid_attn
 from thre3d_atom.utils.constants import EXTRA_ACCUMULATED_WEIGHTS, EXTRA_INFO
 from thre3d_atom.utils.imaging_utils import CameraIntrinsics, CameraPose
@@ -231,7 +232,10 @@ def _load_model(model_path: Path, make_repr, device) -> Tuple[VolumetricModel, D
     # checkpoints hold pickled callables/classes (render procedure, activations), which torch >= 2.6
     # refuses under its default weights_only=True
     model_data = torch.load(model_path, map_location="cpu", weights_only=False)
-    render_config = model_data[RENDER_CONFIG_TYPE](**model_data[RENDER_CONFIG])
+    if COMPRESSED in model_data[THRE3D_REPR]:
+        # a compressed checkpoint: back to an ordinary state dict before the representation is made
+        expand_checkpoint_(model_data)
+    render_config =model_data[RENDER_CONFIG_TYPE](**model_data[RENDER_CONFIG])
     model = VolumetricModel(
         thre3d_repr=make_repr(model_data),
         render_procedure=model_data[RENDER_PROCEDURE],

@@ -305,6 +305,10 @@ HIP_ONLY = {
                                 C.POINTER(C.c_float), C.c_float, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     # per-voxel Fisher information of the rendered colours (additive, still ABI v13)
     "fisher_rays": (C.c_int, [_GD, _RC, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    # vector quantisation against a codebook (additive, still ABI v13)
+    "vq_assign": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
+    "vq_accumulate": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "vq_debug_merge": (C.c_int, [C.c_int32]),
 }
 
 CPU_ONLY = {

@@ -16,7 +16,7 @@ INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
 LIB = os.path.join(HERE, "libvoxe_hip.so")
 OBJ_DIR = os.path.join(HERE, "_obj")
 
-SOURCES = ["voxe_render.hip", "voxe_grid_step.hip", "voxe_render_tile.hip", "voxe_render_tile4.hip", "voxe_render_tilew.hip", "voxe_render_scatter.hip", "voxe_render_region.hip", "voxe_grid_ops.hip", "voxe_refine.hip", "voxe_mesh.hip", "voxe_normals.hip", "voxe_visibility.hip", "voxe_lift.hip", "voxe_distortion.hip", "voxe_depth.hip", "voxe_orientation.hip", "voxe_exposure.hip", "voxe_robust.hip", "voxe_render_rays_bwd.hip", "voxe_fisher.hip", "voxe_transform.hip", "voxe_camera.hip", "voxe_background.hip", "voxe_ssim.hip", "voxe_voxelize.hip", "voxe_api.hip"]
+SOURCES = ["voxe_render.hip", "voxe_grid_step.hip", "voxe_render_tile.hip", "voxe_render_tile4.hip", "voxe_render_tilew.hip", "voxe_render_scatter.hip", "voxe_render_region.hip", "voxe_grid_ops.hip", "voxe_refine.hip", "voxe_mesh.hip", "voxe_normals.hip", "voxe_visibility.hip", "voxe_lift.hip", "voxe_distortion.hip", "voxe_depth.hip", "voxe_orientation.hip", "voxe_exposure.hip", "voxe_robust.hip", "voxe_render_rays_bwd.hip", "voxe_fisher.hip", "voxe_vq.hip", "voxe_transform.hip", "voxe_camera.hip", "voxe_background.hip", "voxe_ssim.hip", "voxe_voxelize.hip", "voxe_api.hip"]
 HEADERS = ["voxe_device.hpp", "voxe_launch.hpp", "voxe_grid_elem.hpp", "voxe_render_common.hpp", "voxe_ray_march.hpp", "voxe_ray_loss.hpp", "voxe_tile_window.hpp", "voxe_mc_table.hpp"]
 
 # -ffp-contract=off : the voxel-index arithmetic must round like the reference (no implicit FMA)

@@ -344,6 +344,77 @@ def lift_debug_merge(mode: int) -> None:
 
 
 # ------------------------------------------------------------------------------------------------
+# vector quantisation against a codebook: plain buffers, no workspace, not differentiable
+# ------------------------------------------------------------------------------------------------
+VQ_MERGE_SHIPPED, VQ_MERGE_PER_LANE, VQ_MERGE_RUNS = 0, 1, 2   # voxe_vq_debug_merge
+VQ_MAX_CHANNELS, VQ_MAX_CODEWORDS = 64, 65536
+
+
+def _vq_points(entry: str, points: torch.Tensor) -> Tuple[int, int]:
+    require_device(points, f"{entry} (points)")
+    if points.dim() != 2:
+        raise VoxeError(f"{entry}: points must be [N,F]; got {tuple(points.shape)}")
+    _require_buffer(entry, "points", points, device=points.device)
+    return int(points.shape[0]), int(points.shape[1])
+
+
+def vq_assign_(points: torch.Tensor, codebook: torch.Tensor, index: Optional[torch.Tensor] = None,
+               dist: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """voxe_vq_assign: index[n] = the codeword of `codebook` ([K,F] float32) nearest to points[n] ([N,F] float32) by the float32
+    score |c|^2 - 2 x.c on the matrix cores, lowest k among bit-equal scores; dist[n] = the plain float32 squared distance to it.
+    `index` (int32 [N]) and `dist` (float32 [N]) are written in place when given; index is allocated when None, dist is left
+    out when None.  Returns (index, dist).  F in 1..64, K in 1..65536; all values finite."""
+    N, F = _vq_points("vq_assign_", points)
+    device = points.device
+    if codebook.dim() != 2 or codebook.shape[1] != F:
+        raise VoxeError(f"vq_assign_: codebook must be [K,F={F}]; got {tuple(codebook.shape)}")
+    _require_buffer("vq_assign_", "codebook", codebook, device=device)
+    K = int(codebook.shape[0])
+    ensure_gfx950(device)
+    with torch.cuda.device(device):
+        if index is None:
+            index = torch.empty((N,), dtype=torch.int32, device=device)
+        _require_buffer("vq_assign_", "index", index, shape=(N,), device=device, dtype=torch.int32)
+        if dist is not None:
+            _require_buffer("vq_assign_", "dist", dist, shape=(N,), device=device)
+        code_norm = torch.empty((max(K, 1),), dtype=torch.float32, device=device)
+        check(lib().voxe_vq_assign(ptr(points), N, F, ptr(codebook), K, ptr(code_norm), ptr(index), ptr(dist),
+                                   stream_ptr(device)), "voxe_vq_assign")
+    return index, dist
+
+
+def vq_accumulate_(points: torch.Tensor, weights: torch.Tensor, index: torch.Tensor, sum_wx: torch.Tensor,
+                   sum_w: torch.Tensor, check_index: bool = True) -> None:
+    """voxe_vq_accumulate: add, in place, q(w_n) to sum_w[index[n]] and q(w_n x_nj) to sum_wx[index[n], j], q(x) = rint(x * 2^32)
+    (LIFT_ONE units).  points [N,F] float32 with |x| <= 1, weights [N] float32 in [0, 1], index [N] int32, sum_wx [K,F] and
+    sum_w [K] int64.  The buffers ACCUMULATE: zero them before the first call.  The result is the same bit for bit however the
+    points are ordered or split over calls.  The library skips a point whose index is outside 0..K-1 and cannot say so; with
+    check_index (one host synchronisation) such an index is refused here with the library's bad-shape status instead."""
+    N, F = _vq_points("vq_accumulate_", points)
+    device = points.device
+    if sum_wx.dim() != 2 or sum_wx.shape[1] != F:
+        raise VoxeError(f"vq_accumulate_: sum_wx must be [K,F={F}]; got {tuple(sum_wx.shape)}")
+    K = int(sum_wx.shape[0])
+    _require_buffer("vq_accumulate_", "weights", weights, shape=(N,), device=device)
+    _require_buffer("vq_accumulate_", "index", index, shape=(N,), device=device, dtype=torch.int32)
+    _require_buffer("vq_accumulate_", "sum_wx", sum_wx, shape=(K, F), device=device, dtype=torch.int64)
+    _require_buffer("vq_accumulate_", "sum_w", sum_w, shape=(K,), device=device, dtype=torch.int64)
+    if check_index and N > 0:
+        lo, hi = (int(v) for v in torch.aminmax(index))
+        if lo < 0 or hi >= K:
+            check(abi.ERR_BAD_SHAPE, f"voxe_vq_accumulate: index spans {lo}..{hi}, outside 0..{K - 1}")
+    ensure_gfx950(device)
+    with torch.cuda.device(device):
+        check(lib().voxe_vq_accumulate(ptr(points), ptr(weights), ptr(index), N, F, K, ptr(sum_wx), ptr(sum_w),
+                                       stream_ptr(device)), "voxe_vq_accumulate")
+
+
+def vq_debug_merge(mode: int) -> None:
+    """test aid: pin the calling thread's later vq_accumulate_ calls to one kernel variant (VQ_MERGE_*); 0 = shipped"""
+    check(lib().voxe_vq_debug_merge(int(mode)), "voxe_vq_debug_merge")
+
+
+# ------------------------------------------------------------------------------------------------
 # rigid transform / re-gridding / composition of grids (DESIGN.md section 4.12): no workspace, not differentiable
 # ------------------------------------------------------------------------------------------------
 def make_resample(A, b, sh_rot=None, sh_degree: int = -1, density_pre_act: int = abi.ACT_IDENTITY, density_fill: float = 0.0,

@@ -16,7 +16,8 @@ from .cameras import (cast_rays, cast_rays_bwd, cast_rays_camera, cast_rays_came
 from .desc import make_grid_desc, make_render_cfg
 from .gridops import (LIFT_MERGE_PER_LANE, LIFT_MERGE_SHIPPED, LIFT_MERGE_WAVE, LIFT_ONE, cc_largest_k, extract_mesh,  # noqa: F401
                       graph_build, graphcut, grid_resample, lift_accumulate_, lift_debug_merge, make_resample, query_normals,
-                      render_normals, upsample_trilinear, visibility_accumulate_, visibility_mask, voxelize_mesh)
+                      render_normals, upsample_trilinear, visibility_accumulate_, visibility_mask, voxelize_mesh,
+                      VQ_MERGE_PER_LANE, VQ_MERGE_RUNS, VQ_MERGE_SHIPPED, vq_accumulate_, vq_assign_, vq_debug_merge)
 from .losses import (adam_step_, attn_masked_l1, density_correlation_loss, density_diff_loss, depth_fwd_bwd,  # noqa: F401
                      depth_loss, distortion_fwd_bwd, distortion_loss, exposure_apply, exposure_apply_bwd, exposure_fit_sums, exposure_fwd_bwd,
                      exposure_loss, feature_correlation_loss, fit_affine_colour, orientation_fwd_bwd, orientation_loss,
